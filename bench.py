@@ -11,6 +11,13 @@ independent, so two are kept in flight (tracer.SweepPipeline): the next pass's t
 beside the drain of the current trace and its combine runs beside the next trace; the timed region
 brackets all K passes, combines included.  Inputs are resident in HBM before the timed region.  The
 workload is fixed as N grows (60 beams sharded N ways) -> "scaling": "strong".  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up passes, the K timed passes, the result line.  Everything
+else the benchmark measures runs only with --full, after the timed region: the deposit windows' diagnostics and the
+roofline object, the trace launch alone (N > 1), the reference's dense grid layout, the CBET leg and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed pass computed, the combined deposition grid, as .npy files (see
+dump_outputs); the inputs are fixed, so two builds of the project can be compared output for output.
 """
 import argparse
 import json
@@ -353,6 +360,47 @@ def dense_layout_times(api, RayTracer, SweepPipeline, p, r, ne, te, bn, samples)
                     "(config.edep_row_pitch)"}
 
 
+DUMP_SAMPLE_CELLS = 4000000   # fp64 cells of the grid written by --dump-outputs (32 MB); smaller grids are written whole
+DUMP_SEED = 20261016
+
+
+def dump_outputs(outdir, pipe, p, world, rank, emulated_share):
+    """--dump-outputs: the combined (nx+2, ny+2, nz+2) fp64 deposition grid of the last timed pass -- what a caller of the
+    pass receives -- gathered from every rank's slab (a --shard-of run: the share's own, uncombined grid), written by rank 0
+    as float64 .npy files:
+        edep_sample.npy       the grid's cells at a fixed, seeded sample of flat indices (np.unique of DUMP_SAMPLE_CELLS
+                              draws from default_rng(DUMP_SEED), ascending), or every cell when the grid has no more
+        edep_plane_sums.npy   the sum over each x plane of the whole grid (nx+2 values: every cell counts)
+    The sample depends on the grid size only, not on N, so lines of any rank count compare."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    b = (pipe.passes - 1) % 2
+    if emulated_share:
+        full = pipe.grids[b]
+    else:
+        full = pipe.slab_store[b]
+        if world > 1:
+            nccl = dist.get_backend() == "nccl"
+            mine = full if nccl else full.cpu()           # gloo has no device path: gather through the host
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            full = torch.cat(parts).to(full.device)
+    if rank != 0:
+        return
+    grid = full[: p.nx + 2, : p.ny + 2, : p.nz + 2].contiguous()   # (the plane padding and the padded rows cut off)
+    flat = grid.reshape(-1)
+    total = flat.numel()
+    if total <= DUMP_SAMPLE_CELLS:
+        idx = np.arange(total)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE_CELLS))
+    sample = flat[torch.from_numpy(idx).to(flat.device)]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "edep_sample.npy"), sample.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(outdir, "edep_plane_sums.npy"), grid.sum(dim=(1, 2)).cpu().numpy().astype(np.float64))
+
+
 def device_identity(torch, index):
     pr = torch.cuda.get_device_properties(index)
     uuid = getattr(pr, "uuid", None)
@@ -379,14 +427,20 @@ def main():
                     "counter profiles of profiles/r*/traffic.json are collected")
     ap.add_argument("--rank-timeout", type=int, default=420, help="--gpus N without a launcher: seconds the N ranks may take "
                     "before the parent terminates them and prints their last stderr lines (exit code 124)")
-    ap.add_argument("--dense-samples", type=int, default=5, help="N = 1: fresh (context, grid) allocations the trace is timed on "
-                    "with the reference's dense edep rows (reported as dense_layout, outside the timed region); 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cbet", action="store_true", help="skip the (unpinned) CBET-iteration leg reported beside the headline")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what the headline does not "
+                    "need: window diagnostics + roofline, the trace alone (N > 1), dense_layout, the CBET leg, the CPU baseline")
+    ap.add_argument("--dense-samples", type=int, default=5, help="--full, N = 1: fresh (context, grid) allocations the trace is "
+                    "timed on with the reference's dense edep rows (reported as dense_layout, outside the timed region); 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-cbet", action="store_true", help="--full: skip the (unpinned) CBET-iteration leg reported beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed pass's deposition grid as .npy "
+                    "files into DIR (a seeded sample of its cells and its plane sums, float64; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: this process becomes the launcher (the counterpart of the one
         # OpenMP thread per GPU of main.cu:166-176).  It never touches the GPU -- the ranks are fresh children of
@@ -464,13 +518,18 @@ def main():
     cnt = pipe.counters(reset=True)
     slab = pipe.finish()
     slab_sum = float(slab.sum().item())
-    # the deposit windows' diagnostics: ONE more launch of this rank's share, un-timed, with cbet_params.window_stats = 1
-    # (the timed launches count ray-steps and rays only); tot[1], tot[4:9] and tot[10] are that launch's counts
-    diag = pipe.window_diagnostics()
-    tot = torch.tensor([float(cnt.ray_steps), float(diag.global_atomics), elapsed,
-                        sum(a.elapsed_time(b) for a, b in pipe.kernel_events) * 1e-3, float(diag.lds_evictions),
-                        float(diag.wave_steps), float(diag.wave_steps_miss), float(diag.wave_steps_wide),
-                        float(diag.slabs_retired), slab_sum, float(diag.ray_steps)],
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe, p, world, rank, shards != world)
+    # --full: the deposit windows' diagnostics, ONE more launch of this rank's share, un-timed, with
+    # cbet_params.window_stats = 1 (the timed launches count ray-steps and rays only); tot[1], tot[4:9] and tot[10] are
+    # that launch's counts (zeros in a plain run, which reports no roofline)
+    diag = pipe.window_diagnostics() if args.full else None
+    dg = [0.0] * 7 if diag is None else [float(diag.global_atomics), float(diag.lds_evictions), float(diag.wave_steps),
+                                         float(diag.wave_steps_miss), float(diag.wave_steps_wide),
+                                         float(diag.slabs_retired), float(diag.ray_steps)]
+    tot = torch.tensor([float(cnt.ray_steps), dg[0], elapsed,
+                        sum(a.elapsed_time(b) for a, b in pipe.kernel_events) * 1e-3, dg[1],
+                        dg[2], dg[3], dg[4], dg[5], slab_sum, dg[6]],
                        dtype=torch.float64, device="cuda")
     tmax = tot.clone()
     if world > 1:
@@ -481,15 +540,17 @@ def main():
     elapsed_max = tmax[2].item()
     kernel_s_rank = tmax[3].item() / max(1, args.steps)   # slowest rank's average trace-kernel time (stretched when traces overlap)
     value = steps_total / elapsed_max
-    # what the launch needs when nothing runs beside it: the duration the roofline is priced with when traces overlap
-    alone = torch.tensor([pipe.time_trace_alone() if shards > 1 else kernel_s_rank], dtype=torch.float64, device="cuda")
-    if world > 1:
-        dist.all_reduce(alone, op=dist.ReduceOp.MAX)
-    kernel_s_alone = alone.item()
+    # --full: what the launch needs when nothing runs beside it, the duration the roofline is priced with when traces
+    # overlap (one trace stream, N = 1: the same measurement as the pipeline's events)
+    kernel_s_alone = kernel_s_rank if shards == 1 else None
+    if args.full and shards > 1:
+        alone = torch.tensor([pipe.time_trace_alone()], dtype=torch.float64, device="cuda")
+        if world > 1:
+            dist.all_reduce(alone, op=dist.ReduceOp.MAX)
+        kernel_s_alone = alone.item()
 
     if rank == 0:
         steps_per_launch = steps_total / args.steps / world   # ray-steps one launch processes (avg rank)
-        traffic = measured_traffic(workload, args.variant, shards)
         out = {
             "metric": "ray-steps/sec, OMEGA 60-beam %d^3 sweep" % n,
             "value": value, "unit": "ray-steps/s", "n_gpus": world, "steps": args.steps,
@@ -505,16 +566,20 @@ def main():
                        **({"shard_emulation": "rank %d of %d on one GPU, no process group (--shard-of): `value` is this "
                                               "share's rate, a profiling aid, not a bench line" % (shards // 2, shards)}
                           if shards != world else {})},
-            "roofline": roofline(traffic, steps_per_launch, kernel_s_alone, tot, steps_total),
             "pipeline": {"passes_in_flight": 2, "traces_overlap": bool(pipe.overlap_traces),
-                         "kernel_ms_in_pipeline": 1e3 * kernel_s_rank, "kernel_ms_alone": 1e3 * kernel_s_alone,
+                         "kernel_ms_in_pipeline": 1e3 * kernel_s_rank,
+                         "kernel_ms_alone": None if kernel_s_alone is None else 1e3 * kernel_s_alone,
                          "note": "N > 1: consecutive passes' trace kernels run on separate streams and overlap (the drain of "
                                  "one beside the head of the next), so the events around a launch in the pipeline measure a "
                                  "stretched duration (kernel_ms_in_pipeline); roofline.kernel_ms is kernel_ms_alone, the "
                                  "same launch timed after the run with nothing beside it, and the counter profile is the "
                                  "one collected for this share of the work (traffic.json shard_count); N = 1 keeps one "
-                                 "trace stream and the two are the same measurement"},
+                                 "trace stream and the two are the same measurement; N > 1 times the launch alone with "
+                                 "--full only"},
         }
+        if args.full:
+            traffic = measured_traffic(workload, args.variant, shards)
+            out["roofline"] = roofline(traffic, steps_per_launch, kernel_s_alone, tot, steps_total)
         distinct = sorted({(d["uuid"] or d["pci"], d["ordinal"]) for d in identities})
         out["ranks"] = {"process_group_ranks": world, "backend": (args.backend if world > 1 else None),
                         "rccl_ranks": (dist.get_world_size() if (world > 1 and args.backend == "nccl") else (1 if world == 1 else 0)),
@@ -522,12 +587,12 @@ def main():
                         "rehearsal": bool("CBET_BENCH_DEVICE" in os.environ or (world > 1 and args.backend != "nccl")),
                         "note": "devices = every rank's HIP device as that rank reports it, gathered over the process group; a "
                                 "rehearsal (ranks sharing one device, or gloo) is flagged and is not a multi-GPU measurement"}
-        if world == 1 and shards == 1 and args.dense_samples > 0:
+        if args.full and world == 1 and shards == 1 and args.dense_samples > 0:
             out["dense_layout"] = dense_layout_times(api, RayTracer, SweepPipeline, p, r, ne, te, bn, args.dense_samples)
-        if world == 1 and not args.no_cbet:
+        if args.full and world == 1 and not args.no_cbet:
             pipe.close()
             out["cbet"] = cbet_leg(api, tr, tr.new_grid(), n)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, r, ne, te, bn)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 for K in 2 4 8; do
   bash scripts/pmc.sh "$TAG/pmc_k$K" --shard-of $K > "$OUT/pmc_k$K.log" 2>&1; rc=$?; echo "pmc --shard-of $K rc=$rc"
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit $rc; fi
-  timeout -k 10 120 python3 bench.py --steps 10 --warmup 3 --shard-of $K --no-cbet --no-cpu-baseline --dense-samples 0 > "$OUT/bench_share_k$K.json" 2>/dev/null
+  timeout -k 10 120 python3 bench.py --full --steps 10 --warmup 3 --shard-of $K --no-cbet --no-cpu-baseline --dense-samples 0 > "$OUT/bench_share_k$K.json" 2>/dev/null
 done
 python3 scripts/shard_timing.py 256 > "$OUT/shard_timing.log" 2>/dev/null
 python3 scripts/launch_size_curve.py > "$OUT/launch_size_curve.log" 2>/dev/null

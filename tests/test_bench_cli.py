@@ -47,3 +47,43 @@ def test_ranks_that_hang_are_terminated_with_their_last_words():
     for rank in (0, 1):
         assert "[rank%d] rank %d: hanging on request" % (rank, rank) in run.stderr, run.stderr[-1500:]
     assert not [l for l in run.stdout.splitlines() if l.startswith("{")]
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed passes and ms_per_step divides by it: zero is refused before any GPU work."""
+    run = run_bench("--gpus", "1", "--steps", "0")
+    assert run.returncode != 0 and "--steps must be >= 1" in run.stderr
+    assert not [l for l in run.stdout.splitlines() if l.startswith("{")]
+
+
+def test_full_and_dump_outputs_are_options():
+    run = run_bench("--help")
+    assert run.returncode == 0
+    assert "--full" in run.stdout and "--dump-outputs" in run.stdout
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """dump_outputs on host tensors (a stand-in for the pipeline after its last pass): the grid is cut out of the padded
+    slab store, a grid larger than the sample budget is written as the same seeded sample every time, float64, and the
+    plane sums cover every cell."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_CELLS", 500)
+    p = types.SimpleNamespace(nx=10, ny=8, nz=6)
+    store = torch.arange(12 * 10 * 16, dtype=torch.float64).reshape(12, 10, 16)    # planes padded to 12, rows to 16
+    pipe = types.SimpleNamespace(passes=4, slab_store=[None, store], grids=[None, None])   # last pass: set 1
+    grid = store[:12, :10, :8].numpy()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pipe, p, world=1, rank=0, emulated_share=False)
+    a, b = (np.load(str(tmp_path / d / "edep_sample.npy")) for d in ("a", "b"))
+    assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert 0 < len(a) <= 500 and np.all(np.diff(a) > 0) and set(a) <= set(grid.ravel())
+    sums = np.load(str(tmp_path / "a" / "edep_plane_sums.npy"))
+    assert sums.dtype == np.float64 and np.array_equal(sums, grid.sum(axis=(1, 2)))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_CELLS", grid.size)                     # small enough: every cell
+    bench.dump_outputs(str(tmp_path / "c"), pipe, p, world=1, rank=0, emulated_share=False)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "edep_sample.npy")), grid.ravel())

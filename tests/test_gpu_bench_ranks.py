@@ -18,7 +18,7 @@ def test_two_rank_bench_rehearsal():
     env = dict(os.environ, CBET_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--grid", "64",
-           "--steps", "3", "--warmup", "1", "--no-cbet", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cbet", "--no-cpu-baseline"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stdout[-1500:] + run.stderr[-1500:]
     lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
@@ -42,7 +42,7 @@ def test_two_rank_line_carries_a_roofline():
     env = dict(os.environ, CBET_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--grid", "256",
-           "--steps", "2", "--warmup", "1", "--no-cbet", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cbet", "--no-cpu-baseline"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stdout[-1500:] + run.stderr[-1500:]
     out = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][0])
