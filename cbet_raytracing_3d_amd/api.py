@@ -104,6 +104,49 @@ class CbetReport(C.Structure):
     ]
 
 
+# ---- exit pass (cbet_trace_exits) ----------------------------------------------------------------
+RAY_LAUNCHED, RAY_CUTOFF, RAY_ESCAPED, RAY_TIMEOUT = 1, 2, 4, 8   # cbet_ray_exit.status bits
+TALLY_COLUMNS = ("launched", "gained", "absorbed", "escaped", "stranded", "unfinished", "n_rays", "n_escaped")
+
+
+class RayExit(C.Structure):
+    """cbet_ray_exit: one ray's state when it ended (80 bytes)."""
+    _fields_ = [
+        ("x", C.c_double), ("y", C.c_double), ("z", C.c_double),
+        ("vx", C.c_double), ("vy", C.c_double), ("vz", C.c_double),
+        ("uray", C.c_double), ("uray0", C.c_double), ("gained", C.c_double),
+        ("steps", C.c_int), ("status", C.c_int),
+    ]
+
+
+# the same record as a numpy structured dtype: view a downloaded [..., 10] float64 array with .view(EXIT_DTYPE)
+EXIT_DTYPE = np.dtype([(name, "<f8" if ct is C.c_double else "<i4") for name, ct in RayExit._fields_])
+assert EXIT_DTYPE.itemsize == C.sizeof(RayExit) == 80
+
+
+def farfield_bins(vx, vy, vz, ntheta, nphi):
+    """The bin coordinates cbet_farfield uses, (1 - vz/|v|)/2 * ntheta and (atan2(vy, vx) + pi)/(2 pi) * nphi, before the floor."""
+    vx, vy, vz = (np.asarray(v, dtype=np.float64) for v in (vx, vy, vz))
+    vn = np.sqrt(vx * vx + vy * vy + vz * vz)
+    return (1.0 - vz / vn) / 2.0 * ntheta, (np.arctan2(vy, vx) + np.pi) / (2.0 * np.pi) * nphi
+
+
+def farfield_numpy(records, ntheta, nphi):
+    """Host restatement of cbet_farfield on a structured array of records (EXIT_DTYPE): hist[ntheta][nphi]."""
+    r = np.asarray(records).reshape(-1)
+    want = RAY_LAUNCHED | RAY_ESCAPED
+    r = r[(r["status"] & want) == want]
+    ct, cp = farfield_bins(r["vx"], r["vy"], r["vz"], ntheta, nphi)
+
+    def idx(c, n):
+        c = np.where(c > 0.0, c, 0.0)
+        return np.minimum(np.floor(c), n - 1).astype(np.int64)
+
+    hist = np.zeros((ntheta, nphi))
+    np.add.at(hist, (idx(ct, ntheta), idx(cp, nphi)), r["uray"])
+    return hist
+
+
 # Every symbol include/cbet_mi355x.h declares; tests check the library exports all of them.
 EXPORTS = [
     "cbet_last_error", "cbet_version", "cbet_params_default", "cbet_derive",
@@ -116,6 +159,7 @@ EXPORTS = [
     "cbet_gain_params_default", "cbet_gain_constants", "cbet_trace_cbet", "cbet_gain_field",
     "cbet_cbet_workspace_bytes", "cbet_cbet_solve", "cbet_gain_field_slab", "cbet_gain_field_packed",
     "cbet_cbet_slab_workspace_bytes", "cbet_cbet_slab_workspace_bytes_parts", "cbet_pack_segments", "cbet_unpack_segments",
+    "cbet_context_list_length", "cbet_cbet_workspace_gain", "cbet_trace_exits", "cbet_exit_tally", "cbet_farfield",
 ]
 
 _lib = None
@@ -189,6 +233,13 @@ def lib():
     L.cbet_cbet_workspace_bytes.restype = C.c_size_t
     L.cbet_cbet_solve.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Params), C.POINTER(GainParams), vp, vp, vp,
                                   C.POINTER(CbetReport)]
+    L.cbet_context_list_length.argtypes = [vp, C.POINTER(C.c_long)]
+    L.cbet_cbet_workspace_gain.argtypes = [C.POINTER(Params), vp]
+    L.cbet_cbet_workspace_gain.restype = vp
+    L.cbet_trace_exits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
+                                   C.POINTER(Params), C.POINTER(GainParams), vp, vp]
+    L.cbet_exit_tally.argtypes = [vp, C.c_long, C.c_int, vp, vp]
+    L.cbet_farfield.argtypes = [vp, C.c_long, C.c_int, C.c_int, vp, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -340,6 +391,12 @@ class Context:
         arr = np.ascontiguousarray(slots, dtype=np.int32)
         _check(lib().cbet_context_set_launch_list(self._h, arr.ctypes.data_as(C.POINTER(C.c_int)), arr.size))
 
+    def list_length(self):
+        """L: entries of the current launch list (64 per bundle, holes included) -- the exit records' per-beam stride."""
+        n = C.c_long()
+        _check(lib().cbet_context_list_length(self._h, C.byref(n)))
+        return n.value
+
     def tables(self):
         a, b = C.c_void_p(), C.c_void_p()
         _check(lib().cbet_context_tables(self._h, C.byref(a), C.byref(b)))
@@ -457,6 +514,34 @@ def cbet_solve(te_data_g, r_data_g, ne_data_g, edep, bbeam_norm, beam_norm, pow_
                                  C.byref(params), C.byref(gain_params), _addr(workspace),
                                  ctx.handle if ctx is not None else None, _addr(stream), C.byref(rep)))
     return rep
+
+
+def cbet_workspace_gain(params, workspace):
+    """Device address of the converged gain inside a workspace cbet_solve has run in ([nbeams][(n+2)^3] doubles)."""
+    addr = lib().cbet_cbet_workspace_gain(C.byref(params), _addr(workspace))
+    if not addr:
+        raise CbetError(EINVAL, lib().cbet_last_error().decode("utf-8", "replace"))
+    return addr
+
+
+# ---- exit pass ---------------------------------------------------------------------------------------
+def trace_exits(ne3d, kappa3d, gain, exits, bbeam_norm, beam_norm, pow_r, phase_r, xconst, yconst, zconst, params,
+                gain_params, ctx, stream=None):
+    """cbet_trace_exits: one cbet_ray_exit record per ray into `exits` ([grid beams][L] records, device)."""
+    _check(lib().cbet_trace_exits(
+        _addr(ne3d), _addr(kappa3d), _addr(gain), _addr(exits), _addr(bbeam_norm), _addr(beam_norm), _addr(pow_r),
+        _addr(phase_r), xconst, yconst, zconst, C.byref(params), C.byref(gain_params) if gain_params is not None else None,
+        ctx.handle, _addr(stream)))
+
+
+def exit_tally(exits, L, nbeams, tally, stream=None):
+    """cbet_exit_tally: tally[nbeams][8] (TALLY_COLUMNS) overwritten with the per-beam energy balance."""
+    _check(lib().cbet_exit_tally(_addr(exits), L, nbeams, _addr(tally), _addr(stream)))
+
+
+def farfield(exits, n, ntheta, nphi, hist, stream=None):
+    """cbet_farfield: the escaped rays' energy among n records ADDED into hist[ntheta][nphi]."""
+    _check(lib().cbet_farfield(_addr(exits), n, ntheta, nphi, _addr(hist), _addr(stream)))
 
 
 def ray_tracing(te_profile, r_profile, ne_profile, edep, params, beam_norm=None, gpus=None, ngpu=1):

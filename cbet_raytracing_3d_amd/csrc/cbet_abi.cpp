@@ -556,6 +556,13 @@ int cbet_debug_bounds_violations(unsigned long long *out, int reset, void *strea
     return CBET_OK;
 }
 
+int cbet_context_list_length(const cbet_context *ctx, long *length)
+{
+    if (!ctx || !length) return fail(CBET_EINVAL, "NULL context/length");
+    *length = ctx->nlive;
+    return CBET_OK;
+}
+
 int cbet_context_tables(cbet_context *ctx, double **ne3d, double **kappa3d)
 {
     if (!ctx) return fail(CBET_EINVAL, "NULL context");
@@ -639,6 +646,7 @@ struct CbetHooks {
     int quantity = 0;
     double *beam_gain = nullptr;
     double max_exponent = 0.0;
+    bool exits = false;     // the exit pass (cbet_trace_exits): `edep` is the record array, no deposit
 };
 
 static int trace_impl(int b, unsigned nindices, const double *ne3d, const double *kappa3d,
@@ -714,6 +722,7 @@ static int trace_impl(int b, unsigned nindices, const double *ne3d, const double
     if (p->edep_zpitch > 0 && (p->per_beam_grids || cbet_hooks))
         return fail(CBET_EINVAL, "edep_zpitch applies to the plain path's single deposit grid (no per-beam grids, no CBET hooks)");
     a.grid_stride = (p->per_beam_grids || hooks.quantity != 0) ? d.edep_size : 0;  // field passes are always beam-resolved
+    if (hooks.exits) a.grid_stride = (long)kExitDoubles * ctx->nlive;            // exit records: L per beam (launch_trace_exit)
     // beam-resolved arrays may hold only the grids of beams [grid_beam0, grid_beam0 + grid_beams)
     const int gb_n = p->grid_beams > 0 ? p->grid_beams : p->nbeams, gb_0 = p->grid_beams > 0 ? p->grid_beam0 : 0;
     if ((a.grid_stride != 0 || hooks.gain) && (beam_lo < gb_0 || beam_hi > gb_0 + gb_n))
@@ -733,7 +742,7 @@ static int trace_impl(int b, unsigned nindices, const double *ne3d, const double
         if (int rc = step_records(ctx, p, ne3d, kappa3d, xconst, yconst, zconst, stream, false)) return rc;
         a.steprec = ctx->steprec;
     }
-    CBET_HIP(launch_trace(a, variant, p->force_wide_index != 0, (hipStream_t)stream));
+    CBET_HIP(launch_trace(a, hooks.exits ? kTraceExits : variant, p->force_wide_index != 0, (hipStream_t)stream));
     return CBET_OK;
 }
 
@@ -1062,6 +1071,58 @@ int cbet_cbet_solve(double *te_data_g, double *r_data_g, double *ne_data_g, doub
     }
     if (rc == CBET_OK && report) *report = rep;
     return rc;
+}
+
+const double *cbet_cbet_workspace_gain(const cbet_params *p, const void *workspace)
+{
+    if (!p || !workspace || validate(p) != CBET_OK) return nullptr;
+    const size_t hsize = (size_t)(p->nx + 2) * (p->ny + 2) * (p->nz + 2);
+    return (const double *)workspace + 4 * (size_t)p->nbeams * hsize;   // the layout of cbet_cbet_solve's workspace
+}
+
+// ---- exit pass ---------------------------------------------------------------
+int cbet_trace_exits(const double *ne3d, const double *kappa3d, const double *gain, cbet_ray_exit *exits,
+                     const double *bbeam_norm, const double *beam_norm, const double *pow_r, const double *phase_r,
+                     double xconst, double yconst, double zconst, const cbet_params *p, const cbet_gain_params *g,
+                     cbet_context *ctx, void *stream)
+{
+    if (int rc = validate(p)) return rc;
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (!exits) return fail(CBET_EINVAL, "NULL exit-record array");
+    if (p->absorption != 1)
+        return fail(CBET_EINVAL, "the exit pass needs absorbing mode (absorption = 1): in bookkeeping mode the increment is no energy loss");
+    if (gain && !g) return fail(CBET_EINVAL, "a gain grid needs gain params (max_exponent)");
+    if (g) {
+        if (int rc = validate_gain(p, g)) return rc;
+    }
+    // the trace's own checks and set-up (geometry, beam range against grid_beam0 / grid_beams, shards, step records);
+    // the deposit-grid options do not apply
+    cbet_params q = *p;
+    q.kernel_variant = CBET_KERNEL_LDS_WINDOW;
+    q.per_beam_grids = 0;
+    q.edep_zpitch = 0;
+    q.window_stats = 0;
+    if (q.beam_hi < 0) { q.beam_lo = 0; q.beam_hi = q.nbeams; }
+    CbetHooks h;
+    h.gain = gain; h.max_exponent = g ? g->max_exponent : 0.0; h.exits = true;
+    return trace_impl(0, (unsigned)ctx->d.nindices, ne3d, kappa3d, reinterpret_cast<double *>(exits), bbeam_norm,
+                      beam_norm, pow_r, phase_r, xconst, yconst, zconst, &q, ctx, stream, h);
+}
+
+int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, void *stream)
+{
+    if (!exits || !tally) return fail(CBET_EINVAL, "NULL exit records / tally");
+    if (L < 0 || nbeams < 0) return fail(CBET_EINVAL, "L = %ld, nbeams = %d", L, nbeams);
+    CBET_HIP(launch_exit_tally(exits, L, nbeams, tally, (hipStream_t)stream));
+    return CBET_OK;
+}
+
+int cbet_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, void *stream)
+{
+    if (!exits || !hist) return fail(CBET_EINVAL, "NULL exit records / histogram");
+    if (n < 0 || ntheta <= 0 || nphi <= 0) return fail(CBET_EINVAL, "n = %ld, ntheta = %d, nphi = %d", n, ntheta, nphi);
+    CBET_HIP(launch_farfield(exits, n, ntheta, nphi, hist, (hipStream_t)stream));
+    return CBET_OK;
 }
 
 }  // extern "C"

@@ -125,6 +125,13 @@ hipError_t audit_violations(unsigned long long *out, bool reset, hipStream_t str
 // variant: CBET_KERNEL_GLOBAL_ATOMICS, _LDS_COMBINE (cbet_kernels.hip) or _LDS_WINDOW (cbet_trace_window.hip)
 hipError_t launch_trace(const TraceArgs &a, int variant, bool force_idx64, hipStream_t stream);
 hipError_t launch_trace_window(const TraceArgs &a, bool force_idx64, hipStream_t stream);
+// Exit pass (cbet_trace_exit.hip): launch_trace with variant kTraceExits runs it -- TraceArgs.edep is then the record array
+// as doubles and grid_stride = kExitDoubles * L -- after the bounds-audit set-up every trace gets.
+constexpr int kTraceExits = 100;
+constexpr int kExitDoubles = 10;                // sizeof(cbet_ray_exit) / sizeof(double)
+hipError_t launch_trace_exit(const TraceArgs &a, bool force_idx64, hipStream_t stream);
+hipError_t launch_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, hipStream_t stream);
+hipError_t launch_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, hipStream_t stream);
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream);
 hipError_t launch_pack_segments(const double *src, long beam_stride, int hy, int hz, const int *seg, long nseg, double *out,
                                 hipStream_t stream);

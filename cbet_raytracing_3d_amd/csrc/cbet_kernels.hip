@@ -397,6 +397,7 @@ hipError_t launch_trace(const TraceArgs &a0, int variant, bool force_idx64, hipS
     }
 #endif
     if (variant == CBET_KERNEL_LDS_WINDOW) return launch_trace_window(a, force_idx64, stream);
+    if (variant == kTraceExits) return launch_trace_exit(a, force_idx64, stream);
     const long waves = a.item_count;
     if (waves <= 0) return hipSuccess;
     const dim3 grid((unsigned)waves);

@@ -51,6 +51,7 @@ class RayTracer:
             if t.numel() != self.params.nprofile:
                 raise ValueError("profile length != params.nprofile")
         self.ctx = api.Context(self.params, self.gpu)
+        self._launch_list = None        # set_launch_list(): the regrouped list (ray_ids())
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     def new_grid(self, per_beam=False, zpitch=None):
@@ -180,6 +181,69 @@ class RayTracer:
             rep = cbet_fixed_point(engine, gain_params, rank, world_size, group)
         rep["gain"] = engine.gain      # all beams (all-reduce loop) / this rank's beams (slab loop), whole grid
         return rep
+
+    # ---- exit pass (include/cbet_mi355x.h cbet_trace_exits) -----------------
+    def ray_ids(self):
+        """The context's current launch list (int32 [L]): slot li of every beam holds thread-ray id ray_ids()[li], -1 = idle."""
+        return api.live_ray_list(self.params) if self._launch_list is None else self._launch_list.copy()
+
+    def set_launch_list(self, slots):
+        """Regroup the bundles (cbet_context_set_launch_list); ray_ids() follows."""
+        self.ctx.set_launch_list(slots)
+        self._launch_list = np.ascontiguousarray(slots, dtype=np.int32).copy()
+
+    def new_exits(self):
+        """Zeroed exit records, float64 [nbeams, L, 10] (cbet_ray_exit: x, y, z, vx, vy, vz, uray, uray0, gained, then
+        steps / status in column 9 -- read them with .view(torch.int32)[..., 18:20])."""
+        return torch.zeros((self.params.nbeams, self.ctx.list_length(), 10), dtype=torch.float64, device=self.device)
+
+    def _check_exits(self, exits):
+        want = (self.params.nbeams, self.ctx.list_length(), 10)
+        if exits.dtype != torch.float64 or not exits.is_contiguous() or tuple(exits.shape) != want:
+            raise ValueError("exits must be a contiguous float64 tensor of shape %s (new_exits())" % (want,))
+
+    def trace_exits(self, exits, gain=None, gain_params=None, shard_index=0, shard_count=1, beam_lo=0, beam_hi=None,
+                    tabulate=True):
+        """The exit pass on torch's current stream: every traced ray's final state into `exits` (new_exits()); slots of
+        rays this launch does not trace are left as they are.  gain: [nbeams][(n+2)^3] gain coefficient (e.g. a CBET
+        solve's) -- the rays then gain energy as in the CBET deposition pass; gain_params defaults to
+        api.default_gain_params().  tabulate: fill the node tables from the profiles first, as launch() does."""
+        self._check_exits(exits)
+        if gain is not None:
+            if gain.dtype != torch.float64 or not gain.is_contiguous() or tuple(gain.shape) != (self.params.nbeams,) + self.grid_shape:
+                raise ValueError("gain must be a contiguous float64 tensor of shape %s" % ((self.params.nbeams,) + self.grid_shape,))
+            if gain_params is None:
+                gain_params = api.default_gain_params()
+        if tabulate:
+            self.tabulate()
+        p = self.params.copy(beam_lo=beam_lo, beam_hi=self.params.nbeams if beam_hi is None else beam_hi,
+                             shard_index=shard_index, shard_count=shard_count)
+        d = self.derived
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        api.trace_exits(None, None, gain, exits, self.d_bbeam_norm, self.d_beam_norm, self.d_pow_r, self.d_phase_r,
+                        d.xconst, d.yconst, d.zconst, p, gain_params, self.ctx, stream)
+        return exits
+
+    def energy_balance(self, exits):
+        """Per-beam energy balance of exit records: float64 [nbeams, 8], columns api.TALLY_COLUMNS (launched, gained,
+        absorbed, escaped, stranded, unfinished, n_rays, n_escaped); launched + gained = absorbed + escaped + stranded +
+        unfinished per beam.  Deterministic."""
+        self._check_exits(exits)
+        tally = torch.empty((self.params.nbeams, 8), dtype=torch.float64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        api.exit_tally(exits, exits.shape[1], self.params.nbeams, tally, stream)
+        return tally
+
+    def farfield(self, exits, ntheta, nphi, beams=None):
+        """The escaped light's far field: float64 [ntheta, nphi] of remaining energy by exit direction (equal solid angle
+        per polar bin, include/cbet_mi355x.h cbet_farfield), from all beams or the beams listed."""
+        self._check_exits(exits)
+        hist = torch.zeros((ntheta, nphi), dtype=torch.float64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L = exits.shape[1]
+        for b in (range(self.params.nbeams) if beams is None else beams):
+            api.farfield(exits[b], L, ntheta, nphi, hist, stream)
+        return hist
 
     def node_tables(self):
         """Copies of the context's node tables (ne3d, kappa3d) as numpy arrays, for tests."""

@@ -205,6 +205,12 @@ int cbet_context_counters(cbet_context *ctx, void *stream, cbet_counters *out, i
  */
 int cbet_context_set_launch_list(cbet_context *ctx, const int *list, long n);
 /*
+ * *length = L, the number of entries of the context's current launch list (holes included; 64 per bundle): the count
+ * cbet_live_ray_list reports, or the n of the last cbet_context_set_launch_list.  The per-beam stride of the exit
+ * records (cbet_trace_exits).
+ */
+int cbet_context_list_length(const cbet_context *ctx, long *length);
+/*
  * Device pointers of the context's own node tables (for tests / the 3-D plasma entry below).  They are writable:
  * the call marks the tables as modified, so the next launch that uses them (ne3d = kappa3d = NULL) rebuilds the
  * per-node step records it gathers from.  Call it again (or cbet_prepare_step_records) after EVERY later in-place
@@ -446,6 +452,82 @@ int cbet_cbet_solve(double *te_data_g, double *r_data_g, double *ne_data_g, doub
                     double *bbeam_norm, double *beam_norm, double *pow_r, double *phase_r,
                     const cbet_params *p, const cbet_gain_params *g, void *workspace,
                     cbet_context *ctx, void *stream, cbet_cbet_report *report);
+/*
+ * The converged gain inside a workspace that cbet_cbet_solve has run in: device [nbeams][(nx+2)(ny+2)(nz+2)]
+ * doubles at a fixed offset of `workspace` (the four field components come first).  Valid after the solve
+ * returns, until the workspace is reused; pass it to cbet_trace_exits to see where the light of that solve went.
+ * NULL on bad arguments.
+ */
+const double *cbet_cbet_workspace_gain(const cbet_params *p, const void *workspace);
+
+/* ---- exit pass --------------------------------------------------------------- */
+/*
+ * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
+ * nothing, and writes ONE record per ray when the ray ends: in the step where the reference's stop test
+ * (launch_ray_XZ.cu:351-356) first holds, or after nt steps.
+ */
+#define CBET_RAY_LAUNCHED 1   /* slot holds a traced ray (0: idle lane of the bundle)                */
+#define CBET_RAY_CUTOFF   2   /* uray <= 0.05 uray0 at the end (launch_ray_XZ.cu:351)                 */
+#define CBET_RAY_ESCAPED  4   /* outside xmin - dx/2 ... zmax + dz/2 at the end (:352-354)            */
+#define CBET_RAY_TIMEOUT  8   /* still inside and above the cutoff after nt steps                      */
+typedef struct cbet_ray_exit {
+    double x, y, z;       /* position after the last step (cm)                                        */
+    double vx, vy, vz;    /* velocity after the last kick (cm/s)                                       */
+    double uray;          /* energy the ray still carries                                              */
+    double uray0;         /* launch energy (:113)                                                      */
+    double gained;        /* CBET: energy gained on the way (0 without a gain grid)                    */
+    int steps;            /* steps taken: the ray's share of cbet_counters.ray_steps                   */
+    int status;           /* CBET_RAY_* bits; CUTOFF and ESCAPED may both be set                       */
+} cbet_ray_exit;          /* 80 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cbet_ray_exit) == 80, "cbet_ray_exit is 80 bytes");
+#else
+_Static_assert(sizeof(cbet_ray_exit) == 80, "cbet_ray_exit is 80 bytes");
+#endif
+
+/* Columns of a cbet_exit_tally row. */
+#define CBET_TALLY_COLUMNS 8
+#define CBET_TALLY_LAUNCHED 0     /* sum of uray0                                                  */
+#define CBET_TALLY_GAINED 1       /* sum of gained                                                 */
+#define CBET_TALLY_ABSORBED 2     /* sum of (uray0 + gained - uray)                                */
+#define CBET_TALLY_ESCAPED 3      /* sum of uray over rays with CBET_RAY_ESCAPED                   */
+#define CBET_TALLY_STRANDED 4     /* ... over rays with CUTOFF and not ESCAPED                     */
+#define CBET_TALLY_UNFINISHED 5   /* ... over rays with TIMEOUT                                    */
+#define CBET_TALLY_N_RAYS 6       /* records with CBET_RAY_LAUNCHED                                */
+#define CBET_TALLY_N_ESCAPED 7    /* ... of those, ESCAPED                                         */
+
+/*
+ * The exit pass: cbet_trace_nodes's rays (same arguments, same beam range, shard_index / shard_count split and
+ * grid_beam0 / grid_beams), no deposit.  exits: device [grid beams][L] records, L = cbet_context_list_length; the
+ * record of launch-list entry li of beam b is exits[(b - grid_beam0) * L + li].  Slots of bundles this launch does not
+ * trace are not written, so shards fill one buffer between them; an idle lane's slot gets a zero record.
+ * ne3d / kappa3d NULL = the context's own tables (fill them first: cbet_tabulate_plasma).  gain: device
+ * [grid beams][(nx+2)(ny+2)(nz+2)] gain coefficient, or NULL: with it every step applies the CBET hook of
+ * cbet_trace_cbet (and g supplies max_exponent); when gain is NULL, g may be NULL too.  Absorbing mode only
+ * (p->absorption == 1, else CBET_EINVAL): in bookkeeping mode the reference's increment is not an energy loss.
+ * p->kernel_variant, per_beam_grids, edep_zpitch and window_stats do not apply.  Counts ray_steps and rays_traced
+ * into the context's counters.  Enqueued on `stream`, no synchronisation (graph-capturable).
+ */
+int cbet_trace_exits(const double *ne3d, const double *kappa3d, const double *gain, cbet_ray_exit *exits,
+                     const double *bbeam_norm, const double *beam_norm, const double *pow_r, const double *phase_r,
+                     double xconst, double yconst, double zconst, const cbet_params *p, const cbet_gain_params *g,
+                     cbet_context *ctx, void *stream);
+/*
+ * Per-beam energy balance of exit records: exits = device [nbeams][L], tally = device double[nbeams][8] (columns
+ * CBET_TALLY_*), OVERWRITTEN.  Only records with CBET_RAY_LAUNCHED count; per beam
+ *   launched + gained = absorbed + escaped + stranded + unfinished   (up to rounding).
+ * Fixed-order reduction (no atomics): bit-reproducible from run to run.  Enqueued on `stream`.
+ */
+int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, void *stream);
+/*
+ * Far field of the escaped light: the remaining uray of every record with CBET_RAY_LAUNCHED and CBET_RAY_ESCAPED among
+ * the n records is ADDED into device double hist[ntheta][nphi], binned by the exit direction v / |v|:
+ *   it = min(ntheta - 1, floor((1 - vz / |v|) / 2 * ntheta))        (equal solid angle per polar bin)
+ *   ip = min(nphi - 1, floor((atan2(vy, vx) + pi) / (2 pi) * nphi))
+ * A beam's own map: pass its contiguous slice exits + (b - grid_beam0) * L, n = L.  Enqueued on `stream`; the sum
+ * order of a bin is not fixed (fp64 atomics).
+ */
+int cbet_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, void *stream);
 
 #ifdef __cplusplus
 }
