@@ -160,6 +160,7 @@ EXPORTS = [
     "cbet_cbet_workspace_bytes", "cbet_cbet_solve", "cbet_gain_field_slab", "cbet_gain_field_packed",
     "cbet_cbet_slab_workspace_bytes", "cbet_cbet_slab_workspace_bytes_parts", "cbet_pack_segments", "cbet_unpack_segments",
     "cbet_context_list_length", "cbet_cbet_workspace_gain", "cbet_trace_exits", "cbet_exit_tally", "cbet_farfield",
+    "cbet_sph_modes_device", "cbet_sph_modes",
 ]
 
 _lib = None
@@ -240,6 +241,9 @@ def lib():
                                    C.POINTER(Params), C.POINTER(GainParams), vp, vp]
     L.cbet_exit_tally.argtypes = [vp, C.c_long, C.c_int, vp, vp]
     L.cbet_farfield.argtypes = [vp, C.c_long, C.c_int, C.c_int, vp, vp]
+    sph = [vp, C.c_int, C.c_long, C.POINTER(Params), dp, dp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.cbet_sph_modes_device.argtypes = sph
+    L.cbet_sph_modes.argtypes = sph
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -542,6 +546,47 @@ def exit_tally(exits, L, nbeams, tally, stream=None):
 def farfield(exits, n, ntheta, nphi, hist, stream=None):
     """cbet_farfield: the escaped rays' energy among n records ADDED into hist[ntheta][nphi]."""
     _check(lib().cbet_farfield(_addr(exits), n, ntheta, nphi, _addr(hist), _addr(stream)))
+
+
+# ---- mode spectra (cbet_sph_modes; DESIGN.md section 11) ------------------------------------------------------------
+def _sph_geometry(center, r_edges):
+    c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    e = np.ascontiguousarray(r_edges, dtype=np.float64).reshape(-1)
+    return c, e
+
+
+def sph_modes(edep, ngrids, grid_stride, params, center, r_edges, lmax, coeffs, shell_energy, shell_nodes, stream=None):
+    """cbet_sph_modes_device: device grids (edep None = geometry mode) and outputs, OVERWRITTEN -- coeffs
+    [ngrids][nshell][(lmax+1)^2], shell_energy [ngrids][nshell], shell_nodes int64 [nshell].  center and r_edges are
+    host values (nshell = len(r_edges) - 1).  Enqueued on `stream`."""
+    c, e = _sph_geometry(center, r_edges)
+    _check(lib().cbet_sph_modes_device(_addr(edep), ngrids, grid_stride, C.byref(params), _dptr(c), _dptr(e), e.size - 1,
+                                       lmax, _addr(coeffs), _addr(shell_energy), _addr(shell_nodes), _addr(stream)))
+
+
+def sph_modes_host(edep, params, center, r_edges, lmax):
+    """cbet_sph_modes on host arrays: edep a float64 numpy grid (nx+2, ny+2, row), a stack (G, nx+2, ny+2, row) of them,
+    or None (geometry mode); a row longer than nz + 2 is a padded row (cbet_params.edep_zpitch).
+    Returns numpy (coeffs [G][nshell][(lmax+1)^2], shell_energy [G][nshell], shell_nodes int64 [nshell])."""
+    c, e = _sph_geometry(center, r_edges)
+    p = params.copy(edep_zpitch=0)
+    if edep is None:
+        a, ngrids, stride = None, 1, 0
+    else:
+        a = np.ascontiguousarray(edep, dtype=np.float64)
+        grid = a.shape[-3:]
+        if grid[:2] != (p.nx + 2, p.ny + 2) or grid[2] < p.nz + 2:
+            raise ValueError("edep grids must be (nx+2, ny+2, >= nz+2), got %s" % (grid,))
+        if grid[2] > p.nz + 2:
+            p.edep_zpitch = grid[2]
+        ngrids, stride = (a.shape[0] if a.ndim == 4 else 1), int(np.prod(grid))
+    nshell, ncoef = e.size - 1, (lmax + 1) ** 2
+    coeffs = np.zeros((ngrids, max(nshell, 0), ncoef))
+    energy = np.zeros((ngrids, max(nshell, 0)))
+    nodes = np.zeros(max(nshell, 0), dtype=np.int64)
+    _check(lib().cbet_sph_modes(_addr(a), ngrids, stride, C.byref(p), _dptr(c), _dptr(e), nshell, lmax, _addr(coeffs),
+                                _addr(energy), _addr(nodes), None))
+    return coeffs, energy, nodes
 
 
 def ray_tracing(te_profile, r_profile, ne_profile, edep, params, beam_norm=None, gpus=None, ngpu=1):

@@ -139,5 +139,22 @@ hipError_t launch_unpack_segments(double *dst, long beam_stride, int hy, int hz,
                                   hipStream_t stream);
 hipError_t launch_edep_average(const double *edep, double *out, int nx, int ny, int nz, hipStream_t stream);
 
+// Spherical-harmonic mode spectra (cbet_sph_modes.hip).  Passed by value: the shell edges are
+// captured at the call.
+struct SphArgs {
+    const double *edep;                     // [ngrids] grids grid_stride doubles apart, or NULL (geometry mode: E = 1)
+    long grid_stride;                       // doubles between grids
+    long row_pitch;                         // doubles per (I, J) row: nz + 2 or cbet_params.edep_zpitch
+    int ngrids, nx, ny, nz;
+    int nshell, lmax;
+    double xmin, ymin, zmin, dx, dy, dz;
+    double cx, cy, cz;                      // centre
+    double *coeffs;                         // [ngrids][nshell][(lmax+1)^2], overwritten
+    double *shell_energy;                   // [ngrids][nshell], overwritten
+    long long *shell_nodes;                 // [nshell], overwritten
+    double r_edges[CBET_SPH_MAX_SHELLS + 1];
+};
+hipError_t launch_sph_modes(const SphArgs &a, hipStream_t stream);
+
 }  // namespace cbet
 #endif

@@ -245,6 +245,43 @@ class RayTracer:
             api.farfield(exits[b], L, ntheta, nphi, hist, stream)
         return hist
 
+    # ---- mode spectra (include/cbet_mi355x.h cbet_sph_modes) ----------------------------------
+    def sph_modes(self, grid, r_edges=None, lmax=16, center=(0.0, 0.0, 0.0), geometry=False):
+        """Real spherical-harmonic coefficients of a deposit grid on shells, on torch's current stream.  grid: one grid
+        (new_grid()), a padded one (new_grid(zpitch=...)) or a [G, ...] stack of grids (new_grid(per_beam=True)); ignored
+        with geometry=True, which projects E = 1 (the lattice's own spectrum).  r_edges: shell edges (default
+        modes.default_shells(params, 32)).  Returns (coeffs [S][(lmax+1)^2], shell_energy [S], shell_nodes int64 [S]),
+        with a leading [G] on the first two for a stack; modes.nonuniformity turns coeffs into sigma_l, sigma_rms."""
+        from . import modes
+        edges = np.ascontiguousarray(modes.default_shells(self.params, 32) if r_edges is None else r_edges, dtype=np.float64)
+        p = self.params.copy(edep_zpitch=0)
+        stack = False
+        if geometry:
+            edep, ngrids, stride = None, 1, 0
+        else:
+            gs = self.grid_shape
+            if grid.dtype != torch.float64 or not grid.is_contiguous() or grid.device != self.device:
+                raise ValueError("grid must be a contiguous float64 tensor on %s" % self.device)
+            if grid.dim() == 4 and tuple(grid.shape[1:]) == gs:
+                stack, ngrids, stride = True, grid.shape[0], int(np.prod(gs))
+            elif grid.dim() == 3 and tuple(grid.shape[:2]) == gs[:2] and grid.shape[2] >= gs[2]:
+                ngrids, stride = 1, 0
+                if grid.shape[2] > gs[2]:
+                    p.edep_zpitch = int(grid.shape[2])
+            else:
+                raise ValueError("grid must be %s, a padded grid or a [G, ...] stack of them, got %s" % (gs, tuple(grid.shape)))
+            edep = grid
+        nshell, ncoef = edges.size - 1, (lmax + 1) ** 2
+        f64 = dict(dtype=torch.float64, device=self.device)
+        coeffs = torch.empty((ngrids, max(nshell, 0), ncoef), **f64)
+        energy = torch.empty((ngrids, max(nshell, 0)), **f64)
+        nodes = torch.empty(max(nshell, 0), dtype=torch.int64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        api.sph_modes(edep, ngrids, stride, p, center, edges, lmax, coeffs, energy, nodes, stream)
+        if not stack:
+            coeffs, energy = coeffs[0], energy[0]
+        return coeffs, energy, nodes
+
     def node_tables(self):
         """Copies of the context's node tables (ne3d, kappa3d) as numpy arrays, for tests."""
         n = self.params.nx * self.params.ny * self.params.nz

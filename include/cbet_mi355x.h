@@ -529,6 +529,53 @@ int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tall
  */
 int cbet_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, void *stream);
 
+/* ---- mode spectra of the deposit ---------------------------------------------------------- */
+/*
+ * How uniformly the energy is deposited around a centre: the real spherical-harmonic coefficients of each grid on
+ * spherical shells.
+ *
+ * Nodes.  The input is the haloed deposit grid edep[I][J][K], I in [0, nx+1] etc., halo nodes included (they hold real
+ * deposits); rows are nz + 2 doubles, or p->edep_zpitch when that is set; ngrids grids lie grid_stride doubles apart.
+ * The coordinates of node (I, J, K) relative to the centre c are evaluated exactly in this order, with no fused
+ * operations (dx, dy, dz from cbet_derive; the node coordinates of cbet_node_coordinates with i = I - 1):
+ *     x = ((I - 1) * dx + xmin) - cx,  y and z alike,  r = sqrt(x*x + y*y + z*z)
+ * Shell s holds the nodes with r_edges[s] <= r < r_edges[s+1]; nodes in no shell are ignored.  r_edges: strictly
+ * increasing, finite, r_edges[0] >= 0.  Angles: cos(theta) = z / r, phi = atan2(y, x).  A node at r == 0 contributes to
+ * its shell's energy and to Y_00 only.
+ *
+ * Harmonics: real, orthonormal, WITHOUT the Condon-Shortley phase (scipy's sph_harm_y includes (-1)^m):
+ *     Y_l0 = N_l0 P_l^0(cos theta),  Y_l,m = sqrt(2) N_lm P_l^m(cos theta) cos(m phi),
+ *     Y_l,-m = sqrt(2) N_lm P_l^m(cos theta) sin(m phi)   (m > 0),
+ *     N_lm = sqrt((2l+1)/(4 pi) (l-m)!/(l+m)!),  P_l^m(x) = (1-x^2)^(m/2) d^m P_l / dx^m  (>= 0 near x = 1).
+ * Coefficient index c = l*l + l + m.
+ *
+ * Outputs, OVERWRITTEN:
+ *     coeffs       double [ngrids][nshell][(lmax+1)^2]  a_gsc = sum over the nodes of shell s of E_g(node) Y_c(node)
+ *     shell_energy double [ngrids][nshell]              sum of E_g over the shell's nodes
+ *     shell_nodes  int64  [nshell]                      nodes in the shell
+ * Geometry mode: edep == NULL with ngrids == 1 projects E = 1: the lattice's own spectrum, the floor a perfectly uniform
+ * deposit shows (about a cubic grid's centre, odd l and l = 2 vanish and l = 4, 6, 8, ... do not).
+ *
+ * Limits: 0 <= lmax <= CBET_SPH_LMAX, 1 <= nshell <= CBET_SPH_MAX_SHELLS, 1 <= ngrids <= CBET_SPH_MAX_GRIDS; with
+ * ngrids > 1, grid_stride >= one grid's (nx+2)(ny+2)(row length) doubles.  Anything else is CBET_EINVAL before any
+ * device work.
+ *
+ * Determinism: fixed-order sums, no floating-point atomics -- the same bits from run to run -- and the order follows the
+ * logical node index, so a padded grid gives the bits of the dense grid with the same values.
+ */
+#define CBET_SPH_LMAX 32
+#define CBET_SPH_MAX_SHELLS 256
+#define CBET_SPH_MAX_GRIDS 64
+/* Device grids and outputs; center (3 doubles) and r_edges (nshell + 1 doubles) are HOST arrays, captured at the call.
+ * Enqueued on `stream`, no synchronisation (graph-capturable). */
+int cbet_sph_modes_device(const double *edep, int ngrids, long grid_stride, const cbet_params *p, const double center[3],
+                          const double *r_edges, int nshell, int lmax, double *coeffs, double *shell_energy,
+                          long long *shell_nodes, void *stream);
+/* The same on HOST arrays, as plain loops (the reference the device result is checked against); stream is unused. */
+int cbet_sph_modes(const double *edep, int ngrids, long grid_stride, const cbet_params *p, const double center[3],
+                   const double *r_edges, int nshell, int lmax, double *coeffs, double *shell_energy,
+                   long long *shell_nodes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
