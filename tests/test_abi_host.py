@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA, ROOT
+from helpers import config_matrix as M
 
 
 @pytest.fixture(scope="module")
@@ -55,10 +56,14 @@ def test_struct_layout_matches_header(api, tmp_path):
     assert (p.xmin, p.xmax, p.courant_mult, p.absorption) == (-0.13, 0.13, 0.5, 1)
 
 
-@pytest.mark.parametrize("n", [64, 100, 256, 512])
+@pytest.mark.parametrize("n", [64, 100, 256, 512] + M.ENTRIES, ids=str)
 def test_derived_bitwise_equal_to_oracle(api, oracle, n):
-    d = api.derive(api.default_params(n))
-    o = oracle.derive(oracle.default_config(n))
+    """The default configuration at four sizes, then every entry of the configuration matrix (Courant, box, launch rule)."""
+    if isinstance(n, M.Entry):
+        d, o = api.derive(n.params(api)), oracle.derive(n.config(oracle))
+    else:
+        d = api.derive(api.default_params(n))
+        o = oracle.derive(oracle.default_config(n))
     for f in ("dx", "dy", "dz", "dt", "nt", "zones_spanned", "nrays_x", "nrays_y", "nrays", "omega",
               "ncrit", "uray_mult", "xconst", "yconst", "zconst", "threads_per_beam", "nindices",
               "grid_y", "edep_size"):
@@ -86,9 +91,18 @@ def test_beam_table_and_profiles(api, inputs):
     assert ei.value.code == api.EINVAL
 
 
-@pytest.mark.parametrize("n", [64, 100])
+@pytest.mark.parametrize("n", [64, 100] + M.ENTRIES, ids=str)
 def test_live_list_is_the_reference_ray_set(api, oracle, inputs, n):
     bn = inputs[0]
+    if isinstance(n, M.Entry):      # a matrix entry: its own box, launch rule and beam table (beam 0 of it)
+        p, cfg, bt = n.params(api), n.config(oracle), n.beam_table(bn)
+        slots = api.live_ray_list(p)
+        live = slots[slots >= 0]
+        d = api.derive(p)
+        assert len(slots) % 64 == 0 and all((slots[k:k + 64] >= 0).any() for k in range(0, len(slots), 64))
+        assert len(live) == d.nlive_rays and len(set(live.tolist())) == len(live)
+        assert sorted(live.tolist()) == M.live_ids(oracle, cfg, bt)
+        return
     p = api.default_params(n)
     slots = api.live_ray_list(p)
     live = slots[slots >= 0]
@@ -102,6 +116,19 @@ def test_live_list_is_the_reference_ray_set(api, oracle, inputs, n):
     assert sorted(live.tolist()) == want
     if n == 100:
         assert len(live) == 15102 and d.ntraced_ids == 19456
+
+
+@pytest.mark.parametrize("entry", M.ENTRIES, ids=str)
+def test_matrix_entry_reaches_its_regime(oracle, inputs, entry):
+    """Each entry of the configuration matrix is named for a regime (rays lost after a far jump, rays launched outside
+    the box, strided passes, ...): assert from the oracle's ray paths of a seeded sample that it still gets there, and
+    that its ray-step count is the one recorded when the table was written."""
+    st = M.regime_stats(oracle, entry, inputs)
+    print(st)
+    assert st["unit_beams"] and st["nlive"] > 0
+    entry.regime(st)
+    if entry.name in M.PINNED_STEPS:
+        assert M.oracle_trace(oracle, entry, inputs)[1] == M.PINNED_STEPS[entry.name]
 
 
 def test_bundles_are_compact_patches(api, oracle, inputs):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, parity_err
+from helpers import config_matrix as M
 
 pytestmark = pytest.mark.gpu
 
@@ -257,6 +258,60 @@ def test_gain_pass_matches_oracle(api, oracle, setup, torch_cuda):
     assert parity_err(e.cpu().numpy(), oe) < TOL
     assert np.abs(bg.cpu().numpy() - obg).max() < TOL * np.abs(obg).max()
     assert np.abs(obg).max() > 1e12          # energy really moves between beams
+
+
+@pytest.mark.parametrize("name", M.CBET_ENTRIES)
+def test_cbet_passes_across_the_knobs(api, oracle, inputs, torch_cuda, name):
+    """The CBET instantiations of the trace kernel (fused field pass, energy-field pass, gain deposit pass) and both gain
+    kernels on entries of the configuration matrix (tests/helpers/config_matrix.py): rays lost after a far jump, an
+    off-centre box, rays launched outside the box, beams along grid axes -- with a seeded random gain in +-60."""
+    from cbet_raytracing_3d_amd.tracer import RayTracer
+    entry = M.BY_NAME[name]
+    bn, r, ne, te = inputs
+    cfg, bt = entry.config(oracle), entry.beam_table(bn)
+    nb = cfg.nbeams
+    tr = RayTracer(entry.params(api), r, ne, te, beam_norm=bt)
+    tr.tabulate()
+    gp, og = api.default_gain_params(relax=1.0), oracle.gain_default()
+    ne3d, kap = oracle.node_tables(cfg, r, ne, te)
+    gain = np.random.default_rng(48).uniform(-60.0, 60.0, size=(nb,) + tr.grid_shape)
+    d_gain = torch_cuda.from_numpy(gain).cuda()
+    of = np.stack([oracle.trace_cbet(cfg, og, bt, ne3d, kap, gain=gain, quantity=q, per_beam=True, nthreads=NCPU)[0]
+                   for q in (1, 2, 3, 4)])
+    oe, osteps, obg = oracle.trace_cbet(cfg, og, bt, ne3d, kap, gain=gain, nthreads=NCPU)
+    assert np.isfinite(of).all() and np.isfinite(oe).all() and np.abs(obg).max() > 0
+    f, fe, e = tr.new_fields(), tr.new_fields(), tr.new_grid()
+    bg = torch_cuda.zeros(nb, dtype=torch_cuda.float64, device="cuda")
+    steps = []
+    tr.counters(reset=True)
+    tr.launch_cbet(f, gp, fields=True, gain=d_gain)
+    steps.append(tr.counters(reset=True).ray_steps)
+    tr.launch_cbet(fe[0], gp, fields="energy", gain=d_gain)
+    steps.append(tr.counters(reset=True).ray_steps)
+    tr.launch_cbet(e, gp, gain=d_gain, beam_gain=bg)
+    steps.append(tr.counters(reset=True).ray_steps)
+    f, fe, e, bg = f.cpu().numpy(), fe.cpu().numpy(), e.cpu().numpy(), bg.cpu().numpy()
+    err_f = max(parity_err(f[q, b], of[q, b]) for q in range(4) for b in range(nb))
+    err_fe = max(parity_err(fe[0, b], of[0, b]) for b in range(nb))
+    err_e = parity_err(e, oe)
+    err_bg = float(np.abs(bg - obg).max() / np.abs(obg).max())
+    # both gain kernels on the oracle's fields
+    ok_, _ = oracle.gain_field(cfg, og, of, ne3d, relax=1.0, nthreads=NCPU)
+    scale = np.abs(ok_).max()
+    K = {}
+    for pair_once in (False, True):
+        g2 = tr.new_grid(per_beam=True)
+        tr.gain_field(torch_cuda.from_numpy(of.copy()).cuda(), g2, gp, None, pair_once=pair_once)
+        K[pair_once] = g2.cpu().numpy()
+    err_k = [float(np.abs(K[po] - ok_).max() / scale) for po in (False, True)]
+    print("%-16s cbet: steps %s (oracle %d)  fields %.2e  energy field %.2e  edep %.2e  beam gain %.2e  K %.2e  K(pair once) %.2e"
+          % (name, steps, osteps, err_f, err_fe, err_e, err_bg, err_k[0], err_k[1]))
+    assert steps == [osteps] * 3
+    assert not fe[1:].any()
+    assert max(err_f, err_fe, err_e, err_bg) < TOL
+    assert scale > 0 and max(err_k) < TOL
+    assert np.array_equal(K[False], ok_)         # the ordered kernel: the oracle's sum order, bit for bit
+    tr.close()
 
 
 def test_solve_converges_conserves_and_matches_oracle(api, oracle, setup, torch_cuda):

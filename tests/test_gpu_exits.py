@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import NCPU
+from helpers import config_matrix as M
 
 pytestmark = pytest.mark.gpu
 
@@ -52,10 +53,14 @@ def t100(api, inputs, torch_cuda):
     tr.close()
 
 
-def _check_against_oracle(api, oracle, inputs, tr, rec, pairs):
-    """pairs: (beam, slot) -> every record field against the oracle's ray path; returns the worst relative error."""
+def _check_against_oracle(api, oracle, inputs, tr, rec, pairs, cfg=None, beam_table=None):
+    """pairs: (beam, slot) -> every record field against the oracle's ray path; returns the worst relative error.
+    cfg, beam_table: the oracle's configuration and beam rows when they are not the default box and the OMEGA table."""
     bn, r, ne, te = inputs
-    cfg = oracle.default_config(tr.params.nx)
+    if beam_table is not None:
+        bn = beam_table
+    if cfg is None:
+        cfg = oracle.default_config(tr.params.nx)
     d = tr.derived
     p = tr.params
     ids = tr.ray_ids()
@@ -100,6 +105,43 @@ def test_per_ray_against_oracle_64(api, oracle, inputs, t64):
     assert not np.ascontiguousarray(rec[:, ids < 0]).view(np.uint8).any()
     assert np.all(rec[:, ids >= 0]["status"] & api.RAY_LAUNCHED)
     print("64^3, %d rays of beams %s: worst relative difference to the oracle %.2e" % (len(pairs), beams, worst))
+
+
+@pytest.mark.parametrize("name", M.EXIT_ENTRIES)
+def test_per_ray_against_oracle_across_the_knobs(api, oracle, inputs, torch_cuda, name):
+    """Entries of the configuration matrix (tests/helpers/config_matrix.py) whose rays are lost after a far jump, start
+    outside the box, run along grid lines or come from a strided launch rule: EVERY live ray of every beam against the
+    oracle's ray path, the per-beam step counts, and the energy balance against the beam-resolved deposit."""
+    from cbet_raytracing_3d_amd.tracer import RayTracer
+    entry = M.BY_NAME[name]
+    bn, r, ne, te = inputs
+    cfg, bt = entry.config(oracle), entry.beam_table(bn)
+    tr = RayTracer(entry.params(api), r, ne, te, beam_norm=bt)
+    ex = tr.trace_exits(tr.new_exits())
+    rec = _records(api, ex)
+    ids = tr.ray_ids()
+    pairs = [(b, li) for b in range(cfg.nbeams) for li in np.nonzero(ids >= 0)[0]]
+    worst = _check_against_oracle(api, oracle, inputs, tr, rec, pairs, cfg=cfg, beam_table=bt)
+    assert not np.ascontiguousarray(rec[:, ids < 0]).view(np.uint8).any()
+    _, steps, per_beam = oracle.trace(cfg, bt, r, ne, te, nthreads=NCPU, want_per_beam=True)
+    got = rec["steps"].astype(np.int64).sum(axis=1)
+    assert np.array_equal(got, per_beam[:cfg.nbeams]) and int(got.sum()) == steps
+    grids = tr.new_grid(per_beam=True)
+    tr.launch(grids)
+    dep = grids.sum(dim=(1, 2, 3)).cpu().numpy()
+    tally = tr.energy_balance(ex).cpu().numpy()
+    launched, gained, absorbed, escaped, stranded, unfinished = tally[:, :6].T
+    status = rec[:, ids >= 0]["status"]
+    print("%s: %d rays, worst relative difference to the oracle %.2e; absorbed vs deposit grids %.2e; balance %.2e; "
+          "cut off %d, escaped %d, timed out %d" %
+          (name, len(pairs), worst, float(np.abs(absorbed / dep - 1).max()),
+           float((np.abs((launched + gained) - (absorbed + escaped + stranded + unfinished)) / launched).max()),
+           int(((status & api.RAY_CUTOFF) != 0).sum()), int(((status & api.RAY_ESCAPED) != 0).sum()),
+           int(((status & api.RAY_TIMEOUT) != 0).sum())))
+    assert np.all(np.abs(absorbed - dep) <= 1e-12 * np.abs(dep))
+    assert np.all(gained == 0.0)
+    assert np.all(np.abs((launched + gained) - (absorbed + escaped + stranded + unfinished)) <= 1e-13 * launched)
+    tr.close()
 
 
 def test_per_ray_sample_against_oracle_100(api, oracle, inputs, t100):
