@@ -160,7 +160,7 @@ EXPORTS = [
     "cbet_cbet_workspace_bytes", "cbet_cbet_solve", "cbet_gain_field_slab", "cbet_gain_field_packed",
     "cbet_cbet_slab_workspace_bytes", "cbet_cbet_slab_workspace_bytes_parts", "cbet_pack_segments", "cbet_unpack_segments",
     "cbet_context_list_length", "cbet_cbet_workspace_gain", "cbet_trace_exits", "cbet_exit_tally", "cbet_farfield",
-    "cbet_sph_modes_device", "cbet_sph_modes",
+    "cbet_sph_modes_device", "cbet_sph_modes", "cbet_prepare_plasma", "cbet_context_step_records",
 ]
 
 _lib = None
@@ -205,6 +205,8 @@ def lib():
                                       C.c_double, C.c_double, C.c_double, C.POINTER(Params), vp, vp]
     L.cbet_tabulate_plasma.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp]
     L.cbet_prepare_step_records.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_double, C.c_double, C.c_double, vp]
+    L.cbet_prepare_plasma.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.c_double, C.c_double, C.c_double, vp]
+    L.cbet_context_step_records.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_ulonglong)]
     L.cbet_trace_nodes.argtypes = [C.c_int, C.c_uint, vp, vp, vp, vp, vp, vp, vp,
                                    C.c_double, C.c_double, C.c_double, C.POINTER(Params), vp, vp]
     L.cbet_ray_tracing.argtypes = [dp, dp, dp, dp, C.POINTER(Params), dp, ip, C.c_int, dp,
@@ -406,6 +408,12 @@ class Context:
         _check(lib().cbet_context_tables(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def step_records(self):
+        """(device address of the per-node step records, number of launches that have written them) -- for tests."""
+        a, n = C.c_void_p(), C.c_ulonglong()
+        _check(lib().cbet_context_step_records(self._h, C.byref(a), C.byref(n)))
+        return a.value, n.value
+
     def close(self):
         if self._h:
             lib().cbet_context_destroy(self._h)
@@ -438,6 +446,12 @@ def prepare_step_records(ctx, params, ne3d, kappa3d, xconst, yconst, zconst, str
     """Build the default kernel's per-node step records now instead of inside the next launch (see the header)."""
     _check(lib().cbet_prepare_step_records(ctx.handle, C.byref(params), _addr(ne3d), _addr(kappa3d), xconst, yconst,
                                            zconst, _addr(stream)))
+
+
+def prepare_plasma(ctx, params, te_data_g, r_data_g, ne_data_g, xconst, yconst, zconst, stream=None):
+    """tabulate_plasma + prepare_step_records of the context's own tables as one kernel (see the header)."""
+    _check(lib().cbet_prepare_plasma(ctx.handle, C.byref(params), _addr(te_data_g), _addr(r_data_g), _addr(ne_data_g),
+                                     xconst, yconst, zconst, _addr(stream)))
 
 
 def trace_nodes(b, nindices, ne3d, kappa3d, edep, bbeam_norm, beam_norm, pow_r, phase_r, xconst,

@@ -263,6 +263,7 @@ struct cbet_context {
     StepRecord *steprec = nullptr;      // per-node step records of the LDS_WINDOW kernel (cbet_device.h)
     // what the records were built from: valid while the context's own tables are unchanged (tables_version)
     unsigned long long tables_version = 0, rec_version = ~0ull;
+    unsigned long long rec_builds = 0;  // launches that wrote the records (cbet_context_step_records)
     const double *rec_ne3d = nullptr, *rec_kap3d = nullptr;
     double rec_const[3] = {0, 0, 0};
     double *xlaunch = nullptr, *ylaunch = nullptr;
@@ -572,6 +573,14 @@ int cbet_context_tables(cbet_context *ctx, double **ne3d, double **kappa3d)
     return CBET_OK;
 }
 
+int cbet_context_step_records(const cbet_context *ctx, const void **records, unsigned long long *builds)
+{
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (records) *records = ctx->steprec;
+    if (builds) *builds = ctx->rec_builds;
+    return CBET_OK;
+}
+
 // The launch must describe the grid / ray geometry the workspace was sized for.
 static int check_geometry(const cbet_context *ctx, const cbet_params *p)
 {
@@ -623,6 +632,7 @@ static int step_records(cbet_context *ctx, const cbet_params *p, const double *n
     t.xconst = xconst; t.yconst = yconst; t.zconst = zconst;
     t.ne3d = ne; t.kap3d = kap; t.rec = ctx->steprec;
     CBET_HIP(launch_step_table(t, (hipStream_t)stream));
+    ++ctx->rec_builds;
     ctx->rec_version = own ? ctx->tables_version : ~0ull;
     ctx->rec_ne3d = ne; ctx->rec_kap3d = kap;
     ctx->rec_const[0] = xconst; ctx->rec_const[1] = yconst; ctx->rec_const[2] = zconst;
@@ -638,6 +648,41 @@ int cbet_prepare_step_records(cbet_context *ctx, const cbet_params *p, const dou
     DeviceGuard guard;
     CBET_HIP(hipSetDevice(ctx->gpu));
     return step_records(ctx, p, ne3d, kappa3d, xconst, yconst, zconst, stream, true);
+}
+
+// cbet_tabulate_plasma directly followed by cbet_prepare_step_records of the context's own tables, as ONE kernel
+// (k_plasma_records): the same tables, the same records, the same cache key as the two calls leave behind.  A profile
+// too long for the fused kernel's LDS budget (the ring beside the staged profile, 64 KB) takes the two kernels.
+int cbet_prepare_plasma(cbet_context *ctx, const cbet_params *p, const double *te_data_g, const double *r_data_g,
+                        const double *ne_data_g, double xconst, double yconst, double zconst, void *stream)
+{
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (int rc = validate(p)) return rc;
+    if (int rc = check_geometry(ctx, p)) return rc;
+    if (!te_data_g || !r_data_g || !ne_data_g) return fail(CBET_EINVAL, "NULL profile pointer");
+    if (plasma_records_lds(p->nprofile) > 65536) {
+        if (int rc = cbet_tabulate_plasma(ctx, p, te_data_g, r_data_g, ne_data_g, stream)) return rc;
+        return cbet_prepare_step_records(ctx, p, nullptr, nullptr, xconst, yconst, zconst, stream);
+    }
+    DeviceGuard guard;
+    CBET_HIP(hipSetDevice(ctx->gpu));
+    PlasmaRecordsArgs a{};
+    TabulateArgs &t = a.t;
+    t.nx = p->nx; t.ny = p->ny; t.nz = p->nz; t.nprofile = p->nprofile;
+    t.xmin = p->xmin; t.ymin = p->ymin; t.zmin = p->zmin;
+    t.dx = ctx->d.dx; t.dy = ctx->d.dy; t.dz = ctx->d.dz; t.dt = ctx->d.dt;
+    t.ncrit = ctx->d.ncrit;
+    t.r = r_data_g; t.ne = ne_data_g; t.te = te_data_g;
+    t.ne3d = ctx->ne3d; t.kap3d = ctx->kap3d;
+    a.xconst = xconst; a.yconst = yconst; a.zconst = zconst;
+    a.rec = ctx->steprec;
+    CBET_HIP(launch_plasma_records(a, (hipStream_t)stream));
+    ++ctx->tables_version;
+    ++ctx->rec_builds;
+    ctx->rec_version = ctx->tables_version;
+    ctx->rec_ne3d = ctx->ne3d; ctx->rec_kap3d = ctx->kap3d;
+    ctx->rec_const[0] = xconst; ctx->rec_const[1] = yconst; ctx->rec_const[2] = zconst;
+    return CBET_OK;
 }
 
 // CBET hooks of a trace launch (all zero: the reference path).
@@ -790,7 +835,10 @@ int cbet_launch_ray_XYZ(int b, unsigned nindices, double *te_data_g, double *r_d
     if (!ctx) {
         if (int rc = default_context(p, &ctx)) return rc;
     }
-    if (int rc = cbet_tabulate_plasma(ctx, p, te_data_g, r_data_g, ne_data_g, stream)) return rc;
+    // the default kernel gathers step records: tables and records in one kernel; the cross-check kernels read the tables
+    const bool records = p->kernel_variant == CBET_KERNEL_DEFAULT || p->kernel_variant == CBET_KERNEL_LDS_WINDOW;
+    if (int rc = records ? cbet_prepare_plasma(ctx, p, te_data_g, r_data_g, ne_data_g, xconst, yconst, zconst, stream)
+                         : cbet_tabulate_plasma(ctx, p, te_data_g, r_data_g, ne_data_g, stream)) return rc;
     return cbet_trace_nodes(b, nindices, nullptr, nullptr, edep, bbeam_norm, beam_norm, pow_r, phase_r,
                             xconst, yconst, zconst, p, ctx, stream);
 }

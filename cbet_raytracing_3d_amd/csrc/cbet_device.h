@@ -53,6 +53,13 @@ struct StepTableArgs {
     StepRecord *rec;                        // out, nx*ny*nz
 };
 
+// The fused table kernel (k_plasma_records): both of the above in one pass.
+struct PlasmaRecordsArgs {
+    TabulateArgs t;
+    double xconst, yconst, zconst;
+    StepRecord *rec;
+};
+
 // Everything the trace kernel needs, passed by value as the kernel argument.
 struct TraceArgs {
     // grid (def.cuh:35-53)
@@ -121,6 +128,8 @@ struct GainArgs {
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);
 hipError_t launch_step_table(const StepTableArgs &a, hipStream_t stream);
+hipError_t launch_plasma_records(const PlasmaRecordsArgs &a, hipStream_t stream);
+size_t plasma_records_lds(int nprofile);       // dynamic LDS of that launch, bytes
 hipError_t audit_violations(unsigned long long *out, bool reset, hipStream_t stream);
 // variant: CBET_KERNEL_GLOBAL_ATOMICS, _LDS_COMBINE (cbet_kernels.hip) or _LDS_WINDOW (cbet_trace_window.hip)
 hipError_t launch_trace(const TraceArgs &a, int variant, bool force_idx64, hipStream_t stream);

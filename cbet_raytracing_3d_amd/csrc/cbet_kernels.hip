@@ -12,6 +12,9 @@
 //                      times per ray-step (8 bisections + 9 sqrt + 9 div); with the tables a ray-step is
 //                      seven 8-byte gathers and ~60 flops, no sqrt/div (k_trace_simple) -- or, folded once
 //                      more into one 32-byte record per node by k_step_table, a single gather (the shipped kernel).
+//   * k_plasma_records : both of the above in one pass (the plain pass's preparation): ne is evaluated per x-plane of a
+//                      y-z tile into a three-plane LDS ring, and the records are formed from the ring instead of from
+//                      the table k_tabulate has just written to HBM.  Bitwise the two-kernel path's tables and records.
 //   * k_trace_simple : one wavefront = one 8x8-ray patch, the reference's step loop written plainly
 //                      (literal relocation loop, no software pipeline), with the deposit either as
 //       1  GLOBAL : 8 global_atomic_add_f64 per ray-step -- the reference's own scheme, the baseline; or
@@ -45,6 +48,21 @@ __device__ __forceinline__ void interp_table2(const double *y1, const double *y2
     o2 = y2[mid] + (y2[mid + 1] - y2[mid]) / dx * t;
 }
 
+// One node's table entries, launch_ray_XZ.cu:296-305: ed = ne at the node's radius, kap = ed/ncrit*nuei*dt (the absorbed
+// fraction up to the trailing "* uray").  Every statement is the reference's, in its order; both table kernels use it.
+__device__ __forceinline__ void node_plasma(const TabulateArgs &a, const double *s_r, const double *s_ne, const double *s_te,
+                                            int i, int j, int k, double &ed, double &kap)
+{
+    // launch_ray_XZ.cu:296 -- node radius, squares summed x,y,z
+    const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
+    const double rho = sqrt(xc * xc + yc * yc + zc * zc);
+    double etemp;                                                   // :297-298
+    interp_table2(s_ne, s_te, s_r, rho, a.nprofile, ed, etemp);
+    const double eta = 5.2e-5 * 10.0 / (etemp * sqrt(etemp));       // :299
+    const double nuei = (1e6 * ed * (kEc * kEc) / kMe) * eta;       // :300
+    kap = ed / a.ncrit * nuei * a.dt;                               // :305 up to "* uray"
+}
+
 // ---------------------------------------------------------------------------------------------
 // Node tables.  One thread per node, grid-stride; the 3 x nprofile profile is staged in LDS
 // (the one thing kept from the reference's layout, launch_ray_XZ.cu:136-150).
@@ -66,15 +84,10 @@ __global__ void __launch_bounds__(256) k_tabulate(const TabulateArgs a)
         const long ij = idx / a.nz;
         const int j = (int)(ij % a.ny);
         const int i = (int)(ij / a.ny);
-        // launch_ray_XZ.cu:296 -- node radius, squares summed x,y,z
-        const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
-        const double rho = sqrt(xc * xc + yc * yc + zc * zc);
-        double ed, etemp;                                               // :297-298
-        interp_table2(s_ne, s_te, s_r, rho, a.nprofile, ed, etemp);
-        const double eta = 5.2e-5 * 10.0 / (etemp * sqrt(etemp));       // :299
-        const double nuei = (1e6 * ed * (kEc * kEc) / kMe) * eta;       // :300
+        double ed, kap;
+        node_plasma(a, s_r, s_ne, s_te, i, j, k, ed, kap);
         a.ne3d[idx] = ed;
-        a.kap3d[idx] = ed / a.ncrit * nuei * a.dt;                      // :305 up to "* uray"
+        a.kap3d[idx] = kap;
     }
 }
 
@@ -102,6 +115,112 @@ __global__ void __launch_bounds__(256) k_step_table(const StepTableArgs a)
         r.kz = a.zconst * (a.ne3d[idx + ozp] - a.ne3d[idx + ozm]);   // :270
         r.kap = a.kap3d[idx];
         a.rec[idx] = r;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Node tables AND step records in one pass (the preparation of a plain pass: k_tabulate + k_step_table without the
+// trip of ne3d through HBM in between).
+//
+// A workgroup owns a tile of kPrTY x kPrTZ nodes in (y, z) and marches over kPrXC x-planes.  Per plane p it evaluates
+// node_plasma for the tile's nodes (and, for planes of its own chunk, ne alone for the one-node cross halo in y and z)
+// into slot p % 3 of a three-plane LDS ring, writes ne3d / kappa3d for its own nodes, and -- as soon as the plane on
+// the far side of a node is in the ring -- forms the node's record from LDS with k_step_table's operands:
+// c * (ne(+1) - ne(-1)), one-sided on the faces (launch_ray_XZ.cu:212-226, 268-270: 0 -> (0, 2), n-1 -> (n-3, n-1)).
+// Tiles are CLAMPED into the grid (a partial last tile overlaps its neighbour and writes the same values again), so a
+// face node's one-sided pair (n-3, n-1) always lies in its own tile; planes 0 and nx-1 are emitted together with their
+// neighbours (at p = 2 and p = nx-1), when the ring holds both planes of their pair.
+// Stores: ne3d / kappa3d 8 B per lane along z; records 16 B per lane along z -- lane pair (2m, 2m+1) writes the
+// {kx, ky} and {kz, kap} halves of node m, a wave 1 KB of whole lines.
+// Work repeated for the halo: (kPrXC + 2) / kPrXC tile planes and 2 (kPrTY + kPrTZ) halo nodes per kPrTY kPrTZ tile
+// nodes of ne alone = 1.41 ne evaluations per node (1 kappa); LDS 28,128 B + the profile (38,760 B at 443 rows:
+// four workgroups = 16 waves per CU).  DESIGN.md 4.1.
+// ---------------------------------------------------------------------------------------------
+constexpr int kPrTY = 8, kPrTZ = 64, kPrXC = 16, kPrThreads = 256;
+constexpr int kPrPZ = kPrTZ + 2;                          // ring row pitch (doubles): the tile's row and its two halo nodes
+constexpr int kPrPlane = (kPrTY + 2) * kPrPZ;             // one ring plane
+constexpr int kPrTile = kPrTY * kPrTZ;
+constexpr int kPrItems = kPrTile + 2 * kPrTZ + 2 * kPrTY; // tile nodes, then the y halo rows, then the z halo columns
+
+__global__ void __launch_bounds__(kPrThreads) k_plasma_records(const PlasmaRecordsArgs a)
+{
+    extern __shared__ double s_prof[];
+    const TabulateArgs &t = a.t;
+    double *s_r = s_prof, *s_ne = s_prof + t.nprofile, *s_te = s_prof + 2 * t.nprofile;
+    double *s_ring = s_prof + 3 * t.nprofile;             // [3][kPrTY + 2][kPrPZ] ne
+    double *s_kap = s_ring + 3 * kPrPlane;                // [3][kPrTile] kappa of the tile's own nodes
+    const int tid = threadIdx.x;
+    for (int i = tid; i < t.nprofile; i += kPrThreads) {
+        s_r[i] = t.r[i];
+        s_ne[i] = t.ne[i];
+        s_te[i] = t.te[i];
+    }
+    __syncthreads();
+    const int nx = t.nx, ny = t.ny, nz = t.nz;
+    const int k0 = max(0, min((int)blockIdx.x * kPrTZ, nz - kPrTZ));
+    const int j0 = max(0, min((int)blockIdx.y * kPrTY, ny - kPrTY));
+    const int x0 = (int)blockIdx.z * kPrXC, x1 = min(x0 + kPrXC, nx);
+    // planes the chunk's records need: its own and one beyond each end, (0, 2) / (nx-3, nx-1) at the faces
+    const int pa = x0 == 0 ? 0 : min(x0 - 1, nx - 3);
+    const int pb = x1 == nx ? nx : max(x1 + 1, 3);
+
+    // records of plane i from the ring: x pair in planes xl / xh, y and z pairs in plane i itself
+    auto emit = [&](int i, int xl, int xh) {
+        const double *lo = s_ring + (xl % 3) * kPrPlane, *hi = s_ring + (xh % 3) * kPrPlane, *mid = s_ring + (i % 3) * kPrPlane;
+        const double *kap = s_kap + (i % 3) * kPrTile;
+        for (int q = tid; q < 2 * kPrTile; q += kPrThreads) {
+            const int n = q >> 1, jr = n / kPrTZ, kr = n % kPrTZ;
+            const int j = j0 + jr, k = k0 + kr;
+            if (j >= ny || k >= nz) continue;
+            const int c = (jr + 1) * kPrPZ + kr + 1;
+            double v0, v1;
+            if ((q & 1) == 0) {
+                const int ym = (j == 0) ? 0 : ((j == ny - 1) ? -2 : -1), yp = (j == 0) ? 2 : ((j == ny - 1) ? 0 : 1);
+                v0 = a.xconst * (hi[c] - lo[c]);                                 // :268
+                v1 = a.yconst * (mid[c + yp * kPrPZ] - mid[c + ym * kPrPZ]);     // :269
+            } else {
+                const int zm = (k == 0) ? 0 : ((k == nz - 1) ? -2 : -1), zp = (k == 0) ? 2 : ((k == nz - 1) ? 0 : 1);
+                v0 = a.zconst * (mid[c + zp] - mid[c + zm]);                     // :270
+                v1 = kap[n];
+            }
+            const long idx = ((long)i * ny + j) * nz + k;
+            reinterpret_cast<double2 *>(a.rec + idx)[q & 1] = make_double2(v0, v1);
+        }
+    };
+
+    for (int p = pa; p < pb; ++p) {
+        const bool own_plane = p >= x0 && p < x1;
+        double *ring = s_ring + (p % 3) * kPrPlane;
+        for (int n = tid; n < (own_plane ? kPrItems : kPrTile); n += kPrThreads) {
+            int jj, kk;
+            if (n < kPrTile) {
+                jj = 1 + n / kPrTZ; kk = 1 + n % kPrTZ;
+            } else if (n < kPrTile + 2 * kPrTZ) {
+                const int h = n - kPrTile;
+                jj = h < kPrTZ ? 0 : kPrTY + 1; kk = 1 + h % kPrTZ;
+            } else {
+                const int h = n - kPrTile - 2 * kPrTZ;
+                kk = h < kPrTY ? 0 : kPrTZ + 1; jj = 1 + h % kPrTY;
+            }
+            const int j = j0 + jj - 1, k = k0 + kk - 1;
+            if (j < 0 || j >= ny || k < 0 || k >= nz) continue;
+            double ed, kap;
+            if (own_plane && n < kPrTile) {
+                node_plasma(t, s_r, s_ne, s_te, p, j, k, ed, kap);
+                s_kap[(p % 3) * kPrTile + n] = kap;
+                const long idx = ((long)p * ny + j) * nz + k;
+                t.ne3d[idx] = ed;
+                t.kap3d[idx] = kap;
+            } else {
+                node_plasma(t, s_r, s_ne, s_te, p, j, k, ed, kap);     // halo: ne alone (kap is dead code here)
+            }
+            ring[jj * kPrPZ + kk] = ed;
+        }
+        __syncthreads();
+        if (p == 2 && x0 == 0) emit(0, 0, 2);
+        if (p - 1 >= 1 && p - 1 >= x0 && p - 1 < x1) emit(p - 1, p - 2, p);
+        if (p == nx - 1 && x1 == nx) emit(nx - 1, nx - 3, nx - 1);
+        __syncthreads();            // the next plane overwrites the slot of plane p - 2
     }
 }
 
@@ -361,6 +480,19 @@ hipError_t launch_step_table(const StepTableArgs &a, hipStream_t stream)
     long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(k_step_table, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+size_t plasma_records_lds(int nprofile)
+{
+    return sizeof(double) * (3 * (size_t)nprofile + 3 * (size_t)kPrPlane + 3 * (size_t)kPrTile);
+}
+
+hipError_t launch_plasma_records(const PlasmaRecordsArgs &a, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((a.t.nz + kPrTZ - 1) / kPrTZ), (unsigned)((a.t.ny + kPrTY - 1) / kPrTY),
+                    (unsigned)((a.t.nx + kPrXC - 1) / kPrXC));
+    hipLaunchKernelGGL(k_plasma_records, grid, dim3(kPrThreads), plasma_records_lds(a.t.nprofile), stream, a);
     return hipGetLastError();
 }
 

@@ -345,7 +345,7 @@ class SweepPipeline:
     Per pass k, with two alternating buffer sets b = k % 2 (deposition grid, node tables + step records = a
     second context):
         prep stream b  : [tables b free = trace k-2 done, grid b free = combine k-2 done]  zero grid b,
-                         tabulate the node tables, build the step records
+                         node tables and step records (one kernel, k_plasma_records)
         trace stream b : [prep k done]  trace this rank's share of the bundles into grid b, then enqueue the combine
         RCCL stream    : reduce-scatter of grid b over xGMI (torch's process-group stream, async)
     Nothing orders trace k+1 behind trace k (each buffer set has its own streams), so pass k+1's preparation AND the
@@ -358,10 +358,12 @@ class SweepPipeline:
     def __init__(self, tracer, rank=0, world_size=1, group=None, overlap_traces=None, force_collectives=False, pad_rows=None):
         self.tr, self.rank, self.world, self.group = tracer, rank, world_size, group
         self.force = force_collectives      # run the RCCL combine on one rank too (smoke test of the collective path)
-        # a rank's share of a sharded pass is a short launch whose drain is a quarter of it: overlap consecutive
-        # traces there; a whole pass on one device gains 2 % and the kernel's own duration would no longer be
-        # what the events around it measure, so it keeps one trace stream
-        self.overlap_traces = (world_size > 1) if overlap_traces is None else bool(overlap_traces)
+        # consecutive traces overlap, at one rank too: a launch's last half millisecond runs at low occupancy, and with one
+        # trace stream the next pass's preparation hides there while the next trace waits behind the drain.  With two, the
+        # next trace fills the drain and the pass costs the trace's steady work plus the preparation's: 12.62 ms against
+        # 12.78-12.89 with one stream at 256^3, same library.  The events around a launch then measure a
+        # stretched duration (kernel_ms_in_pipeline); time_trace_alone() is the launch by itself.
+        self.overlap_traces = True if overlap_traces is None else bool(overlap_traces)
         p = tracer.params
         self.ctx = [tracer.ctx, api.Context(p, tracer.gpu)]
         planes = -(-(p.nx + 2) // world_size) * world_size          # padded to a multiple of the world size
@@ -407,8 +409,8 @@ class SweepPipeline:
                 self.work[b].wait()            # this stream waits for combine k-2 before the grid is cleared
                 self.work[b] = None
             self.grids[b].zero_()
-            api.tabulate_plasma(self.ctx[b], self.launch_p, tr.d_te, tr.d_r, tr.d_ne, sp)
-            api.prepare_step_records(self.ctx[b], self.launch_p, None, None, d.xconst, d.yconst, d.zconst, sp)
+            # node tables and step records in one kernel (k_plasma_records)
+            api.prepare_plasma(self.ctx[b], self.launch_p, tr.d_te, tr.d_r, tr.d_ne, d.xconst, d.yconst, d.zconst, sp)
             self.ev_prep[b].record()
         with torch.cuda.stream(self.s_trace[b]):
             st = self.s_trace[b].cuda_stream

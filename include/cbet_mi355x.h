@@ -217,6 +217,12 @@ int cbet_context_list_length(const cbet_context *ctx, long *length);
  * modification -- a launch cannot see a write on its own.
  */
 int cbet_context_tables(cbet_context *ctx, double **ne3d, double **kappa3d);
+/*
+ * For tests: *records = device pointer of the context's per-node step records (nx*ny*nz records of four doubles
+ * {kx, ky, kz, kappa}, read-only), *builds = how many launches have written them so far (a launch that finds them
+ * current does not).  Either may be NULL.
+ */
+int cbet_context_step_records(const cbet_context *ctx, const void **records, unsigned long long *builds);
 
 /*
  * Bounds-audit builds only (-DCBET_DEBUG_BOUNDS; tests/test_gpu_bounds_audit.py): number of
@@ -242,7 +248,8 @@ int cbet_debug_bounds_violations(unsigned long long *out, int reset, void *strea
  *   pow_r, phase_r  device, CBET_NPHASE doubles each
  *   xconst, yconst, zconst  main.cu:156-159
  * plus: the run-time parameters, the workspace and the stream.  Work is enqueued on `stream`
- * (tabulate node tables -> trace) and the call returns without synchronising; launch errors are
+ * (node tables and, for the default kernel, the per-node step records in one kernel -> trace; the
+ * cross-check kernels: node tables -> trace) and the call returns without synchronising; launch errors are
  * reported through the return value (the reference checks nothing, main.cu:171-175).
  */
 int cbet_launch_ray_XYZ(int b, unsigned nindices, double *te_data_g, double *r_data_g,
@@ -261,6 +268,11 @@ int cbet_launch_ray_XYZ(int b, unsigned nindices, double *te_data_g, double *r_d
  *       rule of :212-238, and kappa3d -- which a launch builds from the tables and xconst / yconst / zconst
  *       when they are not current.  Calling this first moves that pass (0.15 ms at 256^3) out of the launch;
  *       records built from the context's own tables stay valid until the next cbet_tabulate_plasma.
+ *   cbet_prepare_plasma  : cbet_tabulate_plasma directly followed by cbet_prepare_step_records(ctx, p, NULL, NULL, ...)
+ *       as ONE kernel: ne is evaluated plane by plane into LDS and the records are formed there, instead of reading
+ *       back the table the first kernel has just written.  Node tables and records are bit for bit those of the two
+ *       calls, and so is what the context remembers about them (the records stay valid until the tables change).
+ *       cbet_launch_ray_XYZ with the default kernel, and a pass of the pipeline, prepare their plasma this way.
  */
 int cbet_tabulate_plasma(cbet_context *ctx, const cbet_params *p, const double *te_data_g,
                          const double *r_data_g, const double *ne_data_g, void *stream);
@@ -271,6 +283,9 @@ int cbet_trace_nodes(int b, unsigned nindices, const double *ne3d, const double 
 int cbet_prepare_step_records(cbet_context *ctx, const cbet_params *p, const double *ne3d,
                               const double *kappa3d, double xconst, double yconst, double zconst,
                               void *stream);
+int cbet_prepare_plasma(cbet_context *ctx, const cbet_params *p, const double *te_data_g,
+                        const double *r_data_g, const double *ne_data_g, double xconst, double yconst,
+                        double zconst, void *stream);
 
 /* ---- orchestrator ---------------------------------------------------------------------------- */
 /*
