@@ -1,7 +1,10 @@
 """cbet_raytracing_3d_amd -- MI355X-native ray integrator behind the C ABI of include/cbet_mi355x.h.
 
 api     ctypes binding of libcbet_mi355x.so (no CPU fallback; raises if the library is missing)
-tracer  torch-held device buffers + the multi-GPU pass (torch.distributed / RCCL)
+tracer  RayTracer: torch-held device buffers around the launches; re-exports the three modules below
+pipeline   the plain path's grid combine and SweepPipeline (torch.distributed / RCCL)
+cbet_loop  the CBET fixed-point loops and their device engine
+exchange   the slab-owned loop's exchange over point-to-point links
 build   hipcc build of the library for gfx950
 """
 __all__ = ["api", "tracer", "build"]

@@ -251,6 +251,22 @@ static void build_live_list(const cbet_params *p, const cbet_derived *d, int nin
     slots.insert(slots.end(), full.begin(), full.end());
 }
 
+// Everything a launch shape implies, in one place: the derived constants, both launch axes and the launch list
+// (with cbet_derived.ntraced_ids / nlive_rays filled from it).
+static int derive_launch(const cbet_params *p, cbet_derived *d, std::vector<double> &xl, std::vector<double> &yl,
+                         std::vector<int> &live)
+{
+    derive_core(p, d);
+    if (d->threads_per_beam < 1) return fail(CBET_EINVAL, "no threads per beam");
+    xl = launch_axis(d->nrays_x, d->nrays_x, d->dx / 2);
+    yl = launch_axis(d->nrays_y, d->nrays_y, d->dy / 2);
+    long ntraced = 0, nlive = 0;
+    build_live_list(p, d, d->nindices, xl, yl, live, ntraced, nlive);
+    d->ntraced_ids = ntraced;
+    d->nlive_rays = nlive;
+    return CBET_OK;
+}
+
 }  // namespace cbet
 
 using namespace cbet;
@@ -307,16 +323,9 @@ int cbet_derive(const cbet_params *p, cbet_derived *d)
 {
     if (int rc = validate(p)) return rc;
     if (!d) return fail(CBET_EINVAL, "derived is NULL");
-    derive_core(p, d);
-    if (d->threads_per_beam < 1) return fail(CBET_EINVAL, "no threads per beam");
-    auto xl = launch_axis(d->nrays_x, d->nrays_x, d->dx / 2);
-    auto yl = launch_axis(d->nrays_y, d->nrays_y, d->dy / 2);
+    std::vector<double> xl, yl;
     std::vector<int> live;
-    long ntraced = 0, nlive = 0;
-    build_live_list(p, d, d->nindices, xl, yl, live, ntraced, nlive);
-    d->ntraced_ids = ntraced;
-    d->nlive_rays = nlive;
-    return CBET_OK;
+    return derive_launch(p, d, xl, yl, live);
 }
 
 int cbet_live_ray_list(const cbet_params *p, int *out, long cap, long *count)
@@ -324,13 +333,9 @@ int cbet_live_ray_list(const cbet_params *p, int *out, long cap, long *count)
     if (int rc = validate(p)) return rc;
     if (!count) return fail(CBET_EINVAL, "count is NULL");
     cbet_derived d;
-    derive_core(p, &d);
-    if (d.threads_per_beam < 1) return fail(CBET_EINVAL, "no threads per beam");
-    auto xl = launch_axis(d.nrays_x, d.nrays_x, d.dx / 2);
-    auto yl = launch_axis(d.nrays_y, d.nrays_y, d.dy / 2);
+    std::vector<double> xl, yl;
     std::vector<int> live;
-    long ntraced = 0, nlive = 0;
-    build_live_list(p, &d, d.nindices, xl, yl, live, ntraced, nlive);
+    if (int rc = derive_launch(p, &d, xl, yl, live)) return rc;
     *count = (long)live.size();
     if (out)
         for (long i = 0; i < std::min<long>(cap, (long)live.size()); ++i) out[i] = live[i];
@@ -479,15 +484,9 @@ int cbet_context_create(cbet_context **out, const cbet_params *p, int gpu)
     *out = nullptr;
     if (int rc = validate(p)) return rc;
     cbet_derived d;
-    derive_core(p, &d);
-    if (d.threads_per_beam < 1) return fail(CBET_EINVAL, "no threads per beam");
-    auto xl = launch_axis(d.nrays_x, d.nrays_x, d.dx / 2);
-    auto yl = launch_axis(d.nrays_y, d.nrays_y, d.dy / 2);
+    std::vector<double> xl, yl;
     std::vector<int> live;
-    long ntraced = 0, nlive = 0;
-    build_live_list(p, &d, d.nindices, xl, yl, live, ntraced, nlive);
-    d.ntraced_ids = ntraced;
-    d.nlive_rays = nlive;
+    if (int rc = derive_launch(p, &d, xl, yl, live)) return rc;
 
     DeviceGuard guard;
     hipError_t e = hipSetDevice(gpu);
@@ -594,6 +593,20 @@ static int check_geometry(const cbet_context *ctx, const cbet_params *p)
     return CBET_OK;
 }
 
+// k_tabulate's arguments: the grid of `p`, the context's derived constants and tables, the caller's profiles.
+static TabulateArgs tabulate_args(const cbet_params *p, const cbet_context *ctx, const double *te_data_g,
+                                  const double *r_data_g, const double *ne_data_g)
+{
+    TabulateArgs t{};
+    t.nx = p->nx; t.ny = p->ny; t.nz = p->nz; t.nprofile = p->nprofile;
+    t.xmin = p->xmin; t.ymin = p->ymin; t.zmin = p->zmin;
+    t.dx = ctx->d.dx; t.dy = ctx->d.dy; t.dz = ctx->d.dz; t.dt = ctx->d.dt;
+    t.ncrit = ctx->d.ncrit;
+    t.r = r_data_g; t.ne = ne_data_g; t.te = te_data_g;
+    t.ne3d = ctx->ne3d; t.kap3d = ctx->kap3d;
+    return t;
+}
+
 int cbet_tabulate_plasma(cbet_context *ctx, const cbet_params *p, const double *te_data_g,
                          const double *r_data_g, const double *ne_data_g, void *stream)
 {
@@ -603,14 +616,7 @@ int cbet_tabulate_plasma(cbet_context *ctx, const cbet_params *p, const double *
     if (!te_data_g || !r_data_g || !ne_data_g) return fail(CBET_EINVAL, "NULL profile pointer");
     DeviceGuard guard;
     CBET_HIP(hipSetDevice(ctx->gpu));
-    TabulateArgs t{};
-    t.nx = p->nx; t.ny = p->ny; t.nz = p->nz; t.nprofile = p->nprofile;
-    t.xmin = p->xmin; t.ymin = p->ymin; t.zmin = p->zmin;
-    t.dx = ctx->d.dx; t.dy = ctx->d.dy; t.dz = ctx->d.dz; t.dt = ctx->d.dt;
-    t.ncrit = ctx->d.ncrit;
-    t.r = r_data_g; t.ne = ne_data_g; t.te = te_data_g;
-    t.ne3d = ctx->ne3d; t.kap3d = ctx->kap3d;
-    CBET_HIP(launch_tabulate(t, (hipStream_t)stream));
+    CBET_HIP(launch_tabulate(tabulate_args(p, ctx, te_data_g, r_data_g, ne_data_g), (hipStream_t)stream));
     ++ctx->tables_version;   // step records built from the old tables are stale
     return CBET_OK;
 }
@@ -667,13 +673,7 @@ int cbet_prepare_plasma(cbet_context *ctx, const cbet_params *p, const double *t
     DeviceGuard guard;
     CBET_HIP(hipSetDevice(ctx->gpu));
     PlasmaRecordsArgs a{};
-    TabulateArgs &t = a.t;
-    t.nx = p->nx; t.ny = p->ny; t.nz = p->nz; t.nprofile = p->nprofile;
-    t.xmin = p->xmin; t.ymin = p->ymin; t.zmin = p->zmin;
-    t.dx = ctx->d.dx; t.dy = ctx->d.dy; t.dz = ctx->d.dz; t.dt = ctx->d.dt;
-    t.ncrit = ctx->d.ncrit;
-    t.r = r_data_g; t.ne = ne_data_g; t.te = te_data_g;
-    t.ne3d = ctx->ne3d; t.kap3d = ctx->kap3d;
+    a.t = tabulate_args(p, ctx, te_data_g, r_data_g, ne_data_g);
     a.xconst = xconst; a.yconst = yconst; a.zconst = zconst;
     a.rec = ctx->steprec;
     CBET_HIP(launch_plasma_records(a, (hipStream_t)stream));

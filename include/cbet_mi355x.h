@@ -95,11 +95,11 @@ typedef struct cbet_params {
                                  /* (launch_ray_XZ.cu:5-7).  p >= nz+2: the caller's grid has rows of p doubles  */
                                  /* -- node (i,j,k) at (i*(ny+2) + j)*p + k; the entries k >= nz+2 of a row are   */
                                  /* padding the launch never touches.  For callers that own their deposit grid's */
-                                 /* layout (tracer.SweepPipeline pads its private grids' rows to whole 64-byte    */
-                                 /* lines): how the rows of the grid fall on the memory channels relative to the */
-                                 /* record table's decides 10 % of the pass time with dense rows of 258 doubles  */
-                                 /* (16.9 ... 18.6 ms from one process to the next) and 2 % with rows of 264      */
-                                 /* (DESIGN.md section 4.4).  Plain path only.                                    */
+                                 /* layout (pipeline.SweepPipeline pads its private grids' rows to whole 64-byte  */
+                                 /* lines).  With an earlier kernel the pass time depended on where a dense grid  */
+                                 /* landed relative to the record table (16.9 ... 18.6 ms); with the current one  */
+                                 /* five fresh dense allocations give 12.53 ... 12.72 ms: the effect is gone, the */
+                                 /* padding is harmless.  Plain path only.                */
     int window_stats;            /* 0 (default): a launch of the default kernel counts ray_steps and rays_traced  */
                                  /* only.  1: the instantiation that also counts the deposit windows' diagnostics  */
                                  /* (global_atomics, lds_evictions, wave_steps, wave_steps_miss, wave_steps_wide,  */
