@@ -147,6 +147,35 @@ def farfield_numpy(records, ntheta, nphi):
     return hist
 
 
+# ---- perturbed targets (cbet_tabulate_target) ----------------------------------------------------
+TARGET_LMAX = 16
+
+
+class Target(C.Structure):
+    """cbet_target: a target whose centre sits at `offset` (cm) and whose iso-surfaces are displaced by
+    delta(theta, phi) = sum_c coeffs[c] Y_c (relative, dR/R; modes.target_coeffs builds the vector, index l*l + l + m).
+    lmax defaults to what the coefficient vector's length says (0 without one).  The library checks the values."""
+    _fields_ = [("offset", C.c_double * 3), ("lmax", C.c_int), ("coeffs", C.POINTER(C.c_double))]
+
+    def __init__(self, offset=(0.0, 0.0, 0.0), coeffs=None, lmax=None):
+        super().__init__()
+        self.offset = (C.c_double * 3)(*[float(v) for v in offset])
+        self._keep = None
+        if coeffs is not None:
+            self._keep = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1).copy()
+            n = int(round(self._keep.size ** 0.5)) - 1
+            if (n + 1) ** 2 != self._keep.size or (lmax is not None and lmax != n):
+                raise ValueError("coeffs must hold (lmax + 1)^2 values, got %d%s" % (
+                    self._keep.size, "" if lmax is None else " with lmax = %d" % lmax))
+            lmax = n
+            self.coeffs = _dptr(self._keep)
+        self.lmax = 0 if lmax is None else int(lmax)
+
+    def coeff_array(self):
+        """A copy of the coefficient vector ((lmax + 1)^2 zeros without one)."""
+        return np.zeros((self.lmax + 1) ** 2) if self._keep is None else self._keep.copy()
+
+
 # Every symbol include/cbet_mi355x.h declares; tests check the library exports all of them.
 EXPORTS = [
     "cbet_last_error", "cbet_version", "cbet_params_default", "cbet_derive",
@@ -161,6 +190,7 @@ EXPORTS = [
     "cbet_cbet_slab_workspace_bytes", "cbet_cbet_slab_workspace_bytes_parts", "cbet_pack_segments", "cbet_unpack_segments",
     "cbet_context_list_length", "cbet_cbet_workspace_gain", "cbet_trace_exits", "cbet_exit_tally", "cbet_farfield",
     "cbet_sph_modes_device", "cbet_sph_modes", "cbet_prepare_plasma", "cbet_context_step_records",
+    "cbet_tabulate_target", "cbet_target_tables",
 ]
 
 _lib = None
@@ -246,6 +276,8 @@ def lib():
     sph = [vp, C.c_int, C.c_long, C.POINTER(Params), dp, dp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.cbet_sph_modes_device.argtypes = sph
     L.cbet_sph_modes.argtypes = sph
+    L.cbet_tabulate_target.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.POINTER(Target), vp]
+    L.cbet_target_tables.argtypes = [C.POINTER(Params), dp, dp, dp, C.POINTER(Target), dp, dp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -452,6 +484,23 @@ def prepare_plasma(ctx, params, te_data_g, r_data_g, ne_data_g, xconst, yconst, 
     """tabulate_plasma + prepare_step_records of the context's own tables as one kernel (see the header)."""
     _check(lib().cbet_prepare_plasma(ctx.handle, C.byref(params), _addr(te_data_g), _addr(r_data_g), _addr(ne_data_g),
                                      xconst, yconst, zconst, _addr(stream)))
+
+
+def tabulate_target(ctx, params, te_data_g, r_data_g, ne_data_g, target, stream=None):
+    """cbet_tabulate_target: tabulate_plasma on a displaced / distorted target (api.Target), captured at the call."""
+    _check(lib().cbet_tabulate_target(ctx.handle, C.byref(params), _addr(te_data_g), _addr(r_data_g), _addr(ne_data_g),
+                                      C.byref(target), _addr(stream)))
+
+
+def target_tables(params, r_profile, ne_profile, te_profile, target):
+    """cbet_target_tables, the host twin: numpy (ne3d, kappa3d), each (nx, ny, nz), from host profiles."""
+    r, ne, te = (np.ascontiguousarray(a, dtype=np.float64) for a in (r_profile, ne_profile, te_profile))
+    if not (r.size == ne.size == te.size == params.nprofile):
+        raise ValueError("profile length != params.nprofile")
+    shape = (params.nx, params.ny, params.nz)
+    ne3d, kap = np.empty(shape), np.empty(shape)
+    _check(lib().cbet_target_tables(C.byref(params), _dptr(te), _dptr(r), _dptr(ne), C.byref(target), _dptr(ne3d), _dptr(kap)))
+    return ne3d, kap
 
 
 def trace_nodes(b, nindices, ne3d, kappa3d, edep, bbeam_norm, beam_norm, pow_r, phase_r, xconst,

@@ -521,6 +521,8 @@ int cbet_context_create(cbet_context **out, const cbet_params *p, int gpu)
         (e = hipMemcpy(ctx->live, live.data(), live.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
         return bail(e, "hipMemcpy(live)");
     if ((e = hipMemset(ctx->counters, 0, kCntSlots * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(counters)");
+    // the recurrence factors of cbet_tabulate_target into this device's constant memory (the same bytes every time)
+    if ((e = target_upload_factors()) != hipSuccess) return bail(e, "hipMemcpyToSymbol(target factors)");
     *out = ctx;
     return CBET_OK;
 }
@@ -617,6 +619,26 @@ int cbet_tabulate_plasma(cbet_context *ctx, const cbet_params *p, const double *
     DeviceGuard guard;
     CBET_HIP(hipSetDevice(ctx->gpu));
     CBET_HIP(launch_tabulate(tabulate_args(p, ctx, te_data_g, r_data_g, ne_data_g), (hipStream_t)stream));
+    ++ctx->tables_version;   // step records built from the old tables are stale
+    return CBET_OK;
+}
+
+// cbet_tabulate_plasma on a displaced, Y_lm-distorted target (k_tabulate_target): the same duties towards the context.
+int cbet_tabulate_target(cbet_context *ctx, const cbet_params *p, const double *te_data_g, const double *r_data_g,
+                         const double *ne_data_g, const cbet_target *target, void *stream)
+{
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (int rc = validate(p)) return rc;
+    if (int rc = check_geometry(ctx, p)) return rc;
+    if (!te_data_g || !r_data_g || !ne_data_g) return fail(CBET_EINVAL, "NULL profile pointer");
+    int inst;
+    if (int rc = target_check(target, &inst)) return rc;
+    DeviceGuard guard;
+    CBET_HIP(hipSetDevice(ctx->gpu));
+    TargetArgs a{};
+    a.t = tabulate_args(p, ctx, te_data_g, r_data_g, ne_data_g);
+    target_fill(target, &a);
+    CBET_HIP(launch_tabulate_target(a, inst, (hipStream_t)stream));
     ++ctx->tables_version;   // step records built from the old tables are stale
     return CBET_OK;
 }

@@ -165,5 +165,26 @@ struct SphArgs {
 };
 hipError_t launch_sph_modes(const SphArgs &a, hipStream_t stream);
 
+// Perturbed targets (cbet_target.hip, cbet_target_host.cpp, cbet_target_model.h).
+// The factor table F of the header's contract, computed once on the host (target_factors) and read by the kernel (from
+// constant memory, target_upload_factors) and by the host twin alike:
+//   [kTfY00] 1/sqrt(4 pi), [kTfSqrt2] sqrt(2), [kTfD + k] d_k, [kTfA + l * kTargetS + m] a_lm, [kTfB + ...] b_lm
+constexpr int kTargetS = CBET_TARGET_LMAX + 1;
+constexpr int kTargetCoeffs = kTargetS * kTargetS;
+constexpr int kTfY00 = 0, kTfSqrt2 = 1, kTfD = 2, kTfA = kTfD + kTargetS, kTfB = kTfA + kTargetCoeffs,
+              kTargetFactors = kTfB + kTargetCoeffs;
+const double *target_factors();                      // host table, filled on first use
+hipError_t target_upload_factors();                  // host table -> the current device's constant memory (synchronous)
+// Passed by value: offset and coefficients are captured at the call (zero beyond the call's lmax).
+struct TargetArgs {
+    TabulateArgs t;
+    double ox, oy, oz;
+    double c[kTargetCoeffs];
+};
+// Argument checks of both entry points; *inst = the instantiation (0, 2, 8 or 16) that covers the non-zero coefficients.
+int target_check(const cbet_target *target, int *inst);
+void target_fill(const cbet_target *target, TargetArgs *a);   // offset and coefficients into *a
+hipError_t launch_tabulate_target(const TargetArgs &a, int inst, hipStream_t stream);
+
 }  // namespace cbet
 #endif

@@ -1,0 +1,106 @@
+// cbet_target_host.cpp -- perturbed targets (include/cbet_mi355x.h): the recurrence factors, the
+// argument checks of both entry points and the host twin of k_tabulate_target, plain loops over the nodes running the
+// kernel's own statements (cbet_target_model.h).
+#include <hip/hip_runtime_api.h>
+
+#include <array>
+#include <cmath>
+#include <cstring>
+
+#include "cbet_device.h"
+#include "cbet_mi355x.h"
+#include "cbet_target_model.h"
+
+namespace cbet {
+int fail(int code, const char *fmt, ...);
+
+const double *target_factors()
+{
+    static const std::array<double, kTargetFactors> table = [] {
+        std::array<double, kTargetFactors> f{};
+        f[kTfY00] = 1.0 / std::sqrt(4.0 * M_PI);
+        f[kTfSqrt2] = std::sqrt(2.0);
+        for (int k = 1; k <= CBET_TARGET_LMAX; ++k) f[kTfD + k] = std::sqrt((double)(2 * k + 1) / (double)(2 * k));
+        for (int l = 1; l <= CBET_TARGET_LMAX; ++l)
+            for (int m = 0; m < l; ++m) {
+                f[kTfA + l * kTargetS + m] = std::sqrt((double)(4 * l * l - 1) / (double)(l * l - m * m));
+                f[kTfB + l * kTargetS + m] = std::sqrt((double)((l - 1) * (l - 1) - m * m) / (double)(4 * (l - 1) * (l - 1) - 1));
+            }
+        return f;
+    }();
+    return table.data();
+}
+
+int target_check(const cbet_target *tg, int *inst)
+{
+    if (!tg) return fail(CBET_EINVAL, "target is NULL");
+    if (tg->lmax < 0 || tg->lmax > CBET_TARGET_LMAX)
+        return fail(CBET_EINVAL, "target: lmax = %d outside [0, %d]", tg->lmax, CBET_TARGET_LMAX);
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(tg->offset[i])) return fail(CBET_EINVAL, "target: offset is not finite");
+    int top = 0;
+    double bound = 0.0;                   // sum |c_lm| sqrt((2l+1) / (4 pi)) >= max |delta|
+    if (tg->coeffs)
+        for (int l = 0; l <= tg->lmax; ++l)
+            for (int c = l * l; c < (l + 1) * (l + 1); ++c) {
+                if (!std::isfinite(tg->coeffs[c])) return fail(CBET_EINVAL, "target: coefficient %d is not finite", c);
+                if (tg->coeffs[c] != 0.0) top = l;
+                bound += std::fabs(tg->coeffs[c]) * std::sqrt((2 * l + 1) / (4.0 * M_PI));
+            }
+    if (!(bound < 1.0))
+        return fail(CBET_EINVAL, "target: sum |c_lm| sqrt((2l+1)/(4 pi)) = %g must stay below 1 (1 + delta > 0)", bound);
+    *inst = top == 0 ? 0 : top <= 2 ? 2 : top <= 8 ? 8 : 16;
+    return CBET_OK;
+}
+
+void target_fill(const cbet_target *tg, TargetArgs *a)
+{
+    a->ox = tg->offset[0]; a->oy = tg->offset[1]; a->oz = tg->offset[2];
+    std::memset(a->c, 0, sizeof a->c);
+    if (tg->coeffs) std::memcpy(a->c, tg->coeffs, sizeof(double) * (tg->lmax + 1) * (tg->lmax + 1));
+}
+
+namespace {
+
+template <int L>
+void host_tables(const TargetArgs &a, const double *r, const double *ne, const double *te)
+{
+    const TabulateArgs &t = a.t;
+    const double *F = target_factors();
+    for (int i = 0; i < t.nx; ++i)
+        for (int j = 0; j < t.ny; ++j)
+            for (int k = 0; k < t.nz; ++k) {
+                const long idx = ((long)i * t.ny + j) * t.nz + k;
+                target_node<L>(a, F, a.c, r, ne, te, i, j, k, t.ne3d[idx], t.kap3d[idx], TargetNoPin());
+            }
+}
+
+}  // namespace
+}  // namespace cbet
+
+extern "C" int cbet_target_tables(const cbet_params *p, const double *te, const double *r, const double *ne,
+                                  const cbet_target *target, double *ne3d, double *kappa3d)
+{
+    using namespace cbet;
+    cbet_derived d;
+    if (int rc = cbet_derive(p, &d)) return rc;
+    if (!te || !r || !ne) return fail(CBET_EINVAL, "NULL profile pointer");
+    if (!ne3d || !kappa3d) return fail(CBET_EINVAL, "target_tables: NULL output");
+    int inst;
+    if (int rc = target_check(target, &inst)) return rc;
+    TargetArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.t.nx = p->nx; a.t.ny = p->ny; a.t.nz = p->nz; a.t.nprofile = p->nprofile;
+    a.t.xmin = p->xmin; a.t.ymin = p->ymin; a.t.zmin = p->zmin;
+    a.t.dx = d.dx; a.t.dy = d.dy; a.t.dz = d.dz; a.t.dt = d.dt;
+    a.t.ncrit = d.ncrit;
+    a.t.ne3d = ne3d; a.t.kap3d = kappa3d;
+    target_fill(target, &a);
+    switch (inst) {
+    case 0: host_tables<0>(a, r, ne, te); break;
+    case 2: host_tables<2>(a, r, ne, te); break;
+    case 8: host_tables<8>(a, r, ne, te); break;
+    default: host_tables<16>(a, r, ne, te); break;
+    }
+    return CBET_OK;
+}

@@ -63,6 +63,43 @@ def balance(per_beam_coeffs, weights):
     return (w.reshape((-1,) + (1,) * (per_beam_coeffs.ndim - 1)) * per_beam_coeffs).sum(0)
 
 
+def target_coeffs(lmax, amplitudes):
+    """The coefficient vector ((lmax + 1)^2 float64) of a distorted target (api.Target, RayTracer.set_target): amplitudes
+    maps (l, m) to c_lm, the relative radial displacement dR/R carried by the real orthonormal harmonic Y_lm of this
+    module's convention -- target_coeffs(2, {(2, 0): 0.01}).  A uniform relative expansion a is {(0, 0): a * sqrt(4 pi)}."""
+    c = np.zeros((lmax + 1) ** 2)
+    for (l, m), v in amplitudes.items():
+        if l > lmax:
+            raise ValueError("l = %d exceeds lmax = %d" % (l, lmax))
+        c[sph_index(l, m)] = float(v)
+    return c
+
+
+def offset_response(tracer, deltas, axis=2, lmax=8, r_edges=None, coeffs=None):
+    """How the deposit's mode spectrum answers a displaced target: for every delta (cm) the target is set delta along
+    `axis` (0, 1, 2 = x, y, z; `coeffs` adds a fixed distortion), one plain pass is traced, and its grid is projected about
+    the ORIGIN -- where the beams point -- on the shells r_edges (default modes.default_shells).  Returns (sigma_l
+    [len(deltas), lmax + 1], sigma_rms [len(deltas)]) of the shell-summed coefficients as numpy arrays.  The tracer's own
+    target is restored afterwards."""
+    saved = tracer.target
+    grid = tracer.new_grid()
+    rows, rms = [], []
+    try:
+        for delta in deltas:
+            offset = [0.0, 0.0, 0.0]
+            offset[axis] = float(delta)
+            tracer.set_target(offset, coeffs)
+            grid.zero_()
+            tracer.launch(grid)
+            c = tracer.sph_modes(grid, r_edges, lmax)[0].sum(0).cpu().numpy()
+            sl, sr = nonuniformity(c)
+            rows.append(sl)
+            rms.append(float(sr))
+    finally:
+        tracer.target = saved
+    return np.stack(rows), np.asarray(rms)
+
+
 def _stack(parts, like):
     if hasattr(like, "new_tensor"):
         import torch

@@ -64,6 +64,7 @@ class RayTracer:
                 raise ValueError("profile length != params.nprofile")
         self.ctx = api.Context(self.params, self.gpu)
         self._launch_list = None        # set_launch_list(): the regrouped list (ray_ids())
+        self.target = None              # set_target(): api.Target, or None = the spherical target about the origin
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     # ---- the one spelling of what every launch repeats -------------------------------------------------------------
@@ -88,8 +89,26 @@ class RayTracer:
 
     def _prepare_plasma(self, params, ctx):
         """Node tables and step records of `ctx` from the radial profiles, one kernel (cbet_prepare_plasma), on torch's
-        current stream."""
+        current stream.  With a target set: cbet_tabulate_target, then the records of those tables."""
+        if self.target is not None:
+            api.tabulate_target(ctx, params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
+            api.prepare_step_records(ctx, params, None, None, *self._grad_consts(), self._stream())
+            return
         api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
+
+    # ---- perturbed targets (include/cbet_mi355x.h cbet_tabulate_target; DESIGN.md section 12) ------------------------
+    def set_target(self, offset=(0.0, 0.0, 0.0), coeffs=None, lmax=None):
+        """Trace a target whose centre sits at `offset` (cm) and whose iso-surfaces are displaced by sum_c coeffs[c] Y_c
+        (modes.target_coeffs) instead of the spherical one about the origin: tabulate(), launch(), trace_exits() and the
+        pipeline's passes then fill the context's node tables with cbet_tabulate_target and trace those.  set_target(None)
+        goes back to the spherical target and to the calls made without one.  The CBET stage refuses a target (its flow
+        model is centred on the origin)."""
+        self.target = None if offset is None else api.Target(offset, coeffs, lmax)
+
+    def _no_target(self, what):
+        if self.target is not None:
+            raise ValueError("%s models the flow of a spherical target about the origin: clear the target first "
+                             "(set_target(None))" % what)
 
     def _prepare_step_records(self):
         """The step records of the context's own tables, now and on torch's current stream (cbet_prepare_step_records)."""
@@ -126,6 +145,10 @@ class RayTracer:
             p.force_wide_index = force_wide_index
         if stats is not None:
             p.window_stats = 1 if stats else 0
+        if self.target is not None:     # the halves of the launch: the target's tables, then a trace of the context's tables
+            api.tabulate_target(self.ctx, p, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
+            api.trace_nodes(0, self.derived.nindices, None, None, edep, *self._tail(use_host_trig), p, self.ctx, self._stream())
+            return edep
         api.launch_ray_XYZ(0, self.derived.nindices, self.d_te, self.d_r, self.d_ne, edep, *self._tail(use_host_trig), p,
                            ctx=self.ctx, stream=self._stream())
         return edep
@@ -135,7 +158,10 @@ class RayTracer:
 
     # ---- CBET stage (parity unpinned, see include/cbet_mi355x.h) --------------
     def tabulate(self):
-        """Fill the context's node tables from the radial profiles (what launch() does first)."""
+        """Fill the context's node tables from the radial profiles (what launch() does first); on the target, if one is set."""
+        if self.target is not None:
+            api.tabulate_target(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
+            return
         api.tabulate_plasma(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self._stream())
 
     def launch_cbet(self, out, gain_params, fields=False, gain=None, beam_gain=None, shard_index=0,
@@ -146,6 +172,7 @@ class RayTracer:
         fields="energy": the energy field alone, `out` = new_fields()[0] (a grid per beam).
         grid_beams > 0: the beam-resolved arrays (`out` when it is per beam, `gain`) hold only the grids of
         beams [grid_beam0, grid_beam0 + grid_beams) (cbet_params.grid_beam0 / grid_beams)."""
+        self._no_target("launch_cbet")
         ngrids = grid_beams if grid_beams > 0 else self.params.nbeams
         if fields == "energy":
             want = (ngrids,) + self.grid_shape
@@ -193,6 +220,7 @@ class RayTracer:
         the exchange sized for xGMI -- with this device as the engine): the deposition pass is ADDED into
         `edep` (not reduced here: use allreduce_grid).  Single-rank callers can use the native loop instead:
         api.cbet_solve."""
+        self._no_target("cbet_solve")
         engine = _DeviceCbetEngine(self, edep, gain_params, fields, gain)
         engine.force_collectives = force_collectives
         if slabs:

@@ -287,6 +287,70 @@ int cbet_prepare_plasma(cbet_context *ctx, const cbet_params *p, const double *t
                         const double *r_data_g, const double *ne_data_g, double xconst, double yconst,
                         double zconst, void *stream);
 
+/* ---- perturbed targets -------------------------------------------------- */
+/*
+ * The radial profiles evaluated on a target that sits off centre and whose iso-surfaces are distorted by real spherical
+ * harmonics: the producer of node tables for cbet_trace_nodes / cbet_trace_exits that is not spherical about the origin.
+ *
+ * Model.  Node (i, j, k) has cbet_tabulate_plasma's coordinates xc = i*dx + xmin (y, z alike; dx from cbet_derive).  With
+ * the target's offset o and coefficients c[(lmax+1)^2], every statement ONE IEEE fp64 operation per written operator, in
+ * the written order, no fused multiply-add:
+ *     sx = xc - ox,  sy = yc - oy,  sz = zc - oz
+ *     rho   = sqrt(sx*sx + sy*sy + sz*sz)                       (squares summed x, y, z)
+ *     delta = sum_c c[c] Y_c(s / rho)                           (order below)
+ *     rho'  = rho / (1.0 + delta)
+ *     ed, etemp = ne, Te interpolated at rho'                   (cbet_tabulate_plasma's bisection and interpolation)
+ *     kappa = ed / ncrit * nuei * dt                            (launch_ray_XZ.cu:299-305, cbet_tabulate_plasma's statements)
+ * c_lm is a relative radial displacement dR/R of every iso-surface in the direction (theta, phi): the surface that the
+ * unperturbed target has at radius R lies at R (1 + delta(theta, phi)) around the point o.  Te follows the same rho'.
+ *
+ * Harmonics: cbet_sph_modes's -- real, orthonormal, no Condon-Shortley phase, index c = l*l + l + m, m > 0 the cos(m phi)
+ * and m < 0 the sin(|m| phi) member.  Their evaluation here is this header's own (cbet_sph_modes fuses the recurrence's
+ * multiply-subtract; this one does not), with a table F of factors computed ONCE on the host by correctly rounded sqrt and
+ * division and used by the device kernel and the host twin alike:
+ *     y00 = 1.0 / sqrt(4.0 * pi),  q2 = sqrt(2.0),  d_k = sqrt((double)(2k+1) / (double)(2k))            (k = 1 .. 16)
+ *     a_lm = sqrt((double)(4 l l - 1) / (double)(l l - m m)),
+ *     b_lm = sqrt((double)((l-1)(l-1) - m m) / (double)(4 (l-1)(l-1) - 1))                               (0 <= m < l <= 16)
+ * Angles:  rxy = sqrt(sx*sx + sy*sy),  ct = sz / rho,  st = rxy / rho,  (c1, s1) = (sx / rxy, sy / rxy); ON THE z AXIS
+ * (rxy == 0) (c1, s1) = (1, 0), as cbet_sph_modes takes it.  Then, with L the library's instantiation (the smallest of
+ * 0, 2, 8, 16 that covers the highest l with a non-zero coefficient; coefficients beyond the call's lmax count as 0 --
+ * their terms add +-0 and change no table entry):
+ *     pmm = y00, cr = 1, si = 0
+ *     for m = 0 .. L                                              (m outermost)
+ *         if m > 0:  pmm = (pmm * d_m) * st;  cn = cr*c1 - si*s1;  si = cr*s1 + si*c1;  cr = cn
+ *         p1 = pmm, p2 = 0;  A = c[m*m+m+m] * pmm;  B = c[m*m+m-m] * pmm   (m > 0)
+ *         for l = m+1 .. L:   y = a_lm * (ct*p1 - b_lm*p2);  p2 = p1;  p1 = y;
+ *                             A = A + c[l*l+l+m] * y;  B = B + c[l*l+l-m] * y   (m > 0)
+ *         m == 0:  delta = A;      m > 0:  delta = delta + ((q2*cr) * A + (q2*si) * B)
+ * AT rho == 0 (a node exactly at the target's centre, no direction):  delta = c[0] * y00.  L == 0:  delta = c[0] * y00
+ * at every node.
+ *
+ * Limits: 0 <= lmax <= CBET_TARGET_LMAX; offset and coefficients finite; and, so that 1 + delta > 0 everywhere,
+ *     sum_c |c[c]| sqrt((2 l_c + 1) / (4 pi)) < 1
+ * (sufficient: sum_m Y_lm^2 = (2l+1)/(4 pi), so no |Y_lm| exceeds that root).  Anything else is CBET_EINVAL before any
+ * device work.
+ *
+ * Identity: with o = 0 and all c = 0 every operation above is exact (x - 0, 0 * y00, rho / 1.0): the tables are, bit for
+ * bit, cbet_tabulate_plasma's.
+ */
+#define CBET_TARGET_LMAX 16
+typedef struct cbet_target {
+    double offset[3];      /* o: the target's centre (cm)                                          */
+    int lmax;              /* 0 .. CBET_TARGET_LMAX                                                 */
+    const double *coeffs;  /* HOST array of (lmax+1)^2 doubles, or NULL = all zero                  */
+} cbet_target;
+/*
+ * Device profiles (as for cbet_tabulate_plasma) -> the context's ne3d / kappa3d.  Behaves towards the context exactly
+ * like cbet_tabulate_plasma: the same validation and geometry check, enqueued on `stream` without allocation or
+ * synchronisation (graph-capturable), and the step records are marked stale, so the next launch that uses the context's
+ * tables rebuilds them.  The target's host arrays are captured at the call.
+ */
+int cbet_tabulate_target(cbet_context *ctx, const cbet_params *p, const double *te_data_g, const double *r_data_g,
+                         const double *ne_data_g, const cbet_target *target, void *stream);
+/* The host twin, plain loops: HOST profiles of p->nprofile rows -> HOST ne3d / kappa3d of nx*ny*nz doubles each. */
+int cbet_target_tables(const cbet_params *p, const double *te, const double *r, const double *ne,
+                       const cbet_target *target, double *ne3d, double *kappa3d);
+
 /* ---- orchestrator ---------------------------------------------------------------------------- */
 /*
  * rayTracing (main.cu:96-232): host profiles in, host edep (caller-owned, (nx+2)(ny+2)(nz+2)
