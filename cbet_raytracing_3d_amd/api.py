@@ -191,6 +191,7 @@ EXPORTS = [
     "cbet_context_list_length", "cbet_cbet_workspace_gain", "cbet_trace_exits", "cbet_exit_tally", "cbet_farfield",
     "cbet_sph_modes_device", "cbet_sph_modes", "cbet_prepare_plasma", "cbet_context_step_records",
     "cbet_tabulate_target", "cbet_target_tables",
+    "cbet_tabulate_flow", "cbet_context_set_flow", "cbet_context_flow", "cbet_flow_table",
 ]
 
 _lib = None
@@ -278,6 +279,10 @@ def lib():
     L.cbet_sph_modes.argtypes = sph
     L.cbet_tabulate_target.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.POINTER(Target), vp]
     L.cbet_target_tables.argtypes = [C.POINTER(Params), dp, dp, dp, C.POINTER(Target), dp, dp]
+    L.cbet_tabulate_flow.argtypes = [vp, C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Target), vp]
+    L.cbet_context_set_flow.argtypes = [vp, vp]
+    L.cbet_context_flow.argtypes = [vp, C.POINTER(vp)]
+    L.cbet_flow_table.argtypes = [C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Target), dp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -413,6 +418,7 @@ class Context:
     def __init__(self, params, gpu=0):
         self._h = C.c_void_p()
         self.gpu = gpu
+        self._flow_ref = None           # set_flow(): the caller's table, kept alive
         _check(lib().cbet_context_create(C.byref(self._h), C.byref(params), gpu))
 
     @property
@@ -445,6 +451,19 @@ class Context:
         a, n = C.c_void_p(), C.c_ulonglong()
         _check(lib().cbet_context_step_records(self._h, C.byref(a), C.byref(n)))
         return a.value, n.value
+
+    def set_flow(self, flow):
+        """cbet_context_set_flow: the gain updates of this context read the flow from `flow`, a device table
+        [3][nx][ny][nz] of doubles (a torch tensor, kept referenced here, or an address the caller keeps alive); None =
+        back to the closed-form ramp about the origin."""
+        _check(lib().cbet_context_set_flow(self._h, _addr(flow)))
+        self._flow_ref = flow
+
+    def flow(self):
+        """Device address of the flow table in use (tabulate_flow's or set_flow's), None if none -- for tests."""
+        a = C.c_void_p()
+        _check(lib().cbet_context_flow(self._h, C.byref(a)))
+        return a.value
 
     def close(self):
         if self._h:
@@ -501,6 +520,22 @@ def target_tables(params, r_profile, ne_profile, te_profile, target):
     ne3d, kap = np.empty(shape), np.empty(shape)
     _check(lib().cbet_target_tables(C.byref(params), _dptr(te), _dptr(r), _dptr(ne), C.byref(target), _dptr(ne3d), _dptr(kap)))
     return ne3d, kap
+
+
+def tabulate_flow(ctx, params, gain_params, target=None, stream=None):
+    """cbet_tabulate_flow: the gain kernels' flow on `target` (api.Target; None = the sphere about the origin) into the
+    context's own flow table, which the context's gain updates then read.  The first call on a context allocates."""
+    _check(lib().cbet_tabulate_flow(ctx.handle, C.byref(params), C.byref(gain_params),
+                                    None if target is None else C.byref(target), _addr(stream)))
+    ctx._flow_ref = None
+
+
+def flow_table(params, gain_params, target=None):
+    """cbet_flow_table, the host twin: numpy (3, nx, ny, nz) -- ux, uy, uz at the nodes."""
+    out = np.empty((3, params.nx, params.ny, params.nz))
+    _check(lib().cbet_flow_table(C.byref(params), C.byref(gain_params), None if target is None else C.byref(target),
+                                 _dptr(out)))
+    return out
 
 
 def trace_nodes(b, nindices, ne3d, kappa3d, edep, bbeam_norm, beam_norm, pow_r, phase_r, xconst,

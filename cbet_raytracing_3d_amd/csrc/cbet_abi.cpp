@@ -287,6 +287,9 @@ struct cbet_context {
     int *live = nullptr;
     int nlive = 0;  // launch-list slots (64 per bundle, holes included)
     unsigned long long *counters = nullptr;
+    // flow table of the gain kernels (cbet_tabulate_flow / cbet_context_set_flow): NULL = the closed-form ramp
+    double *flow_own = nullptr;         // the context's own [3][nx*ny*nz] table, allocated by the first cbet_tabulate_flow
+    const double *flow = nullptr;       // the table in use: flow_own, a caller's, or NULL
 };
 
 extern "C" {
@@ -439,6 +442,7 @@ int cbet_context_destroy(cbet_context *ctx)
     (void)hipFree(ctx->bounds);
     (void)hipFree(ctx->live);
     (void)hipFree(ctx->counters);
+    (void)hipFree(ctx->flow_own);
     delete ctx;
     return CBET_OK;
 }
@@ -523,6 +527,7 @@ int cbet_context_create(cbet_context **out, const cbet_params *p, int gpu)
     if ((e = hipMemset(ctx->counters, 0, kCntSlots * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(counters)");
     // the recurrence factors of cbet_tabulate_target into this device's constant memory (the same bytes every time)
     if ((e = target_upload_factors()) != hipSuccess) return bail(e, "hipMemcpyToSymbol(target factors)");
+    if ((e = flow_upload_factors()) != hipSuccess) return bail(e, "hipMemcpyToSymbol(flow factors)");
     *out = ctx;
     return CBET_OK;
 }
@@ -1033,12 +1038,68 @@ static int gain_field_impl(double *fields, const double *ne3d, double *gain, dou
     a.consume = (consume && scratch) ? 1 : 0;
     a.frozen = g->directions_frozen ? 1 : 0;
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
+    a.flow = ctx->flow;
     a.store0 = packed ? (long)hx_lo * plane : 0;
     a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
     if (hx_hi == hx_lo) return CBET_OK;   // an empty slab (more ranks than planes)
     DeviceGuard guard;
     CBET_HIP(hipSetDevice(ctx->gpu));
     CBET_HIP(launch_gain_field(a, (hipStream_t)stream));
+    return CBET_OK;
+}
+
+// ---- flow table of the gain kernels --------------------------------------------
+int cbet_tabulate_flow(cbet_context *ctx, const cbet_params *p, const cbet_gain_params *g, const cbet_target *target,
+                       void *stream)
+{
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (int rc = validate(p)) return rc;
+    if (int rc = check_geometry(ctx, p)) return rc;
+    if (int rc = validate_gain(p, g)) return rc;
+    int inst = 0;
+    if (target)
+        if (int rc = target_check(target, &inst)) return rc;
+    double cs = 0;
+    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, nullptr)) return rc;
+    DeviceGuard guard;
+    CBET_HIP(hipSetDevice(ctx->gpu));
+    const size_t nodes = (size_t)p->nx * p->ny * p->nz;
+    if (!ctx->flow_own) {   // the first call on this context: allocates (not capturable)
+        hipError_t e = hipMalloc((void **)&ctx->flow_own, 3 * nodes * sizeof(double));
+        if (e != hipSuccess) {
+            ctx->flow_own = nullptr;
+            return fail(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(flow table): %s", hipGetErrorString(e));
+        }
+    }
+    FlowArgs a{};
+    a.nx = p->nx; a.ny = p->ny; a.nz = p->nz;
+    a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
+    a.dx = ctx->d.dx; a.dy = ctx->d.dy; a.dz = ctx->d.dz;
+    a.cs = cs;
+    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
+    a.flow = ctx->flow_own;
+    if (target) {
+        TargetArgs t{};
+        target_fill(target, &t);
+        a.ox = t.ox; a.oy = t.oy; a.oz = t.oz;
+        std::memcpy(a.c, t.c, sizeof a.c);
+    }
+    CBET_HIP(launch_tabulate_flow(a, inst, (hipStream_t)stream));
+    ctx->flow = ctx->flow_own;
+    return CBET_OK;
+}
+
+int cbet_context_set_flow(cbet_context *ctx, const double *flow)
+{
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    ctx->flow = flow;
+    return CBET_OK;
+}
+
+int cbet_context_flow(cbet_context *ctx, void **out)
+{
+    if (!ctx || !out) return fail(CBET_EINVAL, "NULL context/out");
+    *out = const_cast<double *>(ctx->flow);
     return CBET_OK;
 }
 
@@ -1063,6 +1124,9 @@ int cbet_cbet_solve(double *te_data_g, double *r_data_g, double *ne_data_g, doub
         if (int rc = default_context(p, &ctx)) return rc;
     }
     if (int rc = check_geometry(ctx, p)) return rc;
+    if (ctx->flow)   // this loop tabulates the radial plasma about the origin itself: it does not mix that with another flow
+        return fail(CBET_EINVAL, "cbet_cbet_solve models a spherical target about the origin: the context has a flow table "
+                                 "selected (cbet_context_set_flow(ctx, NULL), or the loop above the C ABI: tracer.cbet_solve)");
     const cbet_derived &d = ctx->d;
     hipStream_t s = (hipStream_t)stream;
     DeviceGuard guard;

@@ -124,6 +124,7 @@ struct GainArgs {
     int consume;                            // symmetric kernel: leave the energy entries zeroed instead of normalised (the solve loop's next pass accumulates into them)
     int frozen;                             // the direction entries already hold k (cbet_gain_params.directions_frozen)
     long store0, bstride;                   // whole-grid arrays: 0, hsize; slab-packed arrays: hx_lo * (ny+2)(nz+2), slab entries
+    const double *flow;                     // [3][nx*ny*nz] node flow table (ux, uy, uz; cbet_tabulate_flow), or NULL: the closed-form ramp about the origin
 };
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);
@@ -185,6 +186,19 @@ struct TargetArgs {
 int target_check(const cbet_target *target, int *inst);
 void target_fill(const cbet_target *target, TargetArgs *a);   // offset and coefficients into *a
 hipError_t launch_tabulate_target(const TargetArgs &a, int inst, hipStream_t stream);
+
+// Flow table of the gain kernels on a target (cbet_flow.hip, cbet_target_host.cpp, cbet_target_model.h target_flow;
+// DESIGN.md section 13).  Passed by value like TargetArgs; c sits last, as the kernel reads it from the argument segment.
+struct FlowArgs {
+    int nx, ny, nz;
+    double xmin, ymin, zmin, dx, dy, dz;
+    double cs, mach_r0, mach_0, mach_r1, mach_1;
+    double *flow;                           // out, [3][nx*ny*nz]: ux, uy, uz
+    double ox, oy, oz;
+    double c[kTargetCoeffs];
+};
+hipError_t flow_upload_factors();                    // the factor table into cbet_flow.hip's constant memory (synchronous)
+hipError_t launch_tabulate_flow(const FlowArgs &a, int inst, hipStream_t stream);
 
 }  // namespace cbet
 #endif

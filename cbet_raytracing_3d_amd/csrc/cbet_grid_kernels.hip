@@ -20,6 +20,9 @@ struct CellState {
     double frac, eps, rt, ux, uy, uz;   // ne/ncrit, 1 - ne/ncrit, sqrt(eps), flow velocity
 };
 
+// FLOW: the flow velocity is read from GainArgs.flow (a node table, cbet_flow.hip) instead of the closed-form radial
+// ramp about the origin.
+template <bool FLOW>
 __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
 {
     const int sYh = a.nz + 2;
@@ -34,6 +37,13 @@ __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
     c.frac = a.ne3d[((long)i * a.ny + j) * a.nz + k] / a.ncrit;
     c.eps = 1.0 - c.frac;
     c.rt = c.eps > 0.0 ? sqrt(c.eps) : 0.0;
+    if (FLOW) {
+        const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
+        c.ux = a.flow[node];
+        c.uy = a.flow[node + nodes];
+        c.uz = a.flow[node + 2 * nodes];
+        return c;
+    }
     const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
     const double rr = sqrt(xc * xc + yc * yc + zc * zc);
     double t = (rr - a.mach_r0) / (a.mach_r1 - a.mach_r0);
@@ -80,6 +90,7 @@ __device__ __forceinline__ void normalise_entry(const GainArgs &a, const CellSta
 //            beam is not present (E <= 0); with GainArgs.frozen only the energy entry (normalise_entry).
 //   phase 2: K_i = sum_{j != i} G_ij I_j, beams in increasing order; gain <- gain + relax (K - gain),
 //            stored only where it changes.
+template <bool FLOW>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
     const int HY = a.ny + 2, HZ = a.nz + 2;
@@ -102,7 +113,7 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
         const long h = valid ? ((long)hi * HY + hj) * HZ + hk : a.store0;
         const long hs = h - a.store0;               // index into the (possibly slab-packed) arrays
         double *fI = a.fields + hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
-        const CellState c = cell_state(a, h);
+        const CellState c = cell_state<FLOW>(a, h);
         const double kmag = a.k0 * c.rt;
         const double ds_node = (kC * c.rt) * a.dt;  // group speed x dt: energy x length -> intensity
         unsigned long long mask = 0ull;             // beams present in some cell of this brick
@@ -239,7 +250,7 @@ __device__ __forceinline__ void lds_order()
     __builtin_amdgcn_wave_barrier();
 }
 
-template <bool FROZEN>
+template <bool FROZEN, bool FLOW>
 __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 {
     static_assert(5 * LCAP * LC >= 64 * (LC + 1), "the slot arrays double as the staging area of the presence masks");
@@ -295,7 +306,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             // the plasma state of 64 cells at a time (lane = cell), handed to the four runs they make up
             if ((ibz & 3) == 0) {
                 const int hk64 = LC * ibz + lane - sft;
-                const CellState c64 = cell_state(a, ((long)hi * HY + hj) * HZ + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                const CellState c64 = cell_state<FLOW>(a, ((long)hi * HY + hj) * HZ + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
                 st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
                 st_pref = c64.eps > 0.0 ? a.gain_const * c64.frac * (1.0 / a.iaw) / c64.rt : 0.0;
             }
@@ -585,14 +596,21 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
-        if (a.frozen) hipLaunchKernelGGL(k_gain_field_sym<true>, dim3((unsigned)rows), dim3(64), 0, stream, a);
-        else hipLaunchKernelGGL(k_gain_field_sym<false>, dim3((unsigned)rows), dim3(64), 0, stream, a);
+        const dim3 grid((unsigned)rows), block(64);
+        if (a.flow) {
+            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_gain_field_sym<false, true>), grid, block, 0, stream, a);
+        } else {
+            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, false>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_gain_field_sym<false, false>), grid, block, 0, stream, a);
+        }
         return hipGetLastError();
     }
     const long bricks = (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8);  // 2 x 4 x 8 cells of the haloed grid each
     long blocks = (bricks + 3) / 4;                                                    // four wavefronts per workgroup
     if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(k_gain_field, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    if (a.flow) hipLaunchKernelGGL(k_gain_field<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_gain_field<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
-// cbet_target_host.cpp -- perturbed targets (include/cbet_mi355x.h): the recurrence factors, the
-// argument checks of both entry points and the host twin of k_tabulate_target, plain loops over the nodes running the
-// kernel's own statements (cbet_target_model.h).
+// cbet_target_host.cpp -- perturbed targets (include/cbet_mi355x.h, DESIGN.md sections 12 and 13): the recurrence factors,
+// the argument checks of the entry points and the host twins of k_tabulate_target and k_tabulate_flow, plain loops over the
+// nodes running the kernels' own statements (cbet_target_model.h).
 #include <hip/hip_runtime_api.h>
 
 #include <array>
@@ -75,6 +75,19 @@ void host_tables(const TargetArgs &a, const double *r, const double *ne, const d
             }
 }
 
+template <int L>
+void host_flow(const FlowArgs &a)
+{
+    const double *F = target_factors();
+    const long nodes = (long)a.nx * a.ny * a.nz;
+    for (int i = 0; i < a.nx; ++i)
+        for (int j = 0; j < a.ny; ++j)
+            for (int k = 0; k < a.nz; ++k) {
+                const long idx = ((long)i * a.ny + j) * a.nz + k;
+                target_flow<L>(a, F, a.c, i, j, k, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes], TargetNoPin());
+            }
+}
+
 }  // namespace
 }  // namespace cbet
 
@@ -101,6 +114,41 @@ extern "C" int cbet_target_tables(const cbet_params *p, const double *te, const 
     case 2: host_tables<2>(a, r, ne, te); break;
     case 8: host_tables<8>(a, r, ne, te); break;
     default: host_tables<16>(a, r, ne, te); break;
+    }
+    return CBET_OK;
+}
+
+// The host twin of k_tabulate_flow (cbet_flow.hip).
+extern "C" int cbet_flow_table(const cbet_params *p, const cbet_gain_params *g, const cbet_target *target, double *out)
+{
+    using namespace cbet;
+    cbet_derived d;
+    if (int rc = cbet_derive(p, &d)) return rc;
+    double cs = 0;
+    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, nullptr)) return rc;   // (validates the gain parameters)
+    if (!out) return fail(CBET_EINVAL, "flow_table: NULL output");
+    int inst = 0;
+    if (target)
+        if (int rc = target_check(target, &inst)) return rc;
+    FlowArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.nx = p->nx; a.ny = p->ny; a.nz = p->nz;
+    a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
+    a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
+    a.cs = cs;
+    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
+    a.flow = out;
+    if (target) {
+        TargetArgs t;
+        target_fill(target, &t);
+        a.ox = t.ox; a.oy = t.oy; a.oz = t.oz;
+        std::memcpy(a.c, t.c, sizeof a.c);
+    }
+    switch (inst) {
+    case 0: host_flow<0>(a); break;
+    case 2: host_flow<2>(a); break;
+    case 8: host_flow<8>(a); break;
+    default: host_flow<16>(a); break;
     }
     return CBET_OK;
 }

@@ -103,5 +103,25 @@ CBET_HD void target_node(const TargetArgs &a, FP F, CP c, const double *r, const
     kap = ed / t.ncrit * nuei * t.dt;                               // :305 up to "* uray"
 }
 
+// One node's flow velocity on the target (include/cbet_mi355x.h, "flow table"): target_node's radius statements, then
+// cell_state's ramp (cbet_grid_kernels.hip) with rho' in the ramp and s / rho as the direction.  With a zero offset and
+// zero coefficients every statement is cell_state's own, in its order.
+template <int L, class FP, class CP, class Pin>
+CBET_HD void target_flow(const FlowArgs &a, FP F, CP c, int i, int j, int k, double &ux, double &uy, double &uz, Pin pin)
+{
+    const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
+    const double sx = xc - a.ox, sy = yc - a.oy, sz = zc - a.oz;
+    const double rho = sqrt(sx * sx + sy * sy + sz * sz);
+    const double q = 1.0 + target_delta<L>(F, c, sx, sy, sz, rho, pin);
+    double rhop = rho;
+    if (q != 1.0) rhop = rho / q;
+    double t = (rhop - a.mach_r0) / (a.mach_r1 - a.mach_r0);
+    if (t < 0.0) t = 0.0;
+    if (t > 1.0) t = 1.0;
+    const double um = (a.mach_0 + (a.mach_1 - a.mach_0) * t) * a.cs;
+    ux = uy = uz = 0.0;
+    if (rho > 0.0) { ux = um * (sx / rho); uy = um * (sy / rho); uz = um * (sz / rho); }
+}
+
 }  // namespace cbet
 #endif

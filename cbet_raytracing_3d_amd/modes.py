@@ -75,13 +75,16 @@ def target_coeffs(lmax, amplitudes):
     return c
 
 
-def offset_response(tracer, deltas, axis=2, lmax=8, r_edges=None, coeffs=None):
+def offset_response(tracer, deltas, axis=2, lmax=8, r_edges=None, coeffs=None, cbet=None):
     """How the deposit's mode spectrum answers a displaced target: for every delta (cm) the target is set delta along
     `axis` (0, 1, 2 = x, y, z; `coeffs` adds a fixed distortion), one plain pass is traced, and its grid is projected about
     the ORIGIN -- where the beams point -- on the shells r_edges (default modes.default_shells).  Returns (sigma_l
-    [len(deltas), lmax + 1], sigma_rms [len(deltas)]) of the shell-summed coefficients as numpy arrays.  The tracer's own
-    target is restored afterwards."""
+    [len(deltas), lmax + 1], sigma_rms [len(deltas)]) of the shell-summed coefficients as numpy arrays.  cbet: gain
+    parameters (api.default_gain_params()) -- instead of the plain pass every offset runs the CBET iteration on the
+    displaced target with the flow centred on it (set_flow("target"), cbet_solve) and the CBET deposit is projected.
+    The tracer's own target and flow are restored afterwards."""
     saved = tracer.target
+    saved_flow = (tracer.flow, tracer._flow_gp)
     grid = tracer.new_grid()
     rows, rms = [], []
     try:
@@ -90,13 +93,19 @@ def offset_response(tracer, deltas, axis=2, lmax=8, r_edges=None, coeffs=None):
             offset[axis] = float(delta)
             tracer.set_target(offset, coeffs)
             grid.zero_()
-            tracer.launch(grid)
+            if cbet is None:
+                tracer.launch(grid)
+            else:
+                tracer.set_flow("target", cbet)
+                tracer.cbet_solve(grid, cbet)
             c = tracer.sph_modes(grid, r_edges, lmax)[0].sum(0).cpu().numpy()
             sl, sr = nonuniformity(c)
             rows.append(sl)
             rms.append(float(sr))
     finally:
         tracer.target = saved
+        if cbet is not None:
+            tracer.set_flow(saved_flow[0], saved_flow[1])
     return np.stack(rows), np.asarray(rms)
 
 

@@ -65,6 +65,8 @@ class RayTracer:
         self.ctx = api.Context(self.params, self.gpu)
         self._launch_list = None        # set_launch_list(): the regrouped list (ray_ids())
         self.target = None              # set_target(): api.Target, or None = the spherical target about the origin
+        self.flow = None                # set_flow(): None, "target" or the caller's [3, nx, ny, nz] table
+        self._flow_gp = None            # the gain parameters a "target" flow is tabulated from
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     # ---- the one spelling of what every launch repeats -------------------------------------------------------------
@@ -93,19 +95,60 @@ class RayTracer:
         if self.target is not None:
             api.tabulate_target(ctx, params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
             api.prepare_step_records(ctx, params, None, None, *self._grad_consts(), self._stream())
-            return
-        api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
+        else:
+            api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
+        self._tabulate_flow(ctx, params)
 
     # ---- perturbed targets (include/cbet_mi355x.h cbet_tabulate_target) ------------------------
     def set_target(self, offset=(0.0, 0.0, 0.0), coeffs=None, lmax=None):
         """Trace a target whose centre sits at `offset` (cm) and whose iso-surfaces are displaced by sum_c coeffs[c] Y_c
         (modes.target_coeffs) instead of the spherical one about the origin: tabulate(), launch(), trace_exits() and the
         pipeline's passes then fill the context's node tables with cbet_tabulate_target and trace those.  set_target(None)
-        goes back to the spherical target and to the calls made without one.  The CBET stage refuses a target (its flow
-        model is centred on the origin)."""
+        goes back to the spherical target and to the calls made without one.  The CBET stage -- launch_cbet, gain_field,
+        cbet_solve -- refuses a target while no flow is set: its closed-form flow is centred on the origin.  With
+        set_flow("target"), or a flow table of the caller's, it runs on the target's tables and that flow."""
         self.target = None if offset is None else api.Target(offset, coeffs, lmax)
 
+    # ---- flow of the CBET stage (include/cbet_mi355x.h cbet_tabulate_flow; DESIGN.md section 13) --------------------
+    def set_flow(self, mode=None, gain_params=None):
+        """Where the gain kernels take the plasma flow from.
+        None (the default): the closed-form radial ramp about the origin; the CBET stage then refuses a target.
+        "target": the ramp's flow on the current target (cbet_tabulate_flow; the sphere about the origin if no target is
+        set), tabulated whenever the node tables are -- tabulate(), the pipeline's preparation, cbet_solve's start -- from
+        the ramp of `gain_params` (default api.default_gain_params(); cbet_solve puts its own in their place).
+        A float64 tensor [3, nx, ny, nz] on this device: the caller's own flow field (ux, uy, uz at the nodes, cm/s), kept
+        referenced here and read as it is at every gain update.
+        With a flow set launch_cbet, gain_field and cbet_solve (slabs=True too) run on a target."""
+        if mode is None:
+            self.flow, self._flow_gp = None, None
+            self.ctx.set_flow(None)
+            return
+        if isinstance(mode, str):
+            if mode != "target":
+                raise ValueError('set_flow: None, "target" or a [3, nx, ny, nz] tensor, got %r' % (mode,))
+            self.ctx.set_flow(None)                     # until the next tabulate() fills and selects the context's table
+            self.flow = "target"
+            self._flow_gp = self._copy_gp(api.default_gain_params() if gain_params is None else gain_params)
+            return
+        _require(mode, (3, self.params.nx, self.params.ny, self.params.nz), "flow")
+        if mode.device != self.device:
+            raise ValueError("flow must be on %s" % self.device)
+        self.flow, self._flow_gp = mode, None
+        self.ctx.set_flow(mode)
+
+    @staticmethod
+    def _copy_gp(gain_params):
+        return type(gain_params).from_buffer_copy(gain_params)
+
+    def _tabulate_flow(self, ctx=None, params=None):
+        """A "target" flow into `ctx` (default: this tracer's context) on torch's current stream; nothing otherwise."""
+        if isinstance(self.flow, str):
+            api.tabulate_flow(self.ctx if ctx is None else ctx, self.params if params is None else params, self._flow_gp,
+                              self.target, self._stream())
+
     def _no_target(self, what):
+        if self.flow is not None:
+            return
         if self.target is not None:
             raise ValueError("%s models the flow of a spherical target about the origin: clear the target first "
                              "(set_target(None))" % what)
@@ -161,8 +204,9 @@ class RayTracer:
         """Fill the context's node tables from the radial profiles (what launch() does first); on the target, if one is set."""
         if self.target is not None:
             api.tabulate_target(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
-            return
-        api.tabulate_plasma(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self._stream())
+        else:
+            api.tabulate_plasma(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self._stream())
+        self._tabulate_flow()
 
     def launch_cbet(self, out, gain_params, fields=False, gain=None, beam_gain=None, shard_index=0,
                     shard_count=1, ne3d=None, kappa3d=None, beam_lo=0, beam_hi=None, grid_beam0=0, grid_beams=0):
@@ -206,7 +250,16 @@ class RayTracer:
         kernel in the CPU checker's sum order (False).  `scratch` is the C ABI's selector for the same choice (any
         tensor = pair-once; it is not touched) and is kept for callers of the earlier signature.
         x_lo, x_hi: only the planes [x_lo, x_hi) of the deposit grid (one rank's slab).
-        frozen: fields[1:4] already hold k from an earlier call; only fields[0] is read and normalised."""
+        frozen: fields[1:4] already hold k from an earlier call; only fields[0] is read and normalised.
+        With a flow set (set_flow) the update reads it; a "target" flow is the one the last tabulate() wrote, from the
+        ramp of set_flow's gain parameters -- `gain_params` must carry the same ramp."""
+        if isinstance(self.flow, str):
+            ramp = lambda g: (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)  # noqa: E731
+            if ramp(gain_params) != ramp(self._flow_gp):
+                raise ValueError("gain_field: the flow table was tabulated from another Mach ramp or sound speed than "
+                                 "gain_params carries (set_flow(\"target\", gain_params), then tabulate())")
+            if self.ctx.flow() is None:
+                raise ValueError("gain_field: set_flow(\"target\") needs tabulate() before the first gain update")
         if pair_once is None:
             pair_once = scratch is not None
         scratch = gain if pair_once else None
@@ -221,6 +274,8 @@ class RayTracer:
         `edep` (not reduced here: use allreduce_grid).  Single-rank callers can use the native loop instead:
         api.cbet_solve."""
         self._no_target("cbet_solve")
+        if isinstance(self.flow, str):
+            self._flow_gp = self._copy_gp(gain_params)      # the engine's tabulate() fills the flow table from this ramp
         engine = _DeviceCbetEngine(self, edep, gain_params, fields, gain)
         engine.force_collectives = force_collectives
         if slabs:

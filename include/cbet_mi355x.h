@@ -491,6 +491,48 @@ int cbet_gain_field_slab(double *fields, const double *ne3d, double *gain, doubl
 int cbet_gain_field_packed(double *fields, const double *ne3d, double *gain, double *scratch, double *change,
                          int hx_lo, int hx_hi, const cbet_params *p, const cbet_gain_params *g,
                          cbet_context *ctx, void *stream);
+/* ---- flow table: the gain kernels on a perturbed target ------------------- */
+/*
+ * By default both gain kernels compute the flow u of a cell in closed form about the ORIGIN (the radial ramp above, from
+ * the cell's node).  A context can instead hold a FLOW TABLE, double [3][nx][ny][nz] on the device, component-major
+ * (ux, then uy, then uz, each in ne3d's node order): every entry that updates the gain with that context --
+ * cbet_gain_field, cbet_gain_field_slab, cbet_gain_field_packed -- then reads u of a cell from the table at the cell's
+ * (clamped) node and evaluates nothing of the ramp.  The trace kernels only gather the gain and need nothing.
+ *
+ * cbet_tabulate_flow fills the table with the ramp's flow on a perturbed target (cbet_target; NULL = the sphere about the
+ * origin).  Model, for node (i, j, k), every statement ONE IEEE fp64 operation per written operator, in the written order,
+ * no fused multiply-add; the first five lines are cbet_tabulate_target's, the rest the gain kernels' own ramp:
+ *     xc = i*dx + xmin  (y, z alike)
+ *     sx = xc - ox,  sy = yc - oy,  sz = zc - oz
+ *     rho   = sqrt(sx*sx + sy*sy + sz*sz)
+ *     q     = 1.0 + delta,  delta = sum_c c[c] Y_c(s / rho)       (cbet_tabulate_target's recurrence, factors and order)
+ *     rho'  = rho if q == 1.0, else rho / q
+ *     t     = (rho' - mach_r0) / (mach_r1 - mach_r0),  clamped to [0, 1]   (t < 0 -> 0, then t > 1 -> 1)
+ *     um    = (mach_0 + (mach_1 - mach_0) * t) * cs               (cs of cbet_gain_constants)
+ *     ux = um * (sx / rho),  uy = um * (sy / rho),  uz = um * (sz / rho);   u = 0 where rho == 0
+ * The Mach number follows the distorted iso-surfaces (rho'), the DIRECTION stays radial from the target's centre o: tilting
+ * the flow to the normal of the distorted surface is out of scope.
+ * Limits and refusals: cbet_tabulate_target's (lmax, finite values, sum |c| sqrt((2l+1)/(4 pi)) < 1) and the gain
+ * parameters' (as cbet_gain_field), CBET_EINVAL before any device work.
+ * Identity: with o = 0 and all c = 0 every statement is the closed-form ramp's own in its order (x - 0 and the skipped
+ * division are exact), so a gain update with that table selected gives, bit for bit, the update with none.
+ *
+ * cbet_tabulate_flow: fills the context's OWN table and selects it.  The FIRST call on a context allocates the table
+ * (3 nx ny nz doubles) and is therefore not graph-capturable; every later call only enqueues the kernel on `stream` (no
+ * allocation, no synchronisation).  The target's host arrays and the gain parameters are captured at the call.
+ * cbet_context_set_flow: selects a CALLER's device table of the same layout (e.g. a hydro code's 3-D flow field); the
+ * caller keeps it alive and unchanged while gain updates that read it are in flight.  NULL = back to the closed-form ramp
+ * (the context's own table stays allocated).  Host-side state only: it applies to launches made after it.
+ * cbet_context_flow: *out = the table in use, NULL if none (for tests).
+ * cbet_flow_table: the host twin of cbet_tabulate_flow, plain loops in node order: HOST out of 3 nx ny nz doubles.
+ * cbet_cbet_solve tabulates the radial plasma about the origin itself and returns CBET_EINVAL for a context that has a
+ * flow table selected, rather than mixing the two models; the loop above the C ABI (tracer.cbet_solve) runs on a target.
+ */
+int cbet_tabulate_flow(cbet_context *ctx, const cbet_params *p, const cbet_gain_params *g,
+                       const cbet_target *target /* NULL = sphere about the origin */, void *stream);
+int cbet_context_set_flow(cbet_context *ctx, const double *flow);
+int cbet_context_flow(cbet_context *ctx, void **out);
+int cbet_flow_table(const cbet_params *p, const cbet_gain_params *g, const cbet_target *target, double *out);
 /*
  * The sparse exchange of the slab-owned CBET loop (tracer._Exchanger).  A segment is a 64-byte run of 8 doubles aligned
  * to 8 along z; `segments` is a DEVICE array of nseg {row of the array (beam), index of the run inside one beam's
