@@ -472,6 +472,12 @@ int cbet_trace_cbet(int b, unsigned nindices, const double *ne3d, const double *
  * dereferenced since round 3 -- pass `gain`); NULL selects the ordered kernel (twice the pair evaluations, every
  * statement one IEEE operation in the CPU checker's order; the pair-once kernel's K agrees with it to ~1e-13
  * of the largest |K|).  ne3d NULL = the context's node table.  Needs nbeams <= CBET_MAX_CBET_BEAMS.
+ * Alignment: `fields` and `gain` need the alignment of a double only (a view that starts anywhere inside a larger
+ * allocation is accepted).  The pair-once kernel cuts a z-row into runs of 16 cells by the cells' ELEMENT INDEX in the
+ * arrays ((row start - first stored element) mod 16), not by their address, so the grouping of a cell's pair sums -- and
+ * with it every bit of K -- is the same wherever the arrays start; it does follow the STORAGE (whole grid or
+ * cbet_gain_field_packed's slab, whose first element is another cell: equal to ~1e-13 of the largest |K|, not bit for
+ * bit).  The runs are whole 128-byte lines only when the arrays start on one: other starts cost time, never bits.
  */
 int cbet_gain_field(double *fields, const double *ne3d, double *gain, double *scratch, double *change,
                     const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx, void *stream);

@@ -1,0 +1,391 @@
+"""Both CBET gain kernels off the cube (cbet_grid_kernels.hip k_gain_field, k_gain_field_sym): z-rows of
+more than 64 cells -- the pair-once kernel computes the plasma state for 64 cells at a time and hands it to four 16-cell runs
+by lane shuffle -- and grids whose three sides differ, against oracle.gain_field cell by cell.
+
+  48 x 21 x 134, six beams, the oracle's traced fields: haloed 50 x 23 x 136 -- a ragged last brick in y, whole bricks in z,
+      three 64-cell state groups per row, planes of 23 * 136 doubles;
+  13 x 11 x 148, sixty beams, synthetic crowded fields: haloed 15 x 13 x 150 -- odd in x, ragged bricks in y and z, the last
+      state group holds 22 cells, the halves and quarters arms in runs beyond the first group;
+  on the first grid the FLOW arms (the sphere's table, a caller's table of an offset target), slab-wise and slab-packed
+      updates, and arrays that start 1 and 8 doubles into an allocation.
+
+The bounds are those of tests/test_gpu_cbet.py and tests/test_gpu_flow.py."""
+import numpy as np
+import pytest
+
+from conftest import NCPU
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-9                 # tests/test_gpu_cbet.py's bound, of max |K|
+LAST_BITS = 1e-12          # pair-once against ordered kernel, of max |K| (the crowded-cells test's bound)
+BEAMS = [0, 16, 29, 38, 47, 55]
+SHAPE = (48, 21, 134)
+CROWDED = (13, 11, 148)
+SHIFT = (20e-4, 0.0, -15e-4)             # tests/test_gpu_flow.py's offset target, cm
+# hk of the pair-once kernel's 64-cell state groups (up to a row's shift of 0 or 8 cells on these grids)
+Z_GROUPS = (slice(0, 64), slice(64, 128), slice(128, None))
+SLAB = (9, 22)
+CUTS = [0, 1, 12, 13, 29, SHAPE[0] + 2]
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "the gpu tests need a HIP device"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def api():
+    from cbet_raytracing_3d_amd import api as a
+    a.lib()
+    return a
+
+
+def _tracer(api, inputs, shape, beam_norm):
+    from cbet_raytracing_3d_amd.tracer import RayTracer
+    _, r, ne, te = inputs
+    p = api.default_params(shape[0], nbeams=len(beam_norm))
+    p.ny, p.nz = shape[1], shape[2]
+    tr = RayTracer(p, r, ne, te, beam_norm=beam_norm)
+    tr.tabulate()
+    return tr
+
+
+def _stream(torch):
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _update(torch, tr, raw, gp, pair_once, frozen=False, x=(0, None), change=True):
+    """One gain update from a zero gain on a copy of the device fields `raw`: (fields, gain, change)."""
+    f = raw.clone()
+    k = tr.new_grid(per_beam=True)
+    ch = torch.zeros(2, dtype=torch.float64, device="cuda") if change else None
+    tr.gain_field(f, k, gp, ch, pair_once=pair_once, frozen=frozen, x_lo=x[0], x_hi=x[1])
+    return f, k, ch
+
+
+def _first_and_frozen(torch, tr, raw, gp, pair_once):
+    """A first call, then a frozen call on fresh energy over the k entries of the first: numpy f, k, change, f2, k2."""
+    f, k, ch = _update(torch, tr, raw, gp, pair_once)
+    f2 = f.clone()
+    f2[0] = raw[0]
+    k2 = torch.zeros_like(k)
+    tr.gain_field(f2, k2, gp, None, pair_once=pair_once, frozen=True)
+    return tuple(t.cpu().numpy() for t in (f, k, ch, f2, k2))
+
+
+def _waves(tr, pair_once, x_lo, x_hi):
+    """Wavefronts of one gain launch over the planes [x_lo, x_hi) (launch_gain_field): each adds its share of the two
+    convergence sums with one atomicAdd."""
+    hy, hz = tr.grid_shape[1], tr.grid_shape[2]
+    if pair_once:
+        return (x_hi - x_lo) * hy                                       # one single-wavefront workgroup per z-row
+    bricks = (((x_hi + 1) >> 1) - (x_lo >> 1)) * ((hy + 3) // 4) * ((hz + 7) // 8)
+    return 4 * min((bricks + 3) // 4, 256 * 64)                         # four wavefronts per workgroup
+
+
+def _group_errors(a, b, scale):
+    return [float(np.abs(a[..., z] - b[..., z]).max() / scale) for z in Z_GROUPS]
+
+
+# ---- A1. real fields on 48 x 21 x 134 ---------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def world(api, oracle, inputs, torch_cuda):
+    bn = inputs[0][BEAMS].copy()
+    _, r, ne, te = inputs
+    tr = _tracer(api, inputs, SHAPE, bn)
+    cfg = oracle.default_config(SHAPE[0], nbeams=len(BEAMS), ny=SHAPE[1], nz=SHAPE[2])
+    assert oracle.grid_shape(cfg) == tr.grid_shape == (50, 23, 136)
+    ne3d, kap = oracle.node_tables(cfg, r, ne, te)
+    og = oracle.gain_default()
+    ofields = np.stack([oracle.trace_cbet(cfg, og, bn, ne3d, kap, quantity=q, per_beam=True, nthreads=NCPU)[0]
+                        for q in (1, 2, 3, 4)])
+    ogain, _ = oracle.gain_field(cfg, og, ofields, ne3d, relax=1.0, nthreads=NCPU)
+    scale = float(np.abs(ogain).max())
+    # the regime: a non-trivial gain (1/cm), and most of it beyond the first 64 cells of its z-row
+    assert scale > 1.0
+    assert int((ogain[..., 64:] != 0).sum()) >= 10000
+    assert all(np.abs(ogain[..., z]).max() > 1e-3 * scale for z in Z_GROUPS[:2])
+    gp = api.default_gain_params(relax=1.0)
+    raw = torch_cuda.from_numpy(ofields).cuda()
+    yield dict(tr=tr, cfg=cfg, og=og, ne3d=ne3d, ofields=ofields, ogain=ogain, scale=scale, gp=gp, raw=raw)
+    tr.close()
+
+
+@pytest.fixture(scope="module")
+def updates(api, world, torch_cuda):
+    """Both kernels on the oracle's fields: first call, frozen call, and a first call with relax = 0.25."""
+    tr, raw = world["tr"], world["raw"]
+    out = {}
+    for pair_once in (False, True):
+        res = _first_and_frozen(torch_cuda, tr, raw, world["gp"], pair_once)
+        _, k3, _ = _update(torch_cuda, tr, raw, api.default_gain_params(relax=0.25), pair_once, change=False)
+        out[pair_once] = res + (k3.cpu().numpy(),)
+    return out
+
+
+def test_ordered_kernel_equals_the_oracle_bitwise(world, updates):
+    f, k, ch, f2, k2, k3 = updates[False]
+    want, scale = world["ogain"], world["scale"]
+    print("48x21x134 ordered: max |K - oracle| / max |K| = %.3e, by 64-cell z group %s" %
+          (np.abs(k - want).max() / scale, _group_errors(k, want, scale)))
+    assert np.array_equal(k, want)
+
+
+def test_pair_once_kernel_matches_oracle_and_ordered_in_every_z_group(world, updates):
+    k_o, k_p = updates[False][1], updates[True][1]
+    want, scale = world["ogain"], world["scale"]
+    err = float(np.abs(k_p - want).max() / scale)
+    by_group_oracle = _group_errors(k_p, want, scale)
+    by_group = _group_errors(k_p, k_o, scale)
+    print("48x21x134 pair-once: max |K - oracle| / max |K| = %.3e (by z group %s); against the ordered kernel %.3e (by z group %s)"
+          % (err, by_group_oracle, float(np.abs(k_p - k_o).max() / scale), by_group))
+    assert err < TOL
+    assert np.abs(k_p - k_o).max() < LAST_BITS * scale
+    for z, e, eo in zip(Z_GROUPS, by_group, by_group_oracle):       # each group against the WHOLE grid's max |K|
+        assert e < LAST_BITS, (z, e)
+        assert eo < TOL, (z, eo)
+    # beyond the first group the pair-once kernel really has something to get wrong
+    assert int((k_p[..., 64:] != 0).sum()) >= 10000
+
+
+@pytest.mark.parametrize("pair_once", [False, True], ids=["ordered", "pair_once"])
+def test_fields_change_exchange_frozen_and_relaxed(world, updates, pair_once):
+    """What test_gain_field_matches_oracle_and_is_antisymmetric asks of the 32^3 cube, on this grid."""
+    tr = world["tr"]
+    nf, K, ch, f2, k2, k3 = updates[pair_once]
+    want, scale, ofields = world["ogain"], world["scale"], world["ofields"]
+    assert abs(ch[0] / ch[1] - 1.0) < 1e-12                     # from zero: every |new - old| is |new|
+    assert abs(ch[1] / np.abs(want).sum() - 1.0) < 1e-9
+    inten = np.where(nf[0] > 0, nf[0], 0.0)
+    exch = (inten * K).sum(axis=0)
+    bound = np.abs(inten * K).sum(axis=0).max()
+    print("48x21x134 %s: exchange per cell %.3e of the largest; frozen %.3e, relax 0.25 %.3e of max |K|" %
+          ("pair-once" if pair_once else "ordered", np.abs(exch).max() / bound, np.abs(k2 - K).max() / scale,
+           np.abs(k3 - 0.25 * K).max() / scale))
+    assert np.abs(exch).max() <= 1e-11 * bound
+    kmag = np.sqrt(nf[1] ** 2 + nf[2] ** 2 + nf[3] ** 2)
+    present, touched = ofields[0] > 0, ofields[0] != 0
+    assert np.all(kmag[touched] <= tr.derived.omega / 2.99792458e10 * (1 + 1e-12))
+    assert np.array_equal(nf[:, ~touched], ofields[:, ~touched])    # untouched entries are left alone
+    assert not nf[0][touched & ~present].any()
+    assert np.abs(k2 - K).max() < 1e-12 * scale                     # frozen directions, fresh energy: the same K
+    assert np.array_equal(f2[1:], nf[1:])                           # ... and the k entries are left alone
+    assert np.abs(k3 - 0.25 * K).max() < 1e-12 * scale              # relax = 0.25 from zero: a quarter of the way
+
+
+def test_both_kernels_normalise_to_the_same_bits(updates):
+    assert np.array_equal(updates[True][0].view(np.int64), updates[False][0].view(np.int64))
+    assert np.array_equal(updates[True][3].view(np.int64), updates[False][3].view(np.int64))
+
+
+# ---- A2. synthetic crowded fields on 13 x 11 x 148, 60 beams ----------------------------------------------------------
+def _crowded_fields(shape):
+    """The generator of test_pair_once_kernel_on_crowded_cells_equals_the_ordered_kernel in numpy, energies of the order of
+    real deposits (x 1e11): (fields [4, 60, ...], present mask)."""
+    rng = np.random.default_rng(20261018)
+    u = rng.random(shape)
+    row = rng.random(shape[:3] + (1,))                          # a beam crosses a z-row or not
+    x = np.arange(shape[1]).reshape(1, -1, 1, 1)
+    density = np.where(x < 5, 0.15, np.where(x < 10, 0.45, 0.9))
+    present = (row < density) & (u < 0.8)
+    touched_only = (row < density + 0.03) & ~present & (u < 0.9)
+    e = (rng.random(shape) * 1e3 + 1.0) * 1e11
+    raw = np.zeros((4,) + shape)
+    raw[0] = np.where(present, e, np.where(touched_only, -e, 0.0))
+    raw[1:] = (rng.random((3,) + shape) - 0.5) * (raw[0] != 0)
+    return raw, present
+
+
+def test_crowded_long_rows_match_the_oracle(api, oracle, inputs, torch_cuda):
+    """Up to ~54 beams per cell in rows of 150 cells: the halves and quarters arms (sh = 3, 2) in runs of the second and
+    third state group, touched-but-absent and untouched entries, super-critical nodes -- oracle, ordered kernel (bitwise)
+    and pair-once kernel, first call and frozen."""
+    bn, r, ne, te = inputs
+    tr = _tracer(api, inputs, CROWDED, bn)
+    assert tr.grid_shape == (15, 13, 150)
+    raw, present = _crowded_fields((60,) + tr.grid_shape)
+    assert (raw[0] < 0).any() and (raw[0] == 0).any()
+    windows = np.stack([present[..., z0:z0 + 16].any(-1).sum(0) for z0 in range(64, tr.grid_shape[2], 16)])
+    classes = [int((windows <= 20).sum()), int(((windows > 20) & (windows <= 40)).sum()), int((windows > 40).sum())]
+    assert min(classes) >= 50, classes           # whole runs, halves and quarters, all beyond the first 64 cells
+    cfg = oracle.default_config(CROWDED[0], nbeams=60, ny=CROWDED[1], nz=CROWDED[2])
+    ne3d, _ = oracle.node_tables(cfg, r, ne, te)
+    assert (ne3d >= tr.derived.ncrit).any()      # the eps <= 0 arm runs
+    want, _ = oracle.gain_field(cfg, oracle.gain_default(), raw, ne3d, relax=1.0, nthreads=NCPU)
+    scale = float(np.abs(want).max())
+    assert scale > 1.0
+    assert all(np.abs(want[..., z]).max() > 1e-3 * scale for z in Z_GROUPS)         # something in all three groups
+    gp = api.default_gain_params(relax=1.0)
+    d_raw = torch_cuda.from_numpy(raw).cuda()
+    f_o, k_o, ch_o, f2_o, k2_o = _first_and_frozen(torch_cuda, tr, d_raw, gp, False)
+    f_p, k_p, ch_p, f2_p, k2_p = _first_and_frozen(torch_cuda, tr, d_raw, gp, True)
+    tr.close()
+    err_o, err_p = float(np.abs(k_o - want).max() / scale), float(np.abs(k_p - want).max() / scale)
+    by_group = _group_errors(k_p, k_o, scale)
+    print("13x11x148 crowded (windows by class %s, max |K| %.3e): ordered vs oracle %.3e, pair-once vs oracle %.3e, "
+          "pair-once vs ordered by z group %s, frozen vs first %.3e / %.3e"
+          % (classes, scale, err_o, err_p, by_group, np.abs(k2_o - k_o).max() / scale, np.abs(k2_p - k_o).max() / scale))
+    assert np.array_equal(k_o, want)                          # the oracle's operations in the oracle's order
+    assert err_p < TOL
+    assert np.abs(k_p - k_o).max() < LAST_BITS * scale
+    for z, e in zip(Z_GROUPS, by_group):
+        assert e < LAST_BITS, (z, e)
+        assert np.abs(k_p[..., z] - want[..., z]).max() < TOL * scale, z
+    assert np.array_equal(f_p.view(np.int64), f_o.view(np.int64)) and np.array_equal(f2_p.view(np.int64), f2_o.view(np.int64))
+    assert np.abs(k2_p - k_o).max() < 1e-12 * scale and np.abs(k2_o - k_o).max() < 1e-12 * scale
+    assert abs(ch_p[1] / ch_o[1] - 1.0) < 1e-12 and abs(ch_p[0] / ch_o[0] - 1.0) < 1e-12
+    inten = np.where(f_p[0] > 0, f_p[0], 0.0)
+    assert np.abs((inten * k_p).sum(axis=0)).max() <= 1e-11 * np.abs(inten * k_p).sum(axis=0).max()
+
+
+# ---- A3. the FLOW arms on a non-cubic grid ----------------------------------------------------------------------------
+@pytest.mark.parametrize("pair_once", [False, True], ids=["ordered", "pair_once"])
+def test_the_spheres_table_changes_no_bit_off_the_cube(api, torch_cuda, world, pair_once):
+    """tabulate_flow(target=None) selected against no flow selected, the whole grid and the slab [9, 22): gain and normalised
+    fields bit for bit; the convergence sums to the rounding of their accumulation order."""
+    torch = torch_cuda
+    tr, gp, raw = world["tr"], world["gp"], world["raw"]
+
+    def calls():
+        out = list(_update(torch, tr, raw, gp, pair_once)) + list(_update(torch, tr, raw, gp, pair_once, x=SLAB))
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out]
+
+    assert tr.ctx.flow() is None
+    plain = calls()
+    api.tabulate_flow(tr.ctx, tr.params, gp, None, _stream(torch))
+    try:
+        assert tr.ctx.flow() is not None
+        table = calls()
+    finally:
+        tr.ctx.set_flow(None)
+    assert np.abs(plain[1]).max() > 1.0 and np.abs(plain[4]).max() > 1.0
+    # the two sums take one fp64 atomicAdd per wavefront in the order the wavefronts finish, so two runs of the SAME kernel
+    # need not agree in the last bits.  Every wavefront's addend is the same bits in both calls (the gain is); sums of n
+    # non-negative addends taken in two orders differ by at most (n - 1) 2^-53 relative (tests/test_gpu_flow.py), with n this
+    # launch's own wavefront count:
+    waves = {"": _waves(tr, pair_once, 0, tr.grid_shape[0]), "slab ": _waves(tr, pair_once, *SLAB)}
+    assert waves[""] == (1150 if pair_once else 2552) and waves["slab "] == (299 if pair_once else 716)
+    for (where, what), a, b in zip([(w, n) for w in ("", "slab ") for n in ("fields", "gain", "change")], plain, table):
+        if what == "change":
+            print("%s%s: %s against %s (%d wavefronts)" % (where, what, a.tolist(), b.tolist(), waves[where]))
+            assert np.all(np.abs(a - b) <= (waves[where] - 1) * 2.0 ** -53 * np.abs(a)), where + what
+        else:
+            assert np.array_equal(a.view(np.int64), b.view(np.int64)), where + what
+
+
+def test_callers_table_of_an_offset_target_matches_the_shifted_oracle(api, oracle, torch_cuda, world):
+    """The host twin's flow table of a target SHIFT off centre, handed in as a caller's table: the gain of both kernels
+    against the oracle with its box moved by -SHIFT (its flow, centred on its origin, then sits where the target does)."""
+    torch = torch_cuda
+    tr, gp, og = world["tr"], world["gp"], world["og"]
+    cfg = oracle.default_config(SHAPE[0], nbeams=len(BEAMS), ny=SHAPE[1], nz=SHAPE[2])
+    cfg.xmin -= SHIFT[0]; cfg.xmax -= SHIFT[0]
+    cfg.ymin -= SHIFT[1]; cfg.ymax -= SHIFT[1]
+    cfg.zmin -= SHIFT[2]; cfg.zmax -= SHIFT[2]
+    want, _ = oracle.gain_field(cfg, og, world["ofields"], world["ne3d"], relax=1.0, nthreads=NCPU)
+    scale = float(np.abs(want).max())
+    assert scale > 1.0
+    moved = float(np.abs(want - world["ogain"]).max())
+    print("48x21x134 offset: the oracle's shifted and centred gains differ by %.3e of max |K|" % (moved / scale))
+    assert moved >= 100 * TOL * scale                                       # a kernel that ignores the table cannot pass
+    table = api.flow_table(tr.params, gp, api.Target(SHIFT))
+    assert table.shape == (3,) + SHAPE
+    tr.set_flow(torch.from_numpy(table).cuda())
+    try:
+        for pair_once in (False, True):
+            _, k, _ = _update(torch, tr, world["raw"], gp, pair_once, change=False)
+            k = k.cpu().numpy()
+            err = float(np.abs(k - want).max() / scale)
+            print("48x21x134 offset, %s kernel: max |K - oracle| / max |K| = %.3e, by z group %s" %
+                  ("pair-once" if pair_once else "ordered", err, _group_errors(k, want, scale)))
+            assert err < TOL, (pair_once, err)
+    finally:
+        tr.set_flow(None)
+
+
+# ---- A4. slabs and packed storage -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pair_once", [False, True], ids=["ordered", "pair_once"])
+def test_update_by_slabs_equals_the_whole_off_the_cube(api, torch_cuda, world, updates, pair_once):
+    """The cuts of test_gain_update_by_slabs_equals_the_whole (odd boundaries through the two-plane bricks) on planes of
+    23 * 136 doubles: bit for bit the whole grid's update, cells outside a slab untouched, the convergence sums add up."""
+    torch = torch_cuda
+    tr, gp = world["tr"], world["gp"]
+    ref = tr.new_grid(per_beam=True).fill_(-7.0)
+    ch_ref = torch.zeros(2, dtype=torch.float64, device="cuda")
+    tr.gain_field(world["raw"].clone(), ref, gp, ch_ref, pair_once=pair_once)
+    parts = tr.new_grid(per_beam=True).fill_(-7.0)
+    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
+    fields = world["raw"].clone()
+    for x0, x1 in zip(CUTS[:-1], CUTS[1:]):
+        before = parts.clone()
+        tr.gain_field(fields, parts, gp, ch, pair_once=pair_once, x_lo=x0, x_hi=x1)
+        assert torch.equal(parts[:, :x0], before[:, :x0]) and torch.equal(parts[:, x1:], before[:, x1:])
+    assert torch.equal(parts, ref)
+    assert torch.equal(fields, torch.from_numpy(updates[pair_once][0]).cuda())
+    assert float(((ch - ch_ref).abs() / ch_ref).max()) < 1e-12               # atomically accumulated: order differs
+    with pytest.raises(api.CbetError):
+        tr.gain_field(fields, parts, gp, None, x_lo=5, x_hi=SHAPE[0] + 3)
+
+
+@pytest.mark.parametrize("pair_once", [False, True], ids=["ordered", "pair_once"])
+def test_packed_slab_equals_whole_grid_storage_off_the_cube(api, torch_cuda, world, pair_once):
+    """cbet_gain_field_packed on the planes [9, 22) alone (store0 = 9 * 23 * 136 = 28152 = 8 mod 16: the pair-once
+    kernel's runs start half a line off the whole grid's), as test_packed_slab_storage_equals_whole_grid_storage."""
+    torch = torch_cuda
+    tr, gp = world["tr"], world["gp"]
+    x0, x1 = SLAB
+    assert (x0 * tr.grid_shape[1] * tr.grid_shape[2]) % 16 == 8
+    f_ref, ref, ch_ref = _update(torch, tr, world["raw"], gp, pair_once, x=SLAB)
+    f_pk = world["raw"][:, :, x0:x1].contiguous()
+    g_pk = torch.zeros_like(ref[:, x0:x1]).contiguous()
+    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
+    api.gain_field_packed(f_pk, None, g_pk, torch.empty_like(g_pk) if pair_once else None, ch, x0, x1, tr.params, gp,
+                          tr.ctx, _stream(torch))
+    scale = float(ref.abs().max())
+    assert scale > 1.0 and not bool(ref[:, :x0].any()) and not bool(ref[:, x1:].any())
+    err = float((g_pk - ref[:, x0:x1]).abs().max()) / scale
+    print("48x21x134 packed slab [9, 22), %s: max |K packed - K whole| / max |K| = %.3e" %
+          ("pair-once" if pair_once else "ordered", err))
+    assert torch.equal(f_pk, f_ref[:, :, x0:x1])                    # the normalisation is cell-local arithmetic
+    if pair_once:
+        assert err < LAST_BITS                                      # the runs, and with them the grouping, follow the storage
+    else:
+        assert torch.equal(g_pk, ref[:, x0:x1])
+    assert float(((ch - ch_ref).abs() / ch_ref).max()) < 1e-12
+
+
+# ---- A5. arrays that do not start on a 128-byte line --------------------------------------------------------------------
+@pytest.mark.parametrize("offset", [1, 8])
+@pytest.mark.parametrize("pair_once", [False, True], ids=["ordered", "pair_once"])
+def test_views_off_the_line_give_the_aligned_bits(torch_cuda, world, updates, pair_once, offset):
+    """include/cbet_mi355x.h, cbet_gain_field: the arrays need the alignment of a double only, and the result does not depend
+    on where they start -- the pair-once kernel cuts its runs by element index, not by address.  Fields and gain as views
+    1 and 8 doubles into larger allocations: both kernels give the bits of the aligned call."""
+    torch = torch_cuda
+    tr, gp, raw = world["tr"], world["gp"], world["raw"]
+    room_f = torch.full((raw.numel() + 16,), float("nan"), dtype=torch.float64, device="cuda")
+    room_k = torch.full((raw[0].numel() + 16,), float("nan"), dtype=torch.float64, device="cuda")
+    assert room_f.data_ptr() % 128 == 0 and room_k.data_ptr() % 128 == 0
+    f = room_f[offset:offset + raw.numel()].view(raw.shape)
+    k = room_k[offset:offset + raw[0].numel()].view(raw[0].shape)
+    assert f.is_contiguous() and k.is_contiguous() and f.data_ptr() % 128 == (8 * offset) % 128 == k.data_ptr() % 128
+    f.copy_(raw)
+    k.zero_()
+    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
+    tr.gain_field(f, k, gp, ch, pair_once=pair_once)
+    nf, K, ch_al = updates[pair_once][:3]
+    scale = world["scale"]
+    err = float(np.abs(k.cpu().numpy() - K).max() / scale)
+    print("48x21x134 %s, arrays %d double(s) off the line: max |K - K aligned| / max |K| = %.3e" %
+          ("pair-once" if pair_once else "ordered", offset, err))
+    assert err < LAST_BITS
+    assert np.array_equal(k.cpu().numpy().view(np.int64), K.view(np.int64))
+    assert np.array_equal(f.cpu().numpy().view(np.int64), nf.view(np.int64))
+    assert np.all(np.abs(ch.cpu().numpy() - ch_al) <= 1e-12 * ch_al)
+    # nothing outside the views was written
+    for room, n in ((room_f, raw.numel()), (room_k, raw[0].numel())):
+        assert bool(torch.isnan(room[:offset]).all()) and bool(torch.isnan(room[offset + n:]).all())

@@ -1,8 +1,12 @@
 """Mode spectra on the GPU (include/cbet_mi355x.h cbet_sph_modes_device): the device projection
-against the host cbet_sph_modes on the real OMEGA deposit, determinism (run to run, padded rows), linearity in the
-beams (per-beam grids, power balance), the symmetry of the cubic lattice, and the 256^3 totals."""
+against the host cbet_sph_modes on the real OMEGA deposit and on seeded grids off the cube (three different sides, off-centre
+and unequally spaced boxes, a centre outside the box, run-time lmax below the instantiated one, empty shells), determinism
+(run to run, padded rows), linearity in the beams (per-beam grids, power balance), the symmetry of the cubic lattice, and the
+256^3 totals."""
 import numpy as np
 import pytest
+
+from helpers import modes_shapes as S
 
 pytestmark = pytest.mark.gpu
 
@@ -102,6 +106,103 @@ def test_device_equals_host_100(api, modes, t100):
     tr, single = t100
     _against_host(api, tr, single, modes.default_shells(tr.params, 32), 16)
     _against_host(api, tr, single, np.linspace(0.0, CORNER * 1.001, 40), 32, center=(0.002, 0.003, -0.001))
+
+
+# ---- off the cube (tests/helpers/modes_shapes.py; the host twin's own check of these cases is in test_modes_host.py) ----
+def _worst(api, tr, dc, hc, host_grid, edges, center):
+    """max |da| over the shell's sum |E| (geometry: its node count), for the printed figure."""
+    if host_grid is None:
+        absE = api.sph_modes_host(None, tr.params, center, edges, 0)[1]
+    else:
+        absE = api.sph_modes_host(np.abs(host_grid), tr.params, center, edges, 0)[1]
+    full = absE > 0
+    return float((np.abs(dc - hc)[full] / absE[full][:, None]).max())
+
+
+def _shaped_tracer(api, inputs, name):
+    """A tracer of the case's grid and box as the handle of sph_modes (nothing is traced)."""
+    from cbet_raytracing_3d_amd.tracer import RayTracer
+    bn, r, ne, te = inputs
+    return RayTracer(S.params(api, name, nbeams=1), r, ne, te, beam_norm=bn[:1])
+
+
+@pytest.fixture(scope="module", params=S.NAMES)
+def shaped(request, api, inputs, torch_cuda):
+    """The case's tracer and a stack of seven seeded grids of both signs."""
+    name = request.param
+    tr = _shaped_tracer(api, inputs, name)
+    stack = torch_cuda.from_numpy(S.grids(name, 7)).cuda()
+    yield name, tr, stack
+    tr.close()
+
+
+def test_device_equals_host_off_the_cube(api, shaped):
+    """Three different sides (the node decode, `plane`), off-centre and unequally spaced boxes (node_range per axis), a
+    centre outside the box, lmax 5 / 3 / 1 under <16> and 17 under <32> (odd: the middle m-group drops its second half),
+    shells without a node: one grid, a stack of three (one ragged block of the four-grid kernel), a stack of seven (a full
+    block and a ragged one), and geometry mode."""
+    name, tr, stack = shaped
+    _, shape, _, center, lmax = S.BY_NAME[name]
+    assert tuple(stack.shape[1:]) == tr.grid_shape == (shape[0] + 2, shape[1] + 2, shape[2] + 2)
+    assert lmax % 2 == 1
+    for what, grid in (("one grid", stack[0].contiguous()), ("stack of 3", stack[:3].contiguous()), ("stack of 7", stack),
+                       ("geometry", None)):
+        dc, hc = _against_host(api, tr, grid, S.EDGES, lmax, center=center, geometry=grid is None)
+        _, _, dn = tr.sph_modes(grid, S.EDGES, lmax, center, grid is None)
+        dn = dn.cpu().numpy()
+        # the regime (asserted on the host twin's cases in test_modes_host.py too): the thin shell and one more are empty
+        assert dn[S.THIN] == 0 and int((dn == 0).sum()) >= 2 and int((dn > 0).sum()) >= 2
+        assert not dc[:, dn == 0].any()                                       # an empty shell is written, with zeros
+        print("%-15s lmax %2d %-10s: max |da - host| / sum |E| = %.2e" %
+              (name, lmax, what, _worst(api, tr, dc, hc, None if grid is None else grid.cpu().numpy(), S.EDGES, center)))
+
+
+def test_padded_rows_off_the_cube_give_the_dense_bits(api, inputs, torch_cuda):
+    """On 12 x 7 x 70: rows padded to whole lines (nz + 2 = 72 is one already: zpitch=True is the dense grid) and to an odd
+    pitch of 77 doubles, the padding NaN, against the dense grid -- bit for bit."""
+    torch = torch_cuda
+    name = "long_z"
+    _, shape, _, center, lmax = S.BY_NAME[name]
+    assert shape == (12, 7, 70)
+    tr = _shaped_tracer(api, inputs, name)
+    dense = torch.from_numpy(S.grids(name, 1)[0]).cuda()
+    want = tr.sph_modes(dense, S.EDGES, lmax, center)
+    for pitch in (True, 77):
+        padded = tr.new_grid(zpitch=pitch)
+        assert padded.shape[2] == (72 if pitch is True else 77)
+        padded.fill_(float("nan"))
+        padded[..., : dense.shape[2]] = dense
+        got = tr.sph_modes(padded, S.EDGES, lmax, center)
+        for x, y in zip(want, got):
+            assert torch.equal(x, y)
+    assert bool(want[2].sum() > 0)
+    tr.close()
+
+
+LMAX_SWEEP = (0, 1, 2, 3, 5, 15, 17, 31)
+
+
+def test_lmax_sweep_is_a_prefix_of_lmax_32(api, modes, t64):
+    """A run-time lmax below the instantiated one -- 0, 1, 2, 3, 5, 15 under <16>, 17 and 31 under <32> -- on the real 64^3
+    deposit: against the host twin, and against the leading (lmax + 1)^2 columns of the lmax = 32 result (a truncated
+    expansion is a prefix of the longer one), both within 1e-11 x the shell's sum |E|."""
+    tr, single, _ = t64
+    shells = modes.default_shells(tr.params, 32)
+    host_grid = single.cpu().numpy()
+    _, absE, _ = api.sph_modes_host(np.abs(host_grid), tr.params, (0.0, 0.0, 0.0), shells, 0)
+    absE = absE[0]
+    assert (absE > 0).sum() > 16
+    a32 = tr.sph_modes(single, shells, 32)[0].cpu().numpy()
+    for lmax in LMAX_SWEEP:
+        dc, hc = _against_host(api, tr, single, shells, lmax)
+        n = (lmax + 1) ** 2
+        assert dc.shape == (1, 32, n)
+        diff = np.abs(dc[0] - a32[:, :n])
+        full = absE > 0
+        print("lmax %2d: max |da - host| / sum |E| = %.2e, against the lmax 32 prefix %.2e" %
+              (lmax, (np.abs(dc - hc)[0][full] / absE[full][:, None]).max(), (diff[full] / absE[full][:, None]).max()))
+        assert np.all(diff <= 1e-11 * absE[:, None]), lmax
+    assert np.abs(a32[:, 1:]).max() > 1e-6 * np.abs(a32[:, 0]).max()          # (not a spectrum of zeros beyond l = 0)
 
 
 def test_bitwise_reproducible_and_padded_rows(modes, t64, torch_cuda):

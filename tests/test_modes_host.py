@@ -1,6 +1,7 @@
 """Mode spectra, host side (no GPU): the entry points exported and refusing bad arguments before touching a device;
 the host cbet_sph_modes against an independent numpy restatement node by node (closed forms for l <= 2, scipy's
-sph_harm_y without its (-1)^m above); the gfx950 listing of cbet_sph_modes.hip (cross-compiled here)."""
+sph_harm_y without its (-1)^m above), on cubes and on the cases off the cube of tests/helpers/modes_shapes.py; the gfx950
+listing of cbet_sph_modes.hip (cross-compiled here)."""
 import ctypes as C
 import math
 import os
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from helpers import modes_shapes as S
 
 CSRC = os.path.join(ROOT, "cbet_raytracing_3d_amd", "csrc")
 
@@ -172,6 +174,41 @@ def test_host_matches_numpy_scipy(api, n, center, edges, G, lmax):
     err = np.abs(coeffs - want) / absE[..., None]
     assert err.max() <= 1e-13, err.max()
     assert np.all(np.abs(energy - want_e) <= 1e-13 * absE)
+
+
+@pytest.mark.parametrize("name", S.NAMES)
+def test_host_matches_numpy_off_the_cube(api, name):
+    """tests/helpers/modes_shapes.py: grids with three different sides, an off-centre box, unequal spacing, a centre
+    outside the box, odd and small lmax, empty shells -- three grids with values of both signs, and geometry mode."""
+    _, shape, _, center, lmax = S.BY_NAME[name]
+    p = S.params(api, name)
+    assert (p.nx, p.ny, p.nz) == shape and len({p.nx, p.ny, p.nz}) == 3
+    X, Y, Z, r = _nodes(api, p, center)
+    assert r.shape == (shape[0] + 2, shape[1] + 2, shape[2] + 2)
+    Yc = _ylm_scipy(lmax, X, Y, Z, r)
+    nc = min(9, (lmax + 1) ** 2)
+    assert np.allclose(Yc[:nc], _ylm_closed(X, Y, Z, r)[:nc], rtol=0, atol=1e-13)
+    grids = S.grids(name)
+    assert (grids < 0).any() and (grids > 0).any()
+    coeffs, energy, nodes = api.sph_modes_host(grids, p, center, S.EDGES, lmax)
+    want, want_e, absE, want_n = _numpy_modes(grids, r, S.EDGES, Yc)
+    # the regime: a shell too thin to hold a node, a second empty one, and shells that do hold nodes
+    assert want_n[S.THIN] == 0 and int((want_n == 0).sum()) >= 2 and int((want_n > 0).sum()) >= 2
+    if name == "centre_outside":
+        assert X.max() < -0.1                                   # every node, halo included, lies to one side of the centre
+    else:
+        assert want_n[-1] == 0 and r.max() < S.EDGES[-2]        # the last shell lies beyond every node
+    assert coeffs.shape == (3, len(S.EDGES) - 1, (lmax + 1) ** 2)
+    assert np.array_equal(nodes, want_n)
+    err = np.abs(coeffs - want) / np.maximum(absE[..., None], 1e-300)
+    print("%s: host twin vs numpy/scipy, max |da| / sum |E| = %.2e, nodes per shell %s" % (name, err.max(), want_n.tolist()))
+    assert np.all(np.abs(coeffs - want) <= 1e-13 * absE[..., None])
+    assert np.all(np.abs(energy - want_e) <= 1e-13 * absE)
+    assert not coeffs[:, want_n == 0].any() and not energy[:, want_n == 0].any()      # an empty shell gives zeros
+    gc, ge, gn = api.sph_modes_host(None, p, center, S.EDGES, lmax)
+    wc, _, wa, _ = _numpy_modes(np.ones((1,) + r.shape), r, S.EDGES, Yc)
+    assert np.array_equal(gn, want_n) and np.array_equal(ge[0], want_n.astype(np.float64))
+    assert np.all(np.abs(gc - wc) <= 1e-13 * wa[..., None])
 
 
 def test_host_padded_rows_give_the_dense_bits(api):
