@@ -1,4 +1,4 @@
-// cbet_device.h -- argument blocks shared by the host ABI (cbet_abi.cpp) and the gfx950 kernels
+// cbet_device.h -- argument blocks shared by the host ABI (cbet_*_abi.cpp, cbet_host_internal.h) and the gfx950 kernels
 // (cbet_kernels.hip).  Internal; the public boundary is include/cbet_mi355x.h.
 #ifndef CBET_DEVICE_H_
 #define CBET_DEVICE_H_

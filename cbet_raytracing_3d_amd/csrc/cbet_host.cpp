@@ -26,11 +26,7 @@
 #include <thread>
 #include <vector>
 
-#include "cbet_mi355x.h"
-
-namespace cbet {
-int fail(int code, const char *fmt, ...);
-}
+#include "cbet_host_internal.h"
 
 namespace {
 
@@ -91,22 +87,14 @@ void release(DeviceJob &j)
 
 }  // namespace
 
-namespace {
-// rayTracing() leaves the process on whatever device it touched last (and ends with
-// cudaDeviceReset, main.cu:217); here the caller's current device is restored instead.
-struct RestoreDevice {
-    int saved = -1;
-    RestoreDevice() { if (hipGetDevice(&saved) != hipSuccess) saved = -1; }
-    ~RestoreDevice() { if (saved >= 0) (void)hipSetDevice(saved); (void)hipGetLastError(); }
-};
-}  // namespace
-
 extern "C" int cbet_ray_tracing(const double *te_profile, const double *r_profile,
                                 const double *ne_profile, double *edep, const cbet_params *p,
                                 const double *beam_norm, const int *gpus, int ngpu, double *timers,
                                 cbet_counters *counters)
 {
-    RestoreDevice restore_device;
+    // rayTracing() leaves the process on whatever device it touched last (and ends with cudaDeviceReset, main.cu:217);
+    // here the caller's current device is restored instead, and no sticky HIP error outlives the call
+    cbet::DeviceGuard restore_device(true);
     if (!te_profile || !r_profile || !ne_profile || !edep || !p)
         return cbet::fail(CBET_EINVAL, "cbet_ray_tracing: NULL argument");
     if (ngpu < 1) return cbet::fail(CBET_EINVAL, "cbet_ray_tracing: ngpu < 1");
@@ -182,7 +170,7 @@ extern "C" int cbet_ray_tracing(const double *te_profile, const double *r_profil
     }
     auto first_error = [&]() -> int {
         for (auto &j : jobs)
-            if (j.rc) return cbet::fail(j.rc, "device %d: %s", j.gpu, j.err.c_str());
+            if (j.rc) return cbet::fail_hip(j.rc, "device %d: %s", j.gpu, j.err.c_str());   // (j.rc may be a HIP code)
         return CBET_OK;
     };
     if (int rc = first_error()) {

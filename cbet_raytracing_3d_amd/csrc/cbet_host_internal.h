@@ -1,0 +1,130 @@
+// cbet_host_internal.h -- what the host .cpp files share and nothing outside them sees: the error helpers, the device
+// guard, the per-device context, the checks every entry point starts with and ONE builder per kernel argument block
+// (a device kernel and its host twin run the same statements on arguments filled by the same function).
+#ifndef CBET_HOST_INTERNAL_H_
+#define CBET_HOST_INTERNAL_H_
+
+#include <hip/hip_runtime_api.h>
+
+#include <vector>
+
+#include "cbet_device.h"
+#include "cbet_mi355x.h"
+
+struct cbet_context {
+    int gpu = -1;
+    cbet_params p{};
+    cbet_derived d{};
+    double *ne3d = nullptr, *kap3d = nullptr;
+    cbet::StepRecord *steprec = nullptr;  // per-node step records of the LDS_WINDOW kernel (cbet_device.h)
+    // what the records were built from: valid while the context's own tables are unchanged (tables_version)
+    unsigned long long tables_version = 0, rec_version = ~0ull;
+    unsigned long long rec_builds = 0;  // launches that wrote the records (cbet_context_step_records)
+    const double *rec_ne3d = nullptr, *rec_kap3d = nullptr;
+    double rec_const[3] = {0, 0, 0};
+    double *xlaunch = nullptr, *ylaunch = nullptr;
+    double *bounds = nullptr;  // {xlo,xhi,ylo,yhi,zlo,zhi}
+    int *live = nullptr;
+    int nlive = 0;  // launch-list slots (64 per bundle, holes included)
+    unsigned long long *counters = nullptr;
+    // flow table of the gain kernels (cbet_tabulate_flow / cbet_context_set_flow): NULL = the closed-form ramp
+    double *flow_own = nullptr;         // the context's own [3][nx*ny*nz] table, allocated by the first cbet_tabulate_flow
+    const double *flow = nullptr;       // the table in use: flow_own, a caller's, or NULL
+};
+
+namespace cbet {
+#pragma GCC visibility push(hidden)   // internal: none of these is an exported symbol
+
+// fail (cbet_params.cpp) only records the text, so that file links without the HIP runtime.  HIP keeps its last error
+// sticky until read, and a reported failure must not leak into the caller's (or torch's) next hipGetLastError() check:
+// every return of CBET_EHIP, CBET_ENODEVICE or CBET_ENOMEM goes through fail_hip, which reads it away.
+int fail(int code, const char *fmt, ...);
+template <class... Values>
+int fail_hip(int code, const char *fmt, Values... values)
+{
+    (void)hipGetLastError();
+    return fail(code, fmt, values...);
+}
+
+#define CBET_HIP(call)                                                                          \
+    do {                                                                                        \
+        hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return ::cbet::fail_hip(CBET_EHIP, "%s failed: %s", #call, hipGetErrorString(e_));  \
+    } while (0)
+
+// Restores the caller's current device on scope exit (moveToAndFromGPU's save/restore, multi_gpu.cpp:50-57);
+// clear_sticky: and leaves no sticky HIP error behind, whatever happened in the scope (cbet_ray_tracing).
+struct DeviceGuard {
+    int saved = -1;
+    bool clear_sticky;
+    explicit DeviceGuard(bool clear = false) : clear_sticky(clear) { if (hipGetDevice(&saved) != hipSuccess) saved = -1; }
+    ~DeviceGuard()
+    {
+        if (saved >= 0) (void)hipSetDevice(saved);
+        if (clear_sticky) (void)hipGetLastError();
+    }
+};
+
+// For the rest of the scope the context's device is current; the caller's comes back on scope exit.
+#define CBET_ENTER_DEVICE(context)                                                                                        \
+    ::cbet::DeviceGuard device_guard_;                                                                                    \
+    if (hipError_t e_ = hipSetDevice((context)->gpu))                                                                     \
+        return ::cbet::fail_hip(CBET_EHIP, "hipSetDevice(ctx->gpu) failed: %s", hipGetErrorString(e_))
+
+// ---- cbet_params.cpp (no HIP call) ----------------------------------------------------------------------
+int validate(const cbet_params *p);
+int validate_gain(const cbet_params *p, const cbet_gain_params *g);
+// validate, the derived constants and the "no threads per beam" refusal, without the launch list that cbet_derive builds
+// and sorts (ntraced_ids and nlive_rays stay 0); derive_launch: with both launch axes and the list.
+int derive_grid(const cbet_params *p, cbet_derived *d);
+int derive_launch(const cbet_params *p, cbet_derived *d, std::vector<double> &xl, std::vector<double> &yl,
+                  std::vector<int> &live);
+
+// ---- cbet_context.cpp -------------------------------------------------------------------------------------
+int check_geometry(const cbet_context *ctx, const cbet_params *p);  // the launch describes the geometry ctx was sized for
+int entry_checks(const cbet_context *ctx, const cbet_params *p);    // ctx != NULL, validate(p), check_geometry: in that order
+int default_context(const cbet_params *p, cbet_context **out);      // the calling thread's device's own, for ctx == NULL
+
+// ---- one builder per argument block -------------------------------------------------------------------------
+// The nine grid scalars of TabulateArgs, TraceArgs, GainArgs, FlowArgs and SphArgs (grid_dims: StepTableArgs' three).
+template <class Args>
+void grid_dims(Args &a, const cbet_params *p)
+{
+    a.nx = p->nx; a.ny = p->ny; a.nz = p->nz;
+}
+template <class Args>
+void grid_args(Args &a, const cbet_params *p, const cbet_derived &d)
+{
+    grid_dims(a, p);
+    a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
+    a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
+}
+// k_tabulate's and its host twin's (cbet_tables_abi.cpp); the twin passes the profiles beside the block.
+TabulateArgs tabulate_args(const cbet_params *p, const cbet_derived &d, double *ne3d, double *kap3d, const double *te,
+                           const double *r, const double *ne);
+// k_tabulate_flow's and its host twin's (cbet_target_host.cpp); target NULL = the sphere about the origin.
+FlowArgs flow_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs,
+                   const cbet_target *target, double *out);
+
+// ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
+int step_records(cbet_context *ctx, const cbet_params *p, const double *ne3d, const double *kappa3d, double xconst,
+                 double yconst, double zconst, void *stream, bool force);
+// CBET hooks of a trace launch (all zero: the reference path).
+struct CbetHooks {
+    const double *gain = nullptr;
+    int quantity = 0;
+    double *beam_gain = nullptr;
+    double max_exponent = 0.0;
+    bool exits = false;     // the exit pass (cbet_trace_exits): `edep` is the record array, no deposit
+};
+int trace_impl(int b, unsigned nindices, const double *ne3d, const double *kappa3d, double *edep, const double *bbeam_norm,
+               const double *beam_norm, const double *pow_r, const double *phase_r, double xconst, double yconst,
+               double zconst, const cbet_params *p, cbet_context *ctx, void *stream, const CbetHooks &hooks);
+int gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo, int hx_hi,
+                    bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx, void *stream,
+                    bool consume = false);
+
+#pragma GCC visibility pop
+}  // namespace cbet
+#endif

@@ -5,11 +5,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cbet_mi355x.h"
-
-namespace cbet {
-int fail(int code, const char *fmt, ...);
-}
+#include "cbet_host_internal.h"
 
 namespace {
 
@@ -103,7 +99,7 @@ extern "C" int cbet_edep_average(const double *edep, double *edepavg, int nx, in
 extern "C" int cbet_node_coordinates(const cbet_params *p, double *x, double *y, double *z)
 {
     cbet_derived d;
-    if (int rc = cbet_derive(p, &d)) return rc;
+    if (int rc = cbet::derive_grid(p, &d)) return rc;
     if (!x || !y || !z) return cbet::fail(CBET_EINVAL, "cbet_node_coordinates: NULL array");
     for (int i = 0; i < p->nx; ++i)
         for (int j = 0; j < p->ny; ++j)

@@ -7,12 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cbet_device.h"
-#include "cbet_mi355x.h"
-
-namespace cbet {
-int fail(int code, const char *fmt, ...);
-}
+#include "cbet_host_internal.h"
 
 namespace {
 
@@ -30,7 +25,7 @@ int sph_check(const double *edep, int ngrids, long grid_stride, const cbet_param
     if (!edep && ngrids != 1) return fail(CBET_EINVAL, "sph_modes: geometry mode (edep NULL) projects one grid, not %d", ngrids);
     if (!center || !r_edges) return fail(CBET_EINVAL, "sph_modes: NULL centre / shell edges");
     if (!coeffs || !shell_energy || !shell_nodes) return fail(CBET_EINVAL, "sph_modes: NULL output");
-    if (int rc = cbet_derive(p, d)) return rc;
+    if (int rc = cbet::derive_grid(p, d)) return rc;
     for (int i = 0; i < 3; ++i)
         if (!std::isfinite(center[i])) return fail(CBET_EINVAL, "sph_modes: centre is not finite");
     if (!(r_edges[0] >= 0.0)) return fail(CBET_EINVAL, "sph_modes: r_edges[0] = %g must be >= 0", r_edges[0]);
@@ -61,18 +56,16 @@ extern "C" int cbet_sph_modes_device(const double *edep, int ngrids, long grid_s
     a.grid_stride = ngrids > 1 ? grid_stride : 0;
     a.row_pitch = pitch;
     a.ngrids = ngrids;
-    a.nx = p->nx; a.ny = p->ny; a.nz = p->nz;
+    cbet::grid_args(a, p, d);
     a.nshell = nshell;
     a.lmax = lmax;
-    a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
-    a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
     a.cx = center[0]; a.cy = center[1]; a.cz = center[2];
     a.coeffs = coeffs;
     a.shell_energy = shell_energy;
     a.shell_nodes = shell_nodes;
     std::memcpy(a.r_edges, r_edges, sizeof(double) * (nshell + 1));
     const hipError_t e = cbet::launch_sph_modes(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CBET_EHIP, "cbet_sph_modes_device: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return cbet::fail_hip(CBET_EHIP, "cbet_sph_modes_device: launch failed: %s", hipGetErrorString(e));
     return CBET_OK;
 }
 

@@ -7,12 +7,10 @@
 #include <cmath>
 #include <cstring>
 
-#include "cbet_device.h"
-#include "cbet_mi355x.h"
+#include "cbet_host_internal.h"
 #include "cbet_target_model.h"
 
 namespace cbet {
-int fail(int code, const char *fmt, ...);
 
 const double *target_factors()
 {
@@ -53,11 +51,27 @@ int target_check(const cbet_target *tg, int *inst)
     return CBET_OK;
 }
 
-void target_fill(const cbet_target *tg, TargetArgs *a)
+// Offset and coefficients (zero beyond the call's lmax) into an argument block that carries ox, oy, oz and c.
+template <class Args>
+static void fill_target(const cbet_target *tg, Args *a)
 {
     a->ox = tg->offset[0]; a->oy = tg->offset[1]; a->oz = tg->offset[2];
     std::memset(a->c, 0, sizeof a->c);
     if (tg->coeffs) std::memcpy(a->c, tg->coeffs, sizeof(double) * (tg->lmax + 1) * (tg->lmax + 1));
+}
+
+void target_fill(const cbet_target *tg, TargetArgs *a) { fill_target(tg, a); }
+
+FlowArgs flow_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs,
+                   const cbet_target *target, double *out)
+{
+    FlowArgs a{};
+    grid_args(a, p, d);
+    a.cs = cs;
+    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
+    a.flow = out;
+    if (target) fill_target(target, &a);
+    return a;
 }
 
 namespace {
@@ -96,18 +110,13 @@ extern "C" int cbet_target_tables(const cbet_params *p, const double *te, const 
 {
     using namespace cbet;
     cbet_derived d;
-    if (int rc = cbet_derive(p, &d)) return rc;
+    if (int rc = derive_grid(p, &d)) return rc;
     if (!te || !r || !ne) return fail(CBET_EINVAL, "NULL profile pointer");
     if (!ne3d || !kappa3d) return fail(CBET_EINVAL, "target_tables: NULL output");
     int inst;
     if (int rc = target_check(target, &inst)) return rc;
-    TargetArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.t.nx = p->nx; a.t.ny = p->ny; a.t.nz = p->nz; a.t.nprofile = p->nprofile;
-    a.t.xmin = p->xmin; a.t.ymin = p->ymin; a.t.zmin = p->zmin;
-    a.t.dx = d.dx; a.t.dy = d.dy; a.t.dz = d.dz; a.t.dt = d.dt;
-    a.t.ncrit = d.ncrit;
-    a.t.ne3d = ne3d; a.t.kap3d = kappa3d;
+    TargetArgs a{};
+    a.t = tabulate_args(p, d, ne3d, kappa3d, nullptr, nullptr, nullptr);   // the profiles go to host_tables beside the block
     target_fill(target, &a);
     switch (inst) {
     case 0: host_tables<0>(a, r, ne, te); break;
@@ -123,27 +132,14 @@ extern "C" int cbet_flow_table(const cbet_params *p, const cbet_gain_params *g, 
 {
     using namespace cbet;
     cbet_derived d;
-    if (int rc = cbet_derive(p, &d)) return rc;
+    if (int rc = derive_grid(p, &d)) return rc;
     double cs = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, nullptr)) return rc;   // (validates the gain parameters)
     if (!out) return fail(CBET_EINVAL, "flow_table: NULL output");
     int inst = 0;
     if (target)
         if (int rc = target_check(target, &inst)) return rc;
-    FlowArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.nx = p->nx; a.ny = p->ny; a.nz = p->nz;
-    a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
-    a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
-    a.cs = cs;
-    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
-    a.flow = out;
-    if (target) {
-        TargetArgs t;
-        target_fill(target, &t);
-        a.ox = t.ox; a.oy = t.oy; a.oz = t.oz;
-        std::memcpy(a.c, t.c, sizeof a.c);
-    }
+    const FlowArgs a = flow_args(p, d, g, cs, target, out);
     switch (inst) {
     case 0: host_flow<0>(a); break;
     case 2: host_flow<2>(a); break;
