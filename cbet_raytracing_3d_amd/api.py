@@ -176,6 +176,71 @@ class Target(C.Structure):
         return np.zeros((self.lmax + 1) ** 2) if self._keep is None else self._keep.copy()
 
 
+# ---- hydro-mesh plasma (cbet_tabulate_mesh) -----------------------------------
+MESH_MAX_COORDS = 2560
+
+
+class Mesh(C.Structure):
+    """cbet_mesh: ne, te and optionally the velocity of a plasma on a spherical-polar mesh about `center` (cm).
+    r [nr], theta [ntheta], phi [nphi]: node coordinates (theta / phi None: the state does not depend on that angle);
+    ne, te: [nr, ntheta, nphi] (a 1-D or 2-D array is taken as [nr] / [nr, ntheta]); velocity: None, three arrays
+    (ur, uth, uph), each of the fields' shape or None (zero), or one array [3, nr, ntheta, nphi].  Numpy arrays make a HOST
+    mesh (mesh_check, mesh_tables, mesh_flow_table); to(device) uploads it once and returns the DEVICE mesh
+    (tabulate_mesh, tabulate_mesh_flow).  The struct keeps its arrays alive.  The library checks the values."""
+    _fields_ = [("center", C.c_double * 3), ("nr", C.c_int), ("ntheta", C.c_int), ("nphi", C.c_int)] + \
+               [(name, C.c_void_p) for name in ("r", "theta", "phi", "ne", "te", "ur", "uth", "uph")]
+
+    def __init__(self, r, theta, phi, ne, te, velocity=None, center=(0.0, 0.0, 0.0)):
+        super().__init__()
+
+        def host(a):
+            return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+        def axis(a, alone):
+            return np.ascontiguousarray([alone] if a is None else host(a), dtype=np.float64).reshape(-1).copy()
+
+        r, theta, phi = axis(r, 0.0), axis(theta, 0.5 * np.pi), axis(phi, 0.0)
+        shape = (r.size, theta.size, phi.size)
+
+        def field(a, what):
+            a = np.ascontiguousarray(host(a), dtype=np.float64)
+            if a.ndim < 3 and a.shape == shape[:a.ndim] and a.size == int(np.prod(shape)):
+                a = a.reshape(shape)
+            if a.shape != shape:
+                raise ValueError("mesh: %s has shape %s, the coordinates say %s" % (what, a.shape, shape))
+            return a.copy()
+
+        if velocity is None:
+            velocity = (None, None, None)
+        if len(velocity) != 3:
+            raise ValueError("mesh: velocity is (ur, uth, uph)")
+        u = [None if c is None else field(c, name) for c, name in zip(velocity, ("ur", "uth", "uph"))]
+        self._set(center, shape, [r, theta, phi, field(ne, "ne"), field(te, "te")] + u)
+
+    def _set(self, center, shape, arrays):
+        self.center = (C.c_double * 3)(*[float(v) for v in center])
+        self.nr, self.ntheta, self.nphi = shape
+        self._keep = arrays
+        for name, a in zip(("r", "theta", "phi", "ne", "te", "ur", "uth", "uph"), arrays):
+            setattr(self, name, _addr(a))
+
+    @property
+    def shape(self):
+        return (self.nr, self.ntheta, self.nphi)
+
+    @property
+    def has_velocity(self):
+        return any(a is not None for a in self._keep[5:])
+
+    def to(self, device):
+        """The same mesh with its arrays on `device` (a torch device), uploaded once."""
+        import torch
+        m = Mesh.__new__(Mesh)
+        C.Structure.__init__(m)
+        m._set(self.center, self.shape, [None if a is None else torch.as_tensor(a).to(device) for a in self._keep])
+        return m
+
+
 # Every symbol include/cbet_mi355x.h declares; tests check the library exports all of them.
 EXPORTS = [
     "cbet_last_error", "cbet_version", "cbet_params_default", "cbet_derive",
@@ -192,6 +257,7 @@ EXPORTS = [
     "cbet_sph_modes_device", "cbet_sph_modes", "cbet_prepare_plasma", "cbet_context_step_records",
     "cbet_tabulate_target", "cbet_target_tables",
     "cbet_tabulate_flow", "cbet_context_set_flow", "cbet_context_flow", "cbet_flow_table",
+    "cbet_tabulate_mesh", "cbet_tabulate_mesh_flow", "cbet_mesh_check", "cbet_mesh_tables", "cbet_mesh_flow_table",
 ]
 
 _lib = None
@@ -283,6 +349,11 @@ def lib():
     L.cbet_context_set_flow.argtypes = [vp, vp]
     L.cbet_context_flow.argtypes = [vp, C.POINTER(vp)]
     L.cbet_flow_table.argtypes = [C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Target), dp]
+    L.cbet_tabulate_mesh.argtypes = [vp, C.POINTER(Params), C.POINTER(Mesh), vp]
+    L.cbet_tabulate_mesh_flow.argtypes = [vp, C.POINTER(Params), C.POINTER(Mesh), vp]
+    L.cbet_mesh_check.argtypes = [C.POINTER(Mesh)]
+    L.cbet_mesh_tables.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp, dp]
+    L.cbet_mesh_flow_table.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -535,6 +606,38 @@ def flow_table(params, gain_params, target=None):
     out = np.empty((3, params.nx, params.ny, params.nz))
     _check(lib().cbet_flow_table(C.byref(params), C.byref(gain_params), None if target is None else C.byref(target),
                                  _dptr(out)))
+    return out
+
+
+def tabulate_mesh(ctx, params, mesh, stream=None):
+    """cbet_tabulate_mesh: the context's node tables from a DEVICE mesh (api.Mesh(...).to(device))."""
+    _check(lib().cbet_tabulate_mesh(ctx.handle, C.byref(params), C.byref(mesh), _addr(stream)))
+
+
+def tabulate_mesh_flow(ctx, params, mesh, stream=None):
+    """cbet_tabulate_mesh_flow: a DEVICE mesh's velocity into the context's own flow table, which the context's gain
+    updates then read.  The first call on a context allocates."""
+    _check(lib().cbet_tabulate_mesh_flow(ctx.handle, C.byref(params), C.byref(mesh), _addr(stream)))
+    ctx._flow_ref = None
+
+
+def mesh_check(mesh):
+    """cbet_mesh_check: the host twins' validation of a HOST mesh alone (raises CbetError naming the first offence)."""
+    _check(lib().cbet_mesh_check(C.byref(mesh)))
+
+
+def mesh_tables(params, mesh):
+    """cbet_mesh_tables, the host twin: numpy (ne3d, kappa3d), each (nx, ny, nz), from a HOST mesh."""
+    shape = (params.nx, params.ny, params.nz)
+    ne3d, kap = np.empty(shape), np.empty(shape)
+    _check(lib().cbet_mesh_tables(C.byref(params), C.byref(mesh), _dptr(ne3d), _dptr(kap)))
+    return ne3d, kap
+
+
+def mesh_flow_table(params, mesh):
+    """cbet_mesh_flow_table, the host twin: numpy (3, nx, ny, nz) -- ux, uy, uz at the nodes -- from a HOST mesh."""
+    out = np.empty((3, params.nx, params.ny, params.nz))
+    _check(lib().cbet_mesh_flow_table(C.byref(params), C.byref(mesh), _dptr(out)))
     return out
 
 

@@ -200,5 +200,23 @@ struct FlowArgs {
 hipError_t flow_upload_factors();                    // the factor table into cbet_flow.hip's constant memory (synchronous)
 hipError_t launch_tabulate_flow(const FlowArgs &a, int inst, hipStream_t stream);
 
+// Plasma on a spherical-polar mesh (cbet_mesh.hip, cbet_mesh_host.cpp, cbet_mesh_model.h).
+// The kernels stage r, theta and phi in LDS; CBET_MESH_MAX_COORDS doubles (20 KiB) let eight 256-thread workgroups share
+// a CU's 160 KiB, which is the 32 waves a CU holds at most: the staging never costs occupancy.
+struct MeshArgs {
+    int nx, ny, nz;
+    double xmin, ymin, zmin, dx, dy, dz, dt;
+    double ncrit;
+    double ox, oy, oz;                      // the mesh's centre
+    int nr, nth, nph;
+    const double *r, *theta, *phi;          // nr, nth, nph node coordinates
+    const double *ne, *te;                  // [nr][nth][nph], phi fastest
+    const double *ur, *uth, *uph;           // the same shape, each may be NULL (zero)
+    double *ne3d, *kap3d;                   // out of the table kernel, nx*ny*nz each
+    double *flow;                           // out of the flow kernel, [3][nx*ny*nz]: ux, uy, uz
+};
+hipError_t launch_tabulate_mesh(const MeshArgs &a, hipStream_t stream);   // k_tabulate_mesh: a.ne3d / a.kap3d
+hipError_t launch_mesh_flow(const MeshArgs &a, hipStream_t stream);       // k_mesh_flow: a.flow
+
 }  // namespace cbet
 #endif

@@ -106,8 +106,14 @@ TabulateArgs tabulate_args(const cbet_params *p, const cbet_derived &d, double *
 // k_tabulate_flow's and its host twin's (cbet_target_host.cpp); target NULL = the sphere about the origin.
 FlowArgs flow_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs,
                    const cbet_target *target, double *out);
+// k_tabulate_mesh's, k_mesh_flow's and their host twins' (cbet_mesh_host.cpp): the outputs a launch does not write stay NULL.
+MeshArgs mesh_args(const cbet_params *p, const cbet_derived &d, const cbet_mesh *mesh, double *ne3d, double *kap3d,
+                   double *flow);
+// The mesh's sizes and NULL pointers (all a device entry can check); whole: the values too (HOST arrays).
+int mesh_check(const cbet_mesh *mesh, bool whole);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
+int flow_own_table(cbet_context *ctx, const cbet_params *p);   // cbet_tabulate_flow's and cbet_tabulate_mesh_flow's first call
 int step_records(cbet_context *ctx, const cbet_params *p, const double *ne3d, const double *kappa3d, double xconst,
                  double yconst, double zconst, void *stream, bool force);
 // CBET hooks of a trace launch (all zero: the reference path).

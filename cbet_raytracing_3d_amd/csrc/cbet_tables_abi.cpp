@@ -48,6 +48,19 @@ int cbet::step_records(cbet_context *ctx, const cbet_params *p, const double *ne
     return CBET_OK;
 }
 
+// The context's own flow table, allocated by the first call on a context (not capturable).  The context's device is current.
+int cbet::flow_own_table(cbet_context *ctx, const cbet_params *p)
+{
+    if (ctx->flow_own) return CBET_OK;
+    const size_t nodes = (size_t)p->nx * p->ny * p->nz;
+    hipError_t e = hipMalloc((void **)&ctx->flow_own, 3 * nodes * sizeof(double));
+    if (e != hipSuccess) {
+        ctx->flow_own = nullptr;
+        return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(flow table): %s", hipGetErrorString(e));
+    }
+    return CBET_OK;
+}
+
 extern "C" {
 
 int cbet_tabulate_plasma(cbet_context *ctx, const cbet_params *p, const double *te_data_g,
@@ -122,14 +135,7 @@ int cbet_tabulate_flow(cbet_context *ctx, const cbet_params *p, const cbet_gain_
     double cs = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, nullptr)) return rc;
     CBET_ENTER_DEVICE(ctx);
-    const size_t nodes = (size_t)p->nx * p->ny * p->nz;
-    if (!ctx->flow_own) {   // the first call on this context: allocates (not capturable)
-        hipError_t e = hipMalloc((void **)&ctx->flow_own, 3 * nodes * sizeof(double));
-        if (e != hipSuccess) {
-            ctx->flow_own = nullptr;
-            return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(flow table): %s", hipGetErrorString(e));
-        }
-    }
+    if (int rc = flow_own_table(ctx, p)) return rc;
     CBET_HIP(launch_tabulate_flow(flow_args(p, ctx->d, g, cs, target, ctx->flow_own), inst, (hipStream_t)stream));
     ctx->flow = ctx->flow_own;
     return CBET_OK;

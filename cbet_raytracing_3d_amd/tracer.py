@@ -65,7 +65,8 @@ class RayTracer:
         self.ctx = api.Context(self.params, self.gpu)
         self._launch_list = None        # set_launch_list(): the regrouped list (ray_ids())
         self.target = None              # set_target(): api.Target, or None = the spherical target about the origin
-        self.flow = None                # set_flow(): None, "target" or the caller's [3, nx, ny, nz] table
+        self.mesh = None                # set_plasma_mesh(): the DEVICE api.Mesh the tables come from, or None = the profiles
+        self.flow = None                # set_flow(): None, "target", "mesh" or the caller's [3, nx, ny, nz] table
         self._flow_gp = None            # the gain parameters a "target" flow is tabulated from
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
@@ -91,13 +92,52 @@ class RayTracer:
 
     def _prepare_plasma(self, params, ctx):
         """Node tables and step records of `ctx` from the radial profiles, one kernel (cbet_prepare_plasma), on torch's
-        current stream.  With a target set: cbet_tabulate_target, then the records of those tables."""
-        if self.target is not None:
-            api.tabulate_target(ctx, params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
+        current stream.  With a target or a mesh set: cbet_tabulate_target / cbet_tabulate_mesh, then the records of those
+        tables."""
+        if self._tabulate_other(ctx, params):
             api.prepare_step_records(ctx, params, None, None, *self._grad_consts(), self._stream())
         else:
             api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
         self._tabulate_flow(ctx, params)
+
+    def _tabulate_other(self, ctx, params):
+        """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False
+        and nothing done otherwise (the caller then takes the path of the radial profiles)."""
+        if self.mesh is not None:
+            api.tabulate_mesh(ctx, params, self.mesh, self._stream())
+        elif self.target is not None:
+            api.tabulate_target(ctx, params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
+        else:
+            return False
+        return True
+
+    # ---- hydro-mesh plasma (include/cbet_mi355x.h cbet_tabulate_mesh; DESIGN.md section 14) -------------------------
+    def set_plasma_mesh(self, r, theta=None, phi=None, ne=None, te=None, velocity=None, center=(0.0, 0.0, 0.0)):
+        """Take the plasma from a hydrodynamics state on a spherical-polar mesh about `center` (cm) instead of the radial
+        profiles: r [nr], theta [ntheta], phi [nphi] node coordinates (None: no dependence on that angle), ne (cm^-3) and
+        te (the profiles' units) [nr, ntheta, nphi], velocity None or (ur, uth, uph) in cm/s (api.Mesh: numpy arrays or
+        tensors).  The mesh is validated on the host by the host twins' rules (api.mesh_check) and uploaded once;
+        tabulate(), launch(), trace_exits() and the pipeline's passes then fill the context's node tables with
+        cbet_tabulate_mesh and trace those.  set_plasma_mesh(None) goes back to the profiles.  A mesh and a target exclude
+        each other.  The CBET stage refuses a mesh while no flow is set, as it refuses a target: set_flow("mesh") gives it
+        the mesh's own velocity."""
+        if r is None:
+            self.mesh = None
+            if self._flow_is("mesh"):
+                self.set_flow(None)
+            return
+        if self.target is not None:
+            raise ValueError("set_plasma_mesh: a target is set (set_target(None) first): a mesh and a target exclude each other")
+        if ne is None or te is None:
+            raise ValueError("set_plasma_mesh: ne and te are required")
+        host = api.Mesh(r, theta, phi, ne, te, velocity, center)
+        try:
+            api.mesh_check(host)
+        except api.CbetError as e:
+            raise ValueError(str(e)) from None
+        if self._flow_is("mesh") and not host.has_velocity:
+            raise ValueError('set_plasma_mesh: set_flow("mesh") is in force and this mesh has no velocity')
+        self.mesh = host.to(self.device)
 
     # ---- perturbed targets (include/cbet_mi355x.h cbet_tabulate_target; DESIGN.md section 12) ------------------------
     def set_target(self, offset=(0.0, 0.0, 0.0), coeffs=None, lmax=None):
@@ -107,6 +147,8 @@ class RayTracer:
         goes back to the spherical target and to the calls made without one.  The CBET stage -- launch_cbet, gain_field,
         cbet_solve -- refuses a target while no flow is set: its closed-form flow is centred on the origin.  With
         set_flow("target"), or a flow table of the caller's, it runs on the target's tables and that flow."""
+        if offset is not None and self.mesh is not None:
+            raise ValueError("set_target: a plasma mesh is set (set_plasma_mesh(None) first): a mesh and a target exclude each other")
         self.target = None if offset is None else api.Target(offset, coeffs, lmax)
 
     # ---- flow of the CBET stage (include/cbet_mi355x.h cbet_tabulate_flow; DESIGN.md section 13) --------------------
@@ -116,6 +158,8 @@ class RayTracer:
         "target": the ramp's flow on the current target (cbet_tabulate_flow; the sphere about the origin if no target is
         set), tabulated whenever the node tables are -- tabulate(), the pipeline's preparation, cbet_solve's start -- from
         the ramp of `gain_params` (default api.default_gain_params(); cbet_solve puts its own in their place).
+        "mesh": the velocity of the current plasma mesh (set_plasma_mesh; cbet_tabulate_mesh_flow), tabulated at the same
+        moments; an error without a mesh or if the mesh has no velocity.
         A float64 tensor [3, nx, ny, nz] on this device: the caller's own flow field (ux, uy, uz at the nodes, cm/s), kept
         referenced here and read as it is at every gain update.
         With a flow set launch_cbet, gain_field and cbet_solve (slabs=True too) run on a target."""
@@ -124,8 +168,14 @@ class RayTracer:
             self.ctx.set_flow(None)
             return
         if isinstance(mode, str):
+            if mode == "mesh":
+                if self.mesh is None or not self.mesh.has_velocity:
+                    raise ValueError('set_flow("mesh"): no plasma mesh is set, or it has no velocity (set_plasma_mesh)')
+                self.ctx.set_flow(None)                 # until the next tabulate() fills and selects the context's table
+                self.flow, self._flow_gp = "mesh", None
+                return
             if mode != "target":
-                raise ValueError('set_flow: None, "target" or a [3, nx, ny, nz] tensor, got %r' % (mode,))
+                raise ValueError('set_flow: None, "target", "mesh" or a [3, nx, ny, nz] tensor, got %r' % (mode,))
             self.ctx.set_flow(None)                     # until the next tabulate() fills and selects the context's table
             self.flow = "target"
             self._flow_gp = self._copy_gp(api.default_gain_params() if gain_params is None else gain_params)
@@ -136,22 +186,27 @@ class RayTracer:
         self.flow, self._flow_gp = mode, None
         self.ctx.set_flow(mode)
 
+    def _flow_is(self, mode):
+        return isinstance(self.flow, str) and self.flow == mode
+
     @staticmethod
     def _copy_gp(gain_params):
         return type(gain_params).from_buffer_copy(gain_params)
 
     def _tabulate_flow(self, ctx=None, params=None):
-        """A "target" flow into `ctx` (default: this tracer's context) on torch's current stream; nothing otherwise."""
-        if isinstance(self.flow, str):
-            api.tabulate_flow(self.ctx if ctx is None else ctx, self.params if params is None else params, self._flow_gp,
-                              self.target, self._stream())
+        """A "target" or "mesh" flow into `ctx` (default: this tracer's context) on torch's current stream; nothing otherwise."""
+        ctx, params = self.ctx if ctx is None else ctx, self.params if params is None else params
+        if self._flow_is("mesh"):
+            api.tabulate_mesh_flow(ctx, params, self.mesh, self._stream())
+        elif isinstance(self.flow, str):
+            api.tabulate_flow(ctx, params, self._flow_gp, self.target, self._stream())
 
     def _no_target(self, what):
         if self.flow is not None:
             return
-        if self.target is not None:
-            raise ValueError("%s models the flow of a spherical target about the origin: clear the target first "
-                             "(set_target(None))" % what)
+        if self.target is not None or self.mesh is not None:
+            raise ValueError("%s models the flow of a spherical target about the origin: clear the target or the mesh first "
+                             "(set_target(None), set_plasma_mesh(None)), or set a flow (set_flow)" % what)
 
     def _prepare_step_records(self):
         """The step records of the context's own tables, now and on torch's current stream (cbet_prepare_step_records)."""
@@ -188,8 +243,7 @@ class RayTracer:
             p.force_wide_index = force_wide_index
         if stats is not None:
             p.window_stats = 1 if stats else 0
-        if self.target is not None:     # the halves of the launch: the target's tables, then a trace of the context's tables
-            api.tabulate_target(self.ctx, p, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
+        if self._tabulate_other(self.ctx, p):   # the halves of the launch: the target's or the mesh's tables, then a trace of them
             api.trace_nodes(0, self.derived.nindices, None, None, edep, *self._tail(use_host_trig), p, self.ctx, self._stream())
             return edep
         api.launch_ray_XYZ(0, self.derived.nindices, self.d_te, self.d_r, self.d_ne, edep, *self._tail(use_host_trig), p,
@@ -201,10 +255,9 @@ class RayTracer:
 
     # ---- CBET stage (parity unpinned, see include/cbet_mi355x.h) --------------
     def tabulate(self):
-        """Fill the context's node tables from the radial profiles (what launch() does first); on the target, if one is set."""
-        if self.target is not None:
-            api.tabulate_target(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self.target, self._stream())
-        else:
+        """Fill the context's node tables from the radial profiles (what launch() does first); on the target or from the
+        mesh, if one is set."""
+        if not self._tabulate_other(self.ctx, self.params):
             api.tabulate_plasma(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self._stream())
         self._tabulate_flow()
 
@@ -252,14 +305,15 @@ class RayTracer:
         x_lo, x_hi: only the planes [x_lo, x_hi) of the deposit grid (one rank's slab).
         frozen: fields[1:4] already hold k from an earlier call; only fields[0] is read and normalised.
         With a flow set (set_flow) the update reads it; a "target" flow is the one the last tabulate() wrote, from the
-        ramp of set_flow's gain parameters -- `gain_params` must carry the same ramp."""
+        ramp of set_flow's gain parameters -- `gain_params` must carry the same ramp; a "mesh" flow is the mesh's velocity
+        as the last tabulate() wrote it."""
         if isinstance(self.flow, str):
             ramp = lambda g: (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)  # noqa: E731
-            if ramp(gain_params) != ramp(self._flow_gp):
+            if self._flow_is("target") and ramp(gain_params) != ramp(self._flow_gp):
                 raise ValueError("gain_field: the flow table was tabulated from another Mach ramp or sound speed than "
                                  "gain_params carries (set_flow(\"target\", gain_params), then tabulate())")
             if self.ctx.flow() is None:
-                raise ValueError("gain_field: set_flow(\"target\") needs tabulate() before the first gain update")
+                raise ValueError("gain_field: set_flow(\"%s\") needs tabulate() before the first gain update" % self.flow)
         if pair_once is None:
             pair_once = scratch is not None
         scratch = gain if pair_once else None
@@ -274,7 +328,7 @@ class RayTracer:
         `edep` (not reduced here: use allreduce_grid).  Single-rank callers can use the native loop instead:
         api.cbet_solve."""
         self._no_target("cbet_solve")
-        if isinstance(self.flow, str):
+        if self._flow_is("target"):
             self._flow_gp = self._copy_gp(gain_params)      # the engine's tabulate() fills the flow table from this ramp
         engine = _DeviceCbetEngine(self, edep, gain_params, fields, gain)
         engine.force_collectives = force_collectives

@@ -539,6 +539,71 @@ int cbet_tabulate_flow(cbet_context *ctx, const cbet_params *p, const cbet_gain_
 int cbet_context_set_flow(cbet_context *ctx, const double *flow);
 int cbet_context_flow(cbet_context *ctx, void **out);
 int cbet_flow_table(const cbet_params *p, const cbet_gain_params *g, const cbet_target *target, double *out);
+
+/* ---- hydro-mesh plasma: node tables and flow from a spherical-polar state -- */
+/*
+ * The producer of node tables and of the flow table for a plasma that is the state of a hydrodynamics run rather than
+ * one radial profile: ne, Te and the fluid velocity on a spherical-polar mesh (r, theta, phi) about a centre o, 1-D, 2-D
+ * axisymmetric or 3-D.
+ *
+ * Mesh.  Node coordinates r[nr] strictly ascending, r[0] >= 0, nr >= 2; theta[ntheta] strictly ascending in [0, pi],
+ * ntheta >= 1; phi[nphi] strictly ascending, -pi <= phi[0] < pi, phi[nphi-1] < phi[0] + 2 pi, nphi >= 1;
+ * nr + ntheta + nphi <= CBET_MESH_MAX_COORDS.  Fields [nr][ntheta][nphi], phi fastest: ne (cm^-3, >= 0), te (the
+ * profile's units, > 0) and optionally ur, uth, uph (cm/s; a NULL component is zero).  ntheta == 1 or nphi == 1: the
+ * state does not depend on that angle (its one coordinate value is not used).
+ *
+ * Model, for node (i, j, k); every statement ONE IEEE fp64 operation per written operator, in the written order, no fused
+ * multiply-add; TWO_PI is the literal 6.283185307179586:
+ *     xc = i*dx + xmin (y, z alike);  sx = xc - ox,  sy = yc - oy,  sz = zc - oz       (cbet_tabulate_target's statements)
+ *     rho = sqrt(sx*sx + sy*sy + sz*sz);   rxy = sqrt(sx*sx + sy*sy)
+ *     theta = atan2(rxy, sz)                                                     (skipped when ntheta == 1)
+ *     phi   = atan2(sy, sx);  if (phi < phi[0]) phi = phi + TWO_PI               (skipped when nphi == 1)
+ * theta bracket: clamped like the profile lookup of cbet_tabulate_plasma -- at or below theta[0] the first row alone, at
+ * or above the last the last row alone, else the bisection's j with wt = (theta - theta[j]) / (theta[j+1] - theta[j]).
+ * phi bracket, periodic: k = the last index with phi[k] <= phi; for k < nphi - 1 the upper node is k + 1 and
+ * wp = (phi - phi[k]) / (phi[k+1] - phi[k]); for k = nphi - 1 the upper node is 0 and
+ * wp = (phi - phi[k]) / ((phi[0] + TWO_PI) - phi[k]); wp is clamped to [0, 1] (wp < 0 -> 0, then wp > 1 -> 1).
+ * r bracket: cbet_tabulate_plasma's tests and bisection on rho: one clamped shell, or the pair m, m + 1.
+ * A field f, the angles first on each shell that is used, the radius last:
+ *     a0 = f[s][j][k] + (f[s][j][k'] - f[s][j][k]) * wp,   a1 = the same on row j'
+ *     v(s) = a0 + (a1 - a0) * wt                                                 (a clamped theta: v(s) = a0)
+ *     f = v(m) + (v(m+1) - v(m)) / (r[m+1] - r[m]) * (rho - r[m])                (a clamped rho: f = v(0) or v(nr-1))
+ * For a field that does not depend on the angles v(s) is f[s] exactly, the last statement is cbet_tabulate_plasma's, and
+ * the tables equal cbet_tabulate_plasma's (centre 0) / cbet_tabulate_target's (offset = centre, no coefficients) bit for bit.
+ * kappa from the interpolated ne and Te: cbet_tabulate_plasma's three statements (launch_ray_XZ.cu:299-305).
+ * Velocity: ct = sz/rho, st = rxy/rho, (c1, s1) = (sx/rxy, sy/rxy), (1, 0) where rxy == 0; with the interpolated components
+ *     h = ur*st + uth*ct;   ux = h*c1 - uph*s1;   uy = h*s1 + uph*c1;   uz = ur*ct - uth*st;     u = 0 where rho == 0
+ * Degenerate nodes: atan2(0, 0) is 0 (host and device), so a node at the centre reads the brackets of theta = 0 and
+ * phi = 0 on the innermost shell, and a node on the polar axis those of phi = 0 (with theta = 0 or pi).
+ * The device and the host evaluate atan2 with different functions: a node that lies on a bracket's edge may be put into
+ * the neighbouring bracket by one of them.  The interpolant is continuous there, so the two sides agree to rounding (the
+ * project's bound for two formulations of one quantity, 1e-12 relative), and bit for bit for angle-independent fields.
+ * Every index the searches produce lies inside its array whatever the coordinates hold: the device entries, which cannot
+ * read a device mesh, check sizes and NULL pointers only, and a bad mesh gives wrong numbers, never a read out of range.
+ *
+ * cbet_tabulate_mesh: DEVICE mesh arrays -> the context's ne3d / kappa3d; behaves towards the context exactly like
+ * cbet_tabulate_target (geometry check, enqueued on `stream`, no allocation, no synchronisation, step records stale).
+ * cbet_tabulate_mesh_flow: DEVICE mesh arrays -> the context's OWN flow table, which it selects; behaves exactly like
+ * cbet_tabulate_flow (the first call on a context allocates; later calls only enqueue).
+ * The struct is captured at the call; the arrays it points to are read when the kernel runs.
+ * cbet_mesh_tables / cbet_mesh_flow_table: the host twins, plain loops in node order over HOST mesh arrays into HOST
+ * ne3d / kappa3d (nx ny nz doubles each) / flow (3 nx ny nz doubles).  They validate the WHOLE mesh first -- cbet_mesh_check:
+ * the rules under "Mesh" above and finite values everywhere -- and return CBET_EINVAL naming the first offence.
+ */
+#define CBET_MESH_MAX_COORDS 2560
+typedef struct cbet_mesh {
+    double center[3];                       /* o (cm)                                                             */
+    int nr, ntheta, nphi;
+    const double *r, *theta, *phi;          /* node coordinates                                                   */
+    const double *ne, *te;                  /* [nr][ntheta][nphi]                                                 */
+    const double *ur, *uth, *uph;           /* the same shape; each may be NULL = zero                            */
+} cbet_mesh;
+int cbet_tabulate_mesh(cbet_context *ctx, const cbet_params *p, const cbet_mesh *mesh /* device pointers */, void *stream);
+int cbet_tabulate_mesh_flow(cbet_context *ctx, const cbet_params *p, const cbet_mesh *mesh /* device pointers */,
+                            void *stream);
+int cbet_mesh_check(const cbet_mesh *mesh /* host pointers */);
+int cbet_mesh_tables(const cbet_params *p, const cbet_mesh *mesh /* host pointers */, double *ne3d, double *kappa3d);
+int cbet_mesh_flow_table(const cbet_params *p, const cbet_mesh *mesh /* host pointers */, double *flow);
 /*
  * The sparse exchange of the slab-owned CBET loop (tracer._Exchanger).  A segment is a 64-byte run of 8 doubles aligned
  * to 8 along z; `segments` is a DEVICE array of nseg {row of the array (beam), index of the run inside one beam's
