@@ -191,9 +191,9 @@ int cbet_context_create(cbet_context **out, const cbet_params *p, int gpu)
         (e = hipMemcpy(ctx->live, live.data(), live.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
         return bail(e, "hipMemcpy(live)");
     if ((e = hipMemset(ctx->counters, 0, kCntSlots * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(counters)");
-    // the recurrence factors of cbet_tabulate_target into this device's constant memory (the same bytes every time)
+    // the recurrence factors of cbet_tabulate_target and cbet_tabulate_flow into this device's constant memory (the same
+    // bytes every time)
     if ((e = target_upload_factors()) != hipSuccess) return bail(e, "hipMemcpyToSymbol(target factors)");
-    if ((e = flow_upload_factors()) != hipSuccess) return bail(e, "hipMemcpyToSymbol(flow factors)");
     *out = ctx;
     return CBET_OK;
 }

@@ -167,8 +167,8 @@ struct SphArgs {
 hipError_t launch_sph_modes(const SphArgs &a, hipStream_t stream);
 
 // Perturbed targets (cbet_target.hip, cbet_target_host.cpp, cbet_target_model.h).
-// The factor table F of the header's contract, computed once on the host (target_factors) and read by the kernel (from
-// constant memory, target_upload_factors) and by the host twin alike:
+// The factor table F of the header's contract, computed once on the host (target_factors) and read by the two kernels (from
+// constant memory, target_upload_factors) and by the host twins alike:
 //   [kTfY00] 1/sqrt(4 pi), [kTfSqrt2] sqrt(2), [kTfD + k] d_k, [kTfA + l * kTargetS + m] a_lm, [kTfB + ...] b_lm
 constexpr int kTargetS = CBET_TARGET_LMAX + 1;
 constexpr int kTargetCoeffs = kTargetS * kTargetS;
@@ -187,7 +187,7 @@ int target_check(const cbet_target *target, int *inst);
 void target_fill(const cbet_target *target, TargetArgs *a);   // offset and coefficients into *a
 hipError_t launch_tabulate_target(const TargetArgs &a, int inst, hipStream_t stream);
 
-// Flow table of the gain kernels on a target (cbet_flow.hip, cbet_target_host.cpp, cbet_target_model.h target_flow;
+// Flow table of the gain kernels on a target (cbet_target.hip, cbet_target_host.cpp, cbet_target_model.h target_flow;
 // DESIGN.md section 13).  Passed by value like TargetArgs; c sits last, as the kernel reads it from the argument segment.
 struct FlowArgs {
     int nx, ny, nz;
@@ -197,7 +197,6 @@ struct FlowArgs {
     double ox, oy, oz;
     double c[kTargetCoeffs];
 };
-hipError_t flow_upload_factors();                    // the factor table into cbet_flow.hip's constant memory (synchronous)
 hipError_t launch_tabulate_flow(const FlowArgs &a, int inst, hipStream_t stream);
 
 // Plasma on a spherical-polar mesh (cbet_mesh.hip, cbet_mesh_host.cpp, cbet_mesh_model.h).

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cbet_device.h"
+#include "cbet_node_model.h"
 
 namespace cbet {
 namespace {
@@ -20,7 +21,7 @@ struct CellState {
     double frac, eps, rt, ux, uy, uz;   // ne/ncrit, 1 - ne/ncrit, sqrt(eps), flow velocity
 };
 
-// FLOW: the flow velocity is read from GainArgs.flow (a node table, cbet_flow.hip) instead of the closed-form radial
+// FLOW: the flow velocity is read from GainArgs.flow (a node table, cbet_target.hip k_tabulate_flow) instead of the closed-form radial
 // ramp about the origin.
 template <bool FLOW>
 __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
@@ -44,14 +45,9 @@ __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
         c.uz = a.flow[node + 2 * nodes];
         return c;
     }
-    const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
-    const double rr = sqrt(xc * xc + yc * yc + zc * zc);
-    double t = (rr - a.mach_r0) / (a.mach_r1 - a.mach_r0);
-    if (t < 0.0) t = 0.0;
-    if (t > 1.0) t = 1.0;
-    const double um = (a.mach_0 + (a.mach_1 - a.mach_0) * t) * a.cs;
-    c.ux = c.uy = c.uz = 0.0;
-    if (rr > 0.0) { c.ux = um * (xc / rr); c.uy = um * (yc / rr); c.uz = um * (zc / rr); }
+    double xc, yc, zc, rr;                                            // the sphere about the origin: no offset, rho' == rho
+    node_centre(a, i, j, k, 0.0, 0.0, 0.0, xc, yc, zc, rr);
+    radial_flow(a, rr, rr, xc, yc, zc, c.ux, c.uy, c.uz);
     return c;
 }
 

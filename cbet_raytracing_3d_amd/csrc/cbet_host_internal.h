@@ -100,6 +100,14 @@ void grid_args(Args &a, const cbet_params *p, const cbet_derived &d)
     a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
     a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
 }
+// The host twins' walk over the nodes, in node order: body(i, j, k, idx) with idx = (i * ny + j) * nz + k.
+template <class Body>
+void for_each_node_host(int nx, int ny, int nz, Body body)
+{
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < ny; ++j)
+            for (int k = 0; k < nz; ++k) body(i, j, k, ((long)i * ny + j) * nz + k);
+}
 // k_tabulate's and its host twin's (cbet_tables_abi.cpp); the twin passes the profiles beside the block.
 TabulateArgs tabulate_args(const cbet_params *p, const cbet_derived &d, double *ne3d, double *kap3d, const double *te,
                            const double *r, const double *ne);

@@ -23,44 +23,23 @@
 //     Both exist to cross-check the shipped kernel (tests/) and to price its deposit scheme.
 #include <hip/hip_runtime.h>
 
+#include "cbet_node_kernel.h"
+#include "cbet_node_model.h"
 #include "cbet_trace_common.h"
 
 namespace cbet {
 namespace {
 
-// Two tables over ONE abscissa (ne and Te share r_data, launch_ray_XZ.cu:297-298): the bisection
-// depends only on (x, xp), so it is done once and both values are interpolated from the same
-// segment -- bit for bit what two interp_table() calls return.
-__device__ __forceinline__ void interp_table2(const double *y1, const double *y2, const double *x, const double xp,
-                                              int n, double &o1, double &o2)
-{
-    const bool ascending = x[0] <= x[n - 1];
-    if (ascending ? (xp <= x[0]) : (xp >= x[0])) { o1 = y1[0]; o2 = y2[0]; return; }
-    if (ascending ? (xp >= x[n - 1]) : (xp <= x[n - 1])) { o1 = y1[n - 1]; o2 = y2[n - 1]; return; }
-    unsigned lo = 0, hi = n - 1, mid = (lo + hi) >> 1;
-    while (lo < hi - 1) {
-        const bool go_low = ascending ? (x[mid] >= xp) : !(x[mid] <= xp);  // :31 / :52 (as written there)
-        if (go_low) hi = mid; else lo = mid;
-        mid = (lo + hi) >> 1;
-    }
-    const double dx = x[mid + 1] - x[mid], t = xp - x[mid];
-    o1 = y1[mid] + (y1[mid + 1] - y1[mid]) / dx * t;
-    o2 = y2[mid] + (y2[mid + 1] - y2[mid]) / dx * t;
-}
-
 // One node's table entries, launch_ray_XZ.cu:296-305: ed = ne at the node's radius, kap = ed/ncrit*nuei*dt (the absorbed
-// fraction up to the trailing "* uray").  Every statement is the reference's, in its order; both table kernels use it.
+// fraction up to the trailing "* uray").  Every statement is the reference's, in its order (cbet_node_model.h); both table
+// kernels use it.
 __device__ __forceinline__ void node_plasma(const TabulateArgs &a, const double *s_r, const double *s_ne, const double *s_te,
                                             int i, int j, int k, double &ed, double &kap)
 {
-    // launch_ray_XZ.cu:296 -- node radius, squares summed x,y,z
-    const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
-    const double rho = sqrt(xc * xc + yc * yc + zc * zc);
-    double etemp;                                                   // :297-298
-    interp_table2(s_ne, s_te, s_r, rho, a.nprofile, ed, etemp);
-    const double eta = 5.2e-5 * 10.0 / (etemp * sqrt(etemp));       // :299
-    const double nuei = (1e6 * ed * (kEc * kEc) / kMe) * eta;       // :300
-    kap = ed / a.ncrit * nuei * a.dt;                               // :305 up to "* uray"
+    double sx, sy, sz, rho, etemp;
+    node_centre(a, i, j, k, 0.0, 0.0, 0.0, sx, sy, sz, rho);       // :296
+    interp2(s_ne, s_te, s_r, rho, a.nprofile, ed, etemp);           // :297-298
+    kap = kappa(ed, etemp, a.ncrit, a.dt);                          // :299-305
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -388,7 +367,7 @@ __global__ void __launch_bounds__(kWave) k_trace_simple(const TraceArgs a)
             const int jp = (s.cj == 0) ? 2 : ((s.cj == ny - 1) ? ny - 1 : s.cj + 1);
             const int km = (s.ck == 0) ? 0 : ((s.ck == nz - 1) ? nz - 3 : s.ck - 1);
             const int kp = (s.ck == 0) ? 2 : ((s.ck == nz - 1) ? nz - 1 : s.ck + 1);
-            auto ne_at = [&](int i, int j, int k) { return node_load<true>(a, a.ne3d, (unsigned)(i * sX + j * sY + k)); };
+            auto ne_at = [&](int i, int j, int k) { return node_load<true>(a, a.ne3d, (unsigned)(i * sX + j * sY + k), a.audit_nodes); };
             // :254-273 six gathers, kick, drift
             s.vx -= a.xconst * (ne_at(ip, s.cj, s.ck) - ne_at(im, s.cj, s.ck));
             s.vy -= a.yconst * (ne_at(s.ci, jp, s.ck) - ne_at(s.ci, jm, s.ck));
@@ -406,7 +385,7 @@ __global__ void __launch_bounds__(kWave) k_trace_simple(const TraceArgs a)
             // :296-311 absorbed energy
             double inc;
             if (absorb) {
-                inc = node_load<true>(a, a.kap3d, (unsigned)(s.ci * sX + s.cj * sY + s.ck)) * s.uray;
+                inc = node_load<true>(a, a.kap3d, (unsigned)(s.ci * sX + s.cj * sY + s.ck), a.audit_nodes) * s.uray;
                 s.uray -= inc;
             } else {
                 inc = s.uray;
@@ -466,20 +445,14 @@ __device__ unsigned long long g_audit_violations;
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream)
 {
-    const long total = (long)a.nx * a.ny * a.nz;
-    long blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;  // 256 CUs x 16 blocks, grid-stride the rest
     const size_t lds = sizeof(double) * 3 * (size_t)a.nprofile;
-    hipLaunchKernelGGL(k_tabulate, dim3((unsigned)blocks), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(k_tabulate, dim3(node_blocks((long)a.nx * a.ny * a.nz)), dim3(256), lds, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_step_table(const StepTableArgs &a, hipStream_t stream)
 {
-    const long total = (long)a.nx * a.ny * a.nz;
-    long blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(k_step_table, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_step_table, dim3(node_blocks((long)a.nx * a.ny * a.nz)), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -7,7 +7,7 @@
 // shared with the host twins), then
 //   * k_tabulate_mesh = k_mesh<false>: interpolates ne and Te and writes the context's ne3d / kap3d;
 //   * k_mesh_flow     = k_mesh<true>:  interpolates (ur, utheta, uphi), turns them into (ux, uy, uz) and writes the
-//     component-major flow table the gain kernels read (cbet_flow.hip's layout).
+//     component-major flow table the gain kernels read (k_tabulate_flow's layout).
 // One walk serves both, so they are one template.  The mesh's fields are read by plain vector gathers, up to eight per
 // field and node (two shells x two rows x two columns; fewer where a bracket clamps).  phi does not depend on z, so the
 // nodes of one z-row -- a wave's lanes -- share their phi bracket and walk through the (r, theta) cells: the two columns
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cbet_mesh_model.h"
+#include "cbet_node_kernel.h"
 
 namespace cbet {
 namespace {
@@ -58,11 +59,8 @@ __global__ void __launch_bounds__(256) k_mesh(const MeshArgs a)
 template <bool FLOW>
 hipError_t launch(const MeshArgs &a, hipStream_t stream)
 {
-    const long total = (long)a.nx * a.ny * a.nz;
-    long blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;  // k_tabulate_target's shape: 256 CUs x 16 blocks, grid-stride the rest
     const size_t lds = sizeof(double) * ((size_t)a.nr + a.nth + a.nph);
-    hipLaunchKernelGGL(k_mesh<FLOW>, dim3((unsigned)blocks), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(k_mesh<FLOW>, dim3(node_blocks((long)a.nx * a.ny * a.nz)), dim3(256), lds, stream, a);
     return hipGetLastError();
 }
 

@@ -86,15 +86,12 @@ template <bool FLOW>
 void host_mesh(const MeshArgs &a)
 {
     const long nodes = (long)a.nx * a.ny * a.nz;
-    for (int i = 0; i < a.nx; ++i)
-        for (int j = 0; j < a.ny; ++j)
-            for (int k = 0; k < a.nz; ++k) {
-                const long idx = ((long)i * a.ny + j) * a.nz + k;
-                MeshNode n;
-                mesh_locate(a, a.r, a.theta, a.phi, i, j, k, n);
-                if (FLOW) mesh_velocity(a, n, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes]);
-                else mesh_tables(a, n, a.ne3d[idx], a.kap3d[idx]);
-            }
+    for_each_node_host(a.nx, a.ny, a.nz, [&](int i, int j, int k, long idx) {
+        MeshNode n;
+        mesh_locate(a, a.r, a.theta, a.phi, i, j, k, n);
+        if (FLOW) mesh_velocity(a, n, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes]);
+        else mesh_tables(a, n, a.ne3d[idx], a.kap3d[idx]);
+    });
 }
 
 }  // namespace

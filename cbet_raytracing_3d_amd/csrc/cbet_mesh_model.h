@@ -16,7 +16,7 @@
 #define CBET_MESH_MODEL_H_
 
 #include "cbet_device.h"
-#include "cbet_target_model.h"
+#include "cbet_node_model.h"
 
 namespace cbet {
 
@@ -32,35 +32,17 @@ struct MeshNode {
     double wp;
 };
 
-// The bracket of target_interp2 (cbet_target_model.h): its two clamp tests and its bisection, unchanged.  n >= 2.
-CBET_HD void mesh_bracket(const double *x, int n, const double xp, int &i0, int &i1)
-{
-    const bool ascending = x[0] <= x[n - 1];
-    if (ascending ? (xp <= x[0]) : (xp >= x[0])) { i0 = i1 = 0; return; }
-    if (ascending ? (xp >= x[n - 1]) : (xp <= x[n - 1])) { i0 = i1 = n - 1; return; }
-    unsigned lo = 0, hi = n - 1, mid = (lo + hi) >> 1;
-    while (lo < hi - 1) {
-        const bool go_low = ascending ? (x[mid] >= xp) : !(x[mid] <= xp);
-        if (go_low) hi = mid; else lo = mid;
-        mid = (lo + hi) >> 1;
-    }
-    i0 = (int)mid;          // lo < hi throughout and hi == lo + 1 here: mid == lo <= n - 2
-    i1 = (int)mid + 1;
-}
-
-// target_node's coordinate statements (cbet_target_model.h:93-95), then the angles and the three brackets.
+// The node's centre and radius about the mesh's centre, then the angles and the three brackets.
 // r / th / ph: the mesh's coordinate arrays (LDS in the kernel).
 CBET_HD void mesh_locate(const MeshArgs &a, const double *r, const double *th, const double *ph, int i, int j, int k,
                          MeshNode &n)
 {
-    const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
-    n.sx = xc - a.ox; n.sy = yc - a.oy; n.sz = zc - a.oz;
-    n.rho = sqrt(n.sx * n.sx + n.sy * n.sy + n.sz * n.sz);
+    node_centre(a, i, j, k, a.ox, a.oy, a.oz, n.sx, n.sy, n.sz, n.rho);
     n.rxy = sqrt(n.sx * n.sx + n.sy * n.sy);
     n.j0 = n.j1 = 0; n.wt = 0.0;
     if (a.nth > 1) {
         const double theta = atan2(n.rxy, n.sz);
-        mesh_bracket(th, a.nth, theta, n.j0, n.j1);
+        bracket(th, a.nth, theta, n.j0, n.j1);
         if (n.j1 != n.j0) n.wt = (theta - th[n.j0]) / (th[n.j1] - th[n.j0]);
     }
     n.k0 = n.k1 = 0; n.wp = 0.0;
@@ -81,7 +63,7 @@ CBET_HD void mesh_locate(const MeshArgs &a, const double *r, const double *th, c
         if (wp > 1.0) wp = 1.0;
         n.wp = wp;
     }
-    mesh_bracket(r, a.nr, n.rho, n.m0, n.m1);
+    bracket(r, a.nr, n.rho, n.m0, n.m1);
     n.dr = r[n.m1] - r[n.m0];
     n.tr = n.rho - r[n.m0];
 }
@@ -99,8 +81,8 @@ CBET_HD double mesh_shell(const MeshArgs &a, const double *f, const MeshNode &n,
     return a0 + (a1 - a0) * n.wt;
 }
 
-// ... and along r last, with target_interp2's own statement: for a field that does not depend on the angles mesh_shell
-// returns f[s] exactly ((b - a) is 0), and the value is, bit for bit, target_interp2's.
+// ... and along r last, with interp2's own statement (cbet_node_model.h): for a field that does not depend on the angles
+// mesh_shell returns f[s] exactly ((b - a) is 0), and the value is, bit for bit, interp2's.
 CBET_HD double mesh_value(const MeshArgs &a, const double *f, const MeshNode &n)
 {
     const double v0 = mesh_shell(a, f, n, n.m0);
@@ -109,14 +91,11 @@ CBET_HD double mesh_value(const MeshArgs &a, const double *f, const MeshNode &n)
     return v0 + (v1 - v0) / n.dr * n.tr;
 }
 
-// The node's table entries: ne and Te of the mesh, then target_node's three statements (cbet_target_model.h:101-103).
+// The node's table entries: ne and Te of the mesh, then the absorbed fraction.
 CBET_HD void mesh_tables(const MeshArgs &a, const MeshNode &n, double &ed, double &kap)
 {
     ed = mesh_value(a, a.ne, n);
-    const double etemp = mesh_value(a, a.te, n);
-    const double eta = 5.2e-5 * 10.0 / (etemp * sqrt(etemp));       // :299
-    const double nuei = (1e6 * ed * (kEc * kEc) / kMe) * eta;       // :300
-    kap = ed / a.ncrit * nuei * a.dt;                               // :305 up to "* uray"
+    kap = kappa(ed, mesh_value(a, a.te, n), a.ncrit, a.dt);
 }
 
 // The node's flow velocity: the mesh's (ur, utheta, uphi), a NULL component zero, turned into Cartesian components with

@@ -6,11 +6,7 @@
 
 #include <math.h>
 
-#if defined(__HIPCC__)
-#define CBET_HD __host__ __device__ __forceinline__
-#else
-#define CBET_HD static inline
-#endif
+#include "cbet_hd.h"
 
 namespace cbet {
 

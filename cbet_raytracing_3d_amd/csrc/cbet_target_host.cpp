@@ -81,12 +81,9 @@ void host_tables(const TargetArgs &a, const double *r, const double *ne, const d
 {
     const TabulateArgs &t = a.t;
     const double *F = target_factors();
-    for (int i = 0; i < t.nx; ++i)
-        for (int j = 0; j < t.ny; ++j)
-            for (int k = 0; k < t.nz; ++k) {
-                const long idx = ((long)i * t.ny + j) * t.nz + k;
-                target_node<L>(a, F, a.c, r, ne, te, i, j, k, t.ne3d[idx], t.kap3d[idx], TargetNoPin());
-            }
+    for_each_node_host(t.nx, t.ny, t.nz, [&](int i, int j, int k, long idx) {
+        target_node<L>(a, F, a.c, r, ne, te, i, j, k, t.ne3d[idx], t.kap3d[idx], TargetNoPin());
+    });
 }
 
 template <int L>
@@ -94,12 +91,9 @@ void host_flow(const FlowArgs &a)
 {
     const double *F = target_factors();
     const long nodes = (long)a.nx * a.ny * a.nz;
-    for (int i = 0; i < a.nx; ++i)
-        for (int j = 0; j < a.ny; ++j)
-            for (int k = 0; k < a.nz; ++k) {
-                const long idx = ((long)i * a.ny + j) * a.nz + k;
-                target_flow<L>(a, F, a.c, i, j, k, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes], TargetNoPin());
-            }
+    for_each_node_host(a.nx, a.ny, a.nz, [&](int i, int j, int k, long idx) {
+        target_flow<L>(a, F, a.c, i, j, k, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes], TargetNoPin());
+    });
 }
 
 }  // namespace
@@ -118,16 +112,11 @@ extern "C" int cbet_target_tables(const cbet_params *p, const double *te, const 
     TargetArgs a{};
     a.t = tabulate_args(p, d, ne3d, kappa3d, nullptr, nullptr, nullptr);   // the profiles go to host_tables beside the block
     target_fill(target, &a);
-    switch (inst) {
-    case 0: host_tables<0>(a, r, ne, te); break;
-    case 2: host_tables<2>(a, r, ne, te); break;
-    case 8: host_tables<8>(a, r, ne, te); break;
-    default: host_tables<16>(a, r, ne, te); break;
-    }
+    dispatch_lmax(inst, [&](auto l) { host_tables<decltype(l)::value>(a, r, ne, te); });
     return CBET_OK;
 }
 
-// The host twin of k_tabulate_flow (cbet_flow.hip).
+// The host twin of k_tabulate_flow (cbet_target.hip).
 extern "C" int cbet_flow_table(const cbet_params *p, const cbet_gain_params *g, const cbet_target *target, double *out)
 {
     using namespace cbet;
@@ -140,11 +129,6 @@ extern "C" int cbet_flow_table(const cbet_params *p, const cbet_gain_params *g, 
     if (target)
         if (int rc = target_check(target, &inst)) return rc;
     const FlowArgs a = flow_args(p, d, g, cs, target, out);
-    switch (inst) {
-    case 0: host_flow<0>(a); break;
-    case 2: host_flow<2>(a); break;
-    case 8: host_flow<8>(a); break;
-    default: host_flow<16>(a); break;
-    }
+    dispatch_lmax(inst, [&](auto l) { host_flow<decltype(l)::value>(a); });
     return CBET_OK;
 }

@@ -1,38 +1,31 @@
 // cbet_target_model.h -- one node of a perturbed target (include/cbet_mi355x.h, "perturbed targets"), written once for
-// the gfx950 kernel (cbet_target.hip) and its host twin (cbet_target_host.cpp).  Built with -ffp-contract=off on both
-// sides: every operator below is one IEEE fp64 operation, in the order the header fixes, so the two agree bit for bit.
-// The includer provides sqrt(double): <hip/hip_runtime.h> in device code, <cmath> on the host.
+// the gfx950 kernels (cbet_target.hip) and their host twins (cbet_target_host.cpp) over the shared node statements
+// (cbet_node_model.h).  Built with -ffp-contract=off on both sides: every operator below is one IEEE fp64 operation, in the
+// order the header fixes, so the two agree bit for bit.  The includer provides sqrt(double): <hip/hip_runtime.h> in device
+// code, <cmath> on the host.
 #ifndef CBET_TARGET_MODEL_H_
 #define CBET_TARGET_MODEL_H_
 
 #include "cbet_device.h"
-
-#if defined(__HIP__)
-#define CBET_HD __attribute__((host)) __attribute__((device)) __attribute__((always_inline)) inline
-#else
-#define CBET_HD inline
-#endif
+#include "cbet_node_model.h"
 
 namespace cbet {
 
-// interp_table2 of cbet_kernels.hip restated (launch_ray_XZ.cu:16-63: clamped piecewise-linear lookup by bisection, the
-// two tables sharing one abscissa).  Restated rather than shared so that k_tabulate's and k_plasma_records' code stays as
-// it is.
-CBET_HD void target_interp2(const double *y1, const double *y2, const double *x, const double xp, int n, double &o1,
-                            double &o2)
+// The instantiations of target_delta: f(LmaxTag<L>()) for the one target_check chose, false if inst is none of them.
+template <int L>
+struct LmaxTag {
+    static constexpr int value = L;
+};
+template <class F>
+bool dispatch_lmax(int inst, F f)
 {
-    const bool ascending = x[0] <= x[n - 1];
-    if (ascending ? (xp <= x[0]) : (xp >= x[0])) { o1 = y1[0]; o2 = y2[0]; return; }
-    if (ascending ? (xp >= x[n - 1]) : (xp <= x[n - 1])) { o1 = y1[n - 1]; o2 = y2[n - 1]; return; }
-    unsigned lo = 0, hi = n - 1, mid = (lo + hi) >> 1;
-    while (lo < hi - 1) {
-        const bool go_low = ascending ? (x[mid] >= xp) : !(x[mid] <= xp);
-        if (go_low) hi = mid; else lo = mid;
-        mid = (lo + hi) >> 1;
+    switch (inst) {
+    case 0: f(LmaxTag<0>()); return true;
+    case 2: f(LmaxTag<2>()); return true;
+    case 8: f(LmaxTag<8>()); return true;
+    case 16: f(LmaxTag<16>()); return true;
     }
-    const double dx = x[mid + 1] - x[mid], t = xp - x[mid];
-    o1 = y1[mid] + (y1[mid + 1] - y1[mid]) / dx * t;
-    o2 = y2[mid] + (y2[mid + 1] - y2[mid]) / dx * t;
+    return false;
 }
 
 // delta = sum_c c[c] Y_c(s / rho) with the header's recurrence and summation order; L is the instantiation, c holds
@@ -83,44 +76,39 @@ CBET_HD double target_delta(FP F, CP c, double sx, double sy, double sz, double 
     return delta;
 }
 
-// One node's table entries: node_plasma of cbet_kernels.hip (launch_ray_XZ.cu:296-305) with the radius taken on the
-// perturbed target.  F: the factor table, c: the coefficients (a.c), r / ne / te: the profile (LDS in the kernel).
+// The node's radius on the perturbed target: rho / (1 + delta).
+template <int L, class FP, class CP, class Pin>
+CBET_HD double target_radius(FP F, CP c, double sx, double sy, double sz, double rho, Pin pin)
+{
+    const double q = 1.0 + target_delta<L>(F, c, sx, sy, sz, rho, pin);
+    double rhop = rho;
+    if (q != 1.0) rhop = rho / q;                                   // (rho / 1.0 is rho: the division is skipped, not changed)
+    return rhop;
+}
+
+// One node's table entries: the plain tabulation's statements (launch_ray_XZ.cu:296-305) with the radius taken about the
+// target's centre, on the perturbed target.  F: the factor table, c: the coefficients (a.c), r / ne / te: the profile (LDS
+// in the kernel).
 template <int L, class FP, class CP, class Pin>
 CBET_HD void target_node(const TargetArgs &a, FP F, CP c, const double *r, const double *ne, const double *te, int i, int j,
                          int k, double &ed, double &kap, Pin pin)
 {
-    const TabulateArgs &t = a.t;
-    const double xc = i * t.dx + t.xmin, yc = j * t.dy + t.ymin, zc = k * t.dz + t.zmin;
-    const double sx = xc - a.ox, sy = yc - a.oy, sz = zc - a.oz;
-    const double rho = sqrt(sx * sx + sy * sy + sz * sz);
-    const double q = 1.0 + target_delta<L>(F, c, sx, sy, sz, rho, pin);
-    double rhop = rho;
-    if (q != 1.0) rhop = rho / q;                                   // (rho / 1.0 is rho: the division is skipped, not changed)
-    double etemp;
-    target_interp2(ne, te, r, rhop, t.nprofile, ed, etemp);
-    const double eta = 5.2e-5 * 10.0 / (etemp * sqrt(etemp));       // :299
-    const double nuei = (1e6 * ed * (kEc * kEc) / kMe) * eta;       // :300
-    kap = ed / t.ncrit * nuei * t.dt;                               // :305 up to "* uray"
+    double sx, sy, sz, rho, etemp;
+    node_centre(a.t, i, j, k, a.ox, a.oy, a.oz, sx, sy, sz, rho);
+    const double rhop = target_radius<L>(F, c, sx, sy, sz, rho, pin);
+    interp2(ne, te, r, rhop, a.t.nprofile, ed, etemp);
+    kap = kappa(ed, etemp, a.t.ncrit, a.t.dt);
 }
 
-// One node's flow velocity on the target (include/cbet_mi355x.h, "flow table"): target_node's radius statements, then
-// cell_state's ramp (cbet_grid_kernels.hip) with rho' in the ramp and s / rho as the direction.  With a zero offset and
-// zero coefficients every statement is cell_state's own, in its order.
+// One node's flow velocity on the target (include/cbet_mi355x.h, "flow table"): target_node's radius, then the Mach ramp
+// of the gain kernels' cell state with rho' in the ramp and s / rho as the direction.  With a zero offset and zero
+// coefficients every statement is cell_state's own (cbet_grid_kernels.hip), in its order.
 template <int L, class FP, class CP, class Pin>
 CBET_HD void target_flow(const FlowArgs &a, FP F, CP c, int i, int j, int k, double &ux, double &uy, double &uz, Pin pin)
 {
-    const double xc = i * a.dx + a.xmin, yc = j * a.dy + a.ymin, zc = k * a.dz + a.zmin;
-    const double sx = xc - a.ox, sy = yc - a.oy, sz = zc - a.oz;
-    const double rho = sqrt(sx * sx + sy * sy + sz * sz);
-    const double q = 1.0 + target_delta<L>(F, c, sx, sy, sz, rho, pin);
-    double rhop = rho;
-    if (q != 1.0) rhop = rho / q;
-    double t = (rhop - a.mach_r0) / (a.mach_r1 - a.mach_r0);
-    if (t < 0.0) t = 0.0;
-    if (t > 1.0) t = 1.0;
-    const double um = (a.mach_0 + (a.mach_1 - a.mach_0) * t) * a.cs;
-    ux = uy = uz = 0.0;
-    if (rho > 0.0) { ux = um * (sx / rho); uy = um * (sy / rho); uz = um * (sz / rho); }
+    double sx, sy, sz, rho;
+    node_centre(a, i, j, k, a.ox, a.oy, a.oz, sx, sy, sz, rho);
+    radial_flow(a, target_radius<L>(F, c, sx, sy, sz, rho, pin), rho, sx, sy, sz, ux, uy, uz);
 }
 
 }  // namespace cbet

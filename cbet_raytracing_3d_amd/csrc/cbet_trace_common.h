@@ -13,6 +13,7 @@ namespace cbet {
 
 // ---------------------------------------------------------------------------------------------
 // launch_ray_XZ.cu:16-63 -- clamped piecewise-linear lookup, bisection; both abscissa orders.
+// (The node tables' lookups share one bracket, cbet_node_model.h; written over it the trace kernels compile differently.)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double interp_table(const double *y, const double *x, const double xp, int n)
 {
@@ -155,29 +156,17 @@ __device__ __forceinline__ int wave_sum(int v)
     return v;
 }
 
-// 8-byte gather from a node table by 32-bit element index: uniform base + zero-extended 32-bit
-// byte offset, which the backend turns into the saddr+voffset form of global_load_dwordx2 (no
-// 64-bit address arithmetic per lane).  Valid while 8*nodes < 2^32 (checked on the host).
+// 8-byte gather from a node table, or from a beam's haloed gain grid (CBET hooks), by 32-bit element index: uniform base +
+// zero-extended 32-bit byte offset, which the backend turns into the saddr+voffset form of global_load_dwordx2 (no 64-bit
+// address arithmetic per lane).  Valid while 8*nodes < 2^32 (checked on the host).  bound: the table's entries, which the
+// bounds-audited build checks the index against (TraceArgs.audit_nodes, audit_hsize).
 template <bool IDX64>
-__device__ __forceinline__ double node_load(const TraceArgs &a, const double *base, unsigned idx)
+__device__ __forceinline__ double node_load(const TraceArgs &a, const double *base, unsigned idx, unsigned long long bound)
 {
 #ifdef CBET_DEBUG_BOUNDS
-    if (!(idx < a.audit_nodes)) { audit_fail(a); return 0.0; }
+    if (!(idx < bound)) { audit_fail(a); return 0.0; }
 #else
-    (void)a;
-#endif
-    if (IDX64) return base[idx];
-    return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + (idx * 8u));
-}
-
-// The same gather from a beam's haloed gain grid (CBET hooks); only the audited range differs.
-template <bool IDX64>
-__device__ __forceinline__ double gain_load(const TraceArgs &a, const double *base, unsigned idx)
-{
-#ifdef CBET_DEBUG_BOUNDS
-    if (!(idx < a.audit_hsize)) { audit_fail(a); return 0.0; }
-#else
-    (void)a;
+    (void)a; (void)bound;
 #endif
     if (IDX64) return base[idx];
     return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + (idx * 8u));

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, parity_err
+from helpers.device_tables import context_flow
 
 pytestmark = pytest.mark.gpu
 
@@ -48,13 +49,9 @@ def _tracer(api, inputs, shape, beams):
 
 def _flow_bits(api, tr):
     """The flow table the tracer's context has selected, [3, nx, ny, nz] int64 bit patterns."""
-    p = tr.params
-    n = 3 * p.nx * p.ny * p.nz
-    addr = tr.ctx.flow()
-    assert addr
-    h = np.empty(n)
-    api.moveToAndFromGPU(h, addr, 8 * n, tr.gpu)
-    return h.view(np.int64).reshape(3, p.nx, p.ny, p.nz)
+    flow = context_flow(api, tr.ctx, tr.params, tr.gpu)
+    assert flow is not None
+    return flow
 
 
 def _stream(torch):

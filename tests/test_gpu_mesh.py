@@ -7,6 +7,7 @@ import pytest
 
 from conftest import NCPU, parity_err
 from helpers import mesh_cases as M
+from helpers.device_tables import context_flow, context_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -39,17 +40,7 @@ def _download(api, tr):
     """(ne3d, kappa3d) of the tracer's context and the flow table it has selected ([3, nx, ny, nz]; None without one)."""
     import torch
     torch.cuda.synchronize()
-    p = tr.params
-    n, shape = p.nx * p.ny * p.nz, (p.nx, p.ny, p.nz)
-    out = []
-    for addr, count, shp in [(a, n, shape) for a in tr.ctx.tables()] + [(tr.ctx.flow(), 3 * n, (3,) + shape)]:
-        if not addr:
-            out.append(None)
-            continue
-        h = np.empty(count)
-        api.moveToAndFromGPU(h, addr, 8 * count, tr.gpu)
-        out.append(h.reshape(shp))
-    return out
+    return context_tables(api, tr.ctx, tr.params, tr.gpu, bits=False) + [context_flow(api, tr.ctx, tr.params, tr.gpu, bits=False)]
 
 
 def _same_bits(a, b):

@@ -4,6 +4,8 @@ must remember the records exactly as after the two calls (reused while nothing c
 import numpy as np
 import pytest
 
+from helpers.device_tables import context_tables
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,16 +24,8 @@ def api():
 
 
 def _download(api, ctx, p, gpu):
-    """(ne3d, kappa3d, records[n, 4]) of a context as int64 bit patterns."""
-    n = p.nx * p.ny * p.nz
-    ne_addr, kap_addr = ctx.tables()
-    rec_addr, _ = ctx.step_records()
-    out = []
-    for addr, count in ((ne_addr, n), (kap_addr, n), (rec_addr, 4 * n)):
-        h = np.empty(count)
-        api.moveToAndFromGPU(h, addr, 8 * count, gpu)
-        out.append(h.view(np.int64))
-    return out[0].reshape(p.nx, p.ny, p.nz), out[1].reshape(p.nx, p.ny, p.nz), out[2].reshape(p.nx, p.ny, p.nz, 4)
+    """(ne3d, kappa3d, records[nx, ny, nz, 4]) of a context as int64 bit patterns."""
+    return context_tables(api, ctx, p, gpu, records=True)
 
 
 def _params(api, shape, padded):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, parity_err
+from helpers.device_tables import context_tables as _download
 
 PARITY_TOL = 1e-9          # the project's bound on the SURVEY 8(c) metric (tests/test_gpu_parity.py)
 UM = 1e-4                  # cm
@@ -38,21 +39,6 @@ def _tracer(api, inputs, shape, beams):
     p = api.default_params(shape[0], nbeams=len(beams))
     p.ny, p.nz = shape[1], shape[2]
     return RayTracer(p, r, ne, te, beam_norm=bn[beams])
-
-
-def _download(api, ctx, p, gpu, records=False):
-    """ne3d, kappa3d (and the step records [n, 4]) of a context as int64 bit patterns."""
-    n = p.nx * p.ny * p.nz
-    ne_addr, kap_addr = ctx.tables()
-    parts = [(ne_addr, n, (p.nx, p.ny, p.nz)), (kap_addr, n, (p.nx, p.ny, p.nz))]
-    if records:
-        parts.append((ctx.step_records()[0], 4 * n, (p.nx, p.ny, p.nz, 4)))
-    out = []
-    for addr, count, shape in parts:
-        h = np.empty(count)
-        api.moveToAndFromGPU(h, addr, 8 * count, gpu)
-        out.append(h.view(np.int64).reshape(shape))
-    return out
 
 
 # ---- 6. device = host twin, bitwise -----------------------------------------------------------------------------------

@@ -110,6 +110,30 @@ def test_zero_target_gives_the_oracle_tables_bitwise(api, oracle, inputs, shape)
             assert g.shape == w.shape and np.array_equal(g.view(np.int64), w.view(np.int64))
 
 
+# ---- 1b. the shared bracket, both abscissa orders -------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(9, 7, 13), (12, 12, 12)], ids=["9x7x13", "12"])
+def test_plain_tables_equal_the_oracle_bitwise_in_both_abscissa_orders(api, oracle, inputs, shape):
+    """The twin's lookup (csrc/cbet_node_model.h bracket, interp2) against the oracle's interp_cuda: the shipped profile
+    (ascending radii) and the same profile reversed, which takes the descending branch of the clamp tests and of the
+    bisection's go-low rule and interpolates every segment from its other end."""
+    _, r, ne, te = inputs
+    p = _params(api, shape)
+    cfg = oracle.default_config(shape[0], ny=shape[1], nz=shape[2])
+    tables = {}
+    for order in ("ascending", "descending"):
+        prof = [np.ascontiguousarray(v if order == "ascending" else v[::-1]) for v in (r, ne, te)]
+        assert (prof[0][0] < prof[0][-1]) == (order == "ascending")
+        got = api.target_tables(p, *prof, api.Target())
+        want = oracle.node_tables(cfg, *prof)
+        for what, g, w in zip(("ne3d", "kappa3d"), got, want):
+            diff = g.view(np.int64) != w.view(np.int64)
+            print("%s %s %s: %d of %d words differ" % (shape, order, what, int(diff.sum()), diff.size))
+            assert g.shape == w.shape and not diff.any(), (order, what, np.argwhere(diff)[:5].tolist())
+        tables[order] = got
+    # the reversed profile is another computation, not the same one relabelled: its tables differ in the last bits
+    assert any((a.view(np.int64) != d.view(np.int64)).any() for a, d in zip(tables["ascending"], tables["descending"]))
+
+
 # ---- 2. independent restatement -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [9, 17])
 @pytest.mark.parametrize("lmax", [0, 1, 2])
