@@ -684,7 +684,7 @@ _Static_assert(sizeof(cbet_ray_exit) == 80, "cbet_ray_exit is 80 bytes");
 #define CBET_TALLY_ABSORBED 2     /* sum of (uray0 + gained - uray)                                */
 #define CBET_TALLY_ESCAPED 3      /* sum of uray over rays with CBET_RAY_ESCAPED                   */
 #define CBET_TALLY_STRANDED 4     /* ... over rays with CUTOFF and not ESCAPED                     */
-#define CBET_TALLY_UNFINISHED 5   /* ... over rays with TIMEOUT                                    */
+#define CBET_TALLY_UNFINISHED 5   /* ... over rays with neither: the trace's TIMEOUT rays          */
 #define CBET_TALLY_N_RAYS 6       /* records with CBET_RAY_LAUNCHED                                */
 #define CBET_TALLY_N_ESCAPED 7    /* ... of those, ESCAPED                                         */
 
@@ -706,8 +706,11 @@ int cbet_trace_exits(const double *ne3d, const double *kappa3d, const double *ga
                      cbet_context *ctx, void *stream);
 /*
  * Per-beam energy balance of exit records: exits = device [nbeams][L], tally = device double[nbeams][8] (columns
- * CBET_TALLY_*), OVERWRITTEN.  Only records with CBET_RAY_LAUNCHED count; per beam
- *   launched + gained = absorbed + escaped + stranded + unfinished   (up to rounding).
+ * CBET_TALLY_*), OVERWRITTEN.  Only records with CBET_RAY_LAUNCHED count, and each of them is booked in exactly one of
+ * escaped, stranded, unfinished -- escaped if ESCAPED is set, else stranded if CUTOFF is set, else unfinished -- so per beam
+ *   launched + gained = absorbed + escaped + stranded + unfinished   (up to rounding)
+ * for ANY records.  cbet_trace_exits sets TIMEOUT on exactly the rays with neither ESCAPED nor CUTOFF; in a record from
+ * elsewhere the TIMEOUT bit itself is not looked at (LAUNCHED alone counts as unfinished, CUTOFF | TIMEOUT as stranded).
  * Fixed-order reduction (no atomics): bit-reproducible from run to run.  Enqueued on `stream`.
  */
 int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, void *stream);
@@ -716,6 +719,8 @@ int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tall
  * the n records is ADDED into device double hist[ntheta][nphi], binned by the exit direction v / |v|:
  *   it = min(ntheta - 1, floor((1 - vz / |v|) / 2 * ntheta))        (equal solid angle per polar bin)
  *   ip = min(nphi - 1, floor((atan2(vy, vx) + pi) / (2 pi) * nphi))
+ * A coordinate (the argument of floor) that is not > 0 goes to bin 0; that includes NaN: a record with v = 0 has no polar
+ * coordinate (0 / 0) and lands in it = 0, with ip from atan2(+-0, +-0) as IEEE 754 defines it (+0 for v = +0).
  * A beam's own map: pass its contiguous slice exits + (b - grid_beam0) * L, n = L.  Enqueued on `stream`; the sum
  * order of a bin is not fixed (fp64 atomics).
  */

@@ -241,6 +241,7 @@ typedef struct ray_ctx {
     long grid_stride;     /* doubles between per-beam output grids; 0 = one grid */
     double max_exponent;  /* clamp on |gain * ds| per step */
     double *beam_gain;    /* [nbeams] energy gained through CBET (sum over steps of uray_after - uray_before) */
+    double *exit;         /* optional: the ray's exit record, CBET_ORACLE_EXIT_DOUBLES doubles (cbet_oracle_ray_exit) */
 } ray_ctx;
 
 /* phi(x) = (exp(x) - 1) / x = sum_{n=0}^{17} x^n / (n+1)!  for |x| <= 1, in Horner form from fp64
@@ -282,6 +283,21 @@ static void deposit(const ray_ctx *c, long idx, double v)
     }
 }
 
+/* launch_ray_XZ.cu:351-356, the stop test: which of its conditions hold (0: the ray goes on). */
+static int stop_bits(const cbet_oracle_config *cfg, const cbet_oracle_derived *d, double uray, double uray0,
+                     double px, double py, double pz)
+{
+    const double xmin = cfg->xmin, ymin = cfg->ymin, zmin = cfg->zmin;
+    const double xmax = cfg->xmax, ymax = cfg->ymax, zmax = cfg->zmax;
+    const double dx = d->dx, dy = d->dy, dz = d->dz;
+    int bits = 0;
+    if (uray <= 0.05 * uray0) bits |= CBET_ORACLE_RAY_CUTOFF;
+    if (px < (xmin - (dx / 2.0)) || px > (xmax + (dx / 2.0)) || py < (ymin - (dy / 2.0)) ||
+        py > (ymax + (dy / 2.0)) || pz < (zmin - (dz / 2.0)) || pz > (zmax + (dz / 2.0)))
+        bits |= CBET_ORACLE_RAY_ESCAPED;
+    return bits;
+}
+
 /* launch_ray_XZ.cu:159-357 for one (beam, thread-ray id).  Returns the number of steps. */
 static int trace_one(const ray_ctx *c, int beam, int pre_raynum)
 {
@@ -289,10 +305,10 @@ static int trace_one(const ray_ctx *c, int beam, int pre_raynum)
     const cbet_oracle_derived *d = &c->d;
     const int nx = cfg->nx, ny = cfg->ny, nz = cfg->nz, nr = cfg->nprofile;
     const double xmin = cfg->xmin, ymin = cfg->ymin, zmin = cfg->zmin;
-    const double xmax = cfg->xmax, ymax = cfg->ymax, zmax = cfg->zmax;
     const double dx = d->dx, dy = d->dy, dz = d->dz, dt = d->dt;
     const double half = 0.5001; /* :132 */
 
+    if (c->exit) memset(c->exit, 0, sizeof(double) * CBET_ORACLE_EXIT_DOUBLES);
     double lp[4];
     if (!launch_point_d(cfg, d, c->beam_norm, beam, pre_raynum, c->pow_r, c->phase_r, lp))
         return 0; /* :161,181-183 */
@@ -326,8 +342,9 @@ static int trace_one(const ray_ctx *c, int beam, int pre_raynum)
 
     const long beam_off = (long)beam * c->grid_stride; /* per-beam output grids (CBET extension) */
     double gained = 0.0;
+    double x_max = 0.0, x_min = HUGE_VAL; /* exit record: extremes of the gain exponent over the steps */
 
-    int steps = 0;
+    int steps = 0, stop = 0;
     for (int tt = 0; tt < d->nt; ++tt) { /* :207 */
         /* :212-238 central-difference neighbours, one-sided at the faces */
         int im = ci - 1, ip = ci + 1, jm = cj - 1, jp = cj + 1, km = ck - 1, kp = ck + 1;
@@ -417,8 +434,10 @@ static int trace_one(const ray_ctx *c, int beam, int pre_raynum)
             const double k56 = a5 * gk[hbase + sy * sYh] + a6 * gk[hbase + sx * sXh + sy * sYh];
             const double k78 = a7 * gk[hbase + sy * sYh + sz] + a8 * gk[hbase + sx * sXh + sy * sYh + sz];
             double x = ((k12 + k34) + (k56 + k78)) * ds;
+            if (fabs(x) > x_max) x_max = fabs(x); /* as gathered, before the clamp */
             if (x > c->max_exponent) x = c->max_exponent;
             if (x < -c->max_exponent) x = -c->max_exponent;
+            if (fabs(x) < x_min) x_min = fabs(x); /* as the series sees it, after the clamp */
             const double phi = phi_det(x);
             const double dg = uray * (x * phi);
             u_eff = uray * phi;
@@ -479,10 +498,18 @@ static int trace_one(const ray_ctx *c, int beam, int pre_raynum)
         ++steps;
 
         /* :351-356 */
-        if (uray <= 0.05 * uray0 || px < (xmin - (dx / 2.0)) || px > (xmax + (dx / 2.0)) ||
-            py < (ymin - (dy / 2.0)) || py > (ymax + (dy / 2.0)) || pz < (zmin - (dz / 2.0)) ||
-            pz > (zmax + (dz / 2.0)))
-            break;
+        stop = stop_bits(cfg, d, uray, uray0, px, py, pz);
+        if (stop) break;
+    }
+    if (c->exit) {
+        double *e = c->exit;
+        e[0] = px; e[1] = py; e[2] = pz;
+        e[3] = vx; e[4] = vy; e[5] = vz;
+        e[6] = uray; e[7] = uray0; e[8] = gained;
+        e[9] = steps;
+        e[10] = CBET_ORACLE_RAY_LAUNCHED | (stop ? stop : CBET_ORACLE_RAY_TIMEOUT);
+        e[11] = x_max;
+        e[12] = (x_min == HUGE_VAL) ? 0.0 : x_min;
     }
     if (c->beam_gain) {
 #ifdef _OPENMP
@@ -752,6 +779,33 @@ long long cbet_oracle_trace_cbet_list(const cbet_oracle_config *cfg, const cbet_
 #endif
     for (long it = 0; it < nitems; ++it) total += trace_one(&c, beams[it], raynums[it]);
     return total;
+}
+
+int cbet_oracle_ray_exit(const cbet_oracle_config *cfg, const cbet_oracle_gain_config *g,
+                         const double *beam_norm, const double *ne3d, const double *kap3d,
+                         const double *gain, int beam, int raynum, double *out)
+{
+    /* called once per ray: the power table (it depends on nothing) is filled on the first call only, which makes that
+     * first call not re-entrant */
+    static double phase_r[CBET_ORACLE_NPHASE], pow_r[CBET_ORACLE_NPHASE];
+    static int have_tables = 0;
+    ray_ctx c;
+    if (!have_tables) {
+        cbet_oracle_power_table(phase_r, pow_r);
+        have_tables = 1;
+    }
+    memset(&c, 0, sizeof(c));
+    c.cfg = cfg;
+    cbet_oracle_derive(cfg, &c.d);
+    c.beam_norm = beam_norm;
+    c.phase_r = phase_r;
+    c.pow_r = pow_r;
+    c.ne3d = ne3d;
+    c.kap3d = kap3d;
+    c.gain = gain;
+    c.max_exponent = g->max_exponent;
+    c.exit = out;
+    return trace_one(&c, beam, raynum);
 }
 
 double cbet_oracle_phi(double x) { return phi_det(x); }

@@ -160,6 +160,23 @@ long long cbet_oracle_trace_cbet_list(const cbet_oracle_config *cfg, const cbet_
                                       const double *gain, int quantity, int per_beam, long nitems,
                                       const int *beams, const int *raynums, double *out,
                                       double *beam_gain, int nthreads);
+/*
+ * One ray's exit record from that loop (same node tables, same hooks, gain may be NULL; no deposit):
+ *   out[0..2] final position, out[3..5] velocity after the last kick, out[6] uray, out[7] uray0, out[8] the energy
+ *   gained through CBET, out[9] steps, out[10] status (CBET_ORACLE_RAY_* = the CBET_RAY_* bits of
+ *   include/cbet_mi355x.h: the stop test's conditions that held in the last step, TIMEOUT when none did after nt steps),
+ *   out[11] max over the steps of |x|, x = K ds as gathered (before the clamp to max_exponent),
+ *   out[12] min over the steps of |x| after the clamp (what the choice of the series sees); both 0 without a gain.
+ * A culled ray (cbet_oracle_launch_point == 0) gives all zeros.  Returns the number of steps.
+ */
+#define CBET_ORACLE_RAY_LAUNCHED 1
+#define CBET_ORACLE_RAY_CUTOFF 2
+#define CBET_ORACLE_RAY_ESCAPED 4
+#define CBET_ORACLE_RAY_TIMEOUT 8
+#define CBET_ORACLE_EXIT_DOUBLES 13
+int cbet_oracle_ray_exit(const cbet_oracle_config *cfg, const cbet_oracle_gain_config *g,
+                         const double *beam_norm, const double *ne3d, const double *kap3d,
+                         const double *gain, int beam, int raynum, double *out);
 /* (exp(x) - 1) / x as the ray loop evaluates it (|x| <= 1) */
 double cbet_oracle_phi(double x);
 /* fields[4][nbeams][(n+2)^3] -> gain[nbeams][(n+2)^3] <- gain + relax * (raw - gain); change = {sum |new-old|, sum |new|} */

@@ -105,6 +105,9 @@ def lib():
     L.cbet_oracle_trace_cbet_list.argtypes = [C.POINTER(Config), C.POINTER(GainConfig), _dp, _dp, _dp, C.c_void_p,
                                               C.c_int, C.c_int, C.c_long, _ip, _ip, _dp, C.c_void_p, C.c_int]
     L.cbet_oracle_trace_cbet_list.restype = C.c_longlong
+    L.cbet_oracle_ray_exit.argtypes = [C.POINTER(Config), C.POINTER(GainConfig), _dp, _dp, _dp, C.c_void_p, C.c_int,
+                                       C.c_int, _dp]
+    L.cbet_oracle_ray_exit.restype = C.c_int
     L.cbet_oracle_phi.argtypes = [C.c_double]
     L.cbet_oracle_phi.restype = C.c_double
     L.cbet_oracle_gain_field.argtypes = [C.POINTER(Config), C.POINTER(GainConfig), _dp, _dp, C.c_double, _dp,
@@ -267,6 +270,22 @@ def trace_cbet(cfg, g, beam_norm, ne3d, kap3d, gain=None, quantity=0, per_beam=F
                                          np.ascontiguousarray(kap3d, dtype=np.float64), gp, quantity,
                                          1 if per_beam else 0, out, beam_gain.ctypes.data_as(C.c_void_p), nthreads)
     return out, int(steps), beam_gain
+
+
+EXIT_FIELDS = ("x", "y", "z", "vx", "vy", "vz", "uray", "uray0", "gained", "steps", "status", "x_max", "x_min")
+
+
+def ray_exit(cfg, g, beam_norm, ne3d, kap3d, gain, beam, raynum):
+    """One ray's exit record from the node-table CBET loop (gain may be None): float64 [13], EXIT_FIELDS -- the fields
+    of cbet_ray_exit, then max |x| before the clamp and min |x| after it over the ray's steps."""
+    out = np.zeros(len(EXIT_FIELDS))
+    gp = None
+    if gain is not None:
+        assert gain.dtype == np.float64 and gain.flags.c_contiguous
+        assert gain.size == cfg.nbeams * (cfg.nx + 2) * (cfg.ny + 2) * (cfg.nz + 2)
+        gp = gain.ctypes.data_as(C.c_void_p)
+    lib().cbet_oracle_ray_exit(C.byref(cfg), C.byref(g), beam_norm, ne3d, kap3d, gp, beam, raynum, out)
+    return out
 
 
 def gain_field(cfg, g, fields, ne3d, relax=1.0, gain=None, nthreads=1):
