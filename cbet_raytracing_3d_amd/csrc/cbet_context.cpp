@@ -178,9 +178,8 @@ int cbet_context_create(cbet_context **out, const cbet_params *p, int gpu)
     if ((e = hipMalloc((void **)&ctx->ylaunch, yl.size() * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(ylaunch)");
     if ((e = hipMalloc((void **)&ctx->bounds, 6 * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(bounds)");
     {
-        // launch_ray_XZ.cu:352-354: xmin - (dx / 2.0), xmax + (dx / 2.0), ...
-        const double hb[6] = {p->xmin - (d.dx / 2.0), p->xmax + (d.dx / 2.0), p->ymin - (d.dy / 2.0),
-                              p->ymax + (d.dy / 2.0), p->zmin - (d.dz / 2.0), p->zmax + (d.dz / 2.0)};
+        double hb[6];
+        host_exit_planes(p, d, hb);
         if ((e = hipMemcpy(ctx->bounds, hb, sizeof hb, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(bounds)");
     }
     if ((e = hipMalloc((void **)&ctx->live, std::max<size_t>(1, live.size()) * sizeof(int))) != hipSuccess) return bail(e, "hipMalloc(live)");

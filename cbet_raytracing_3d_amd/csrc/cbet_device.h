@@ -69,6 +69,7 @@ struct TraceArgs {
     double inv_dx, inv_dy, inv_dz;          // (1/dx) of launch_ray_XZ.cu:276-278
     double fx_hi, fy_hi, fz_hi;             // n - 3: cell-unit positions beyond it are "near a face"
     const double *bounds;                   // device: {xlo,xhi,ylo,yhi,zlo,zhi} = xmin-(dx/2.0) ... launch_ray_XZ.cu:352-354
+    double exit_planes[6];                  // ... the same six values in the argument segment (host_exit_planes): the shipped kernel compares with scalar operands
     double tol_x, tol_y, tol_z;             // 0.5001*dx of launch_ray_XZ.cu:164-176
     double xconst, yconst, zconst;          // main.cu:156-159
     int nt, absorption;

@@ -100,6 +100,14 @@ void grid_args(Args &a, const cbet_params *p, const cbet_derived &d)
     a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
     a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
 }
+// The six exit planes {xlo, xhi, ylo, yhi, zlo, zhi} of launch_ray_XZ.cu:352-354, xmin - (dx / 2.0), xmax + (dx / 2.0), ...:
+// ONE statement for the array context_create uploads (cbet_context::bounds) and for TraceArgs::exit_planes.
+inline void host_exit_planes(const cbet_params *p, const cbet_derived &d, double out[6])
+{
+    out[0] = p->xmin - (d.dx / 2.0); out[1] = p->xmax + (d.dx / 2.0);
+    out[2] = p->ymin - (d.dy / 2.0); out[3] = p->ymax + (d.dy / 2.0);
+    out[4] = p->zmin - (d.dz / 2.0); out[5] = p->zmax + (d.dz / 2.0);
+}
 // The host twins' walk over the nodes, in node order: body(i, j, k, idx) with idx = (i * ny + j) * nz + k.
 template <class Body>
 void for_each_node_host(int nx, int ny, int nz, Body body)

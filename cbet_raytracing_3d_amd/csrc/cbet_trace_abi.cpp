@@ -49,6 +49,7 @@ int cbet::trace_impl(int b, unsigned nindices, const double *ne3d, const double 
     a.inv_dx = 1 / d.dx; a.inv_dy = 1 / d.dy; a.inv_dz = 1 / d.dz;      // launch_ray_XZ.cu:276-278
     a.fx_hi = p->nx - 3.0; a.fy_hi = p->ny - 3.0; a.fz_hi = p->nz - 3.0;
     a.bounds = ctx->bounds;                                              // :352-354, see context_create
+    host_exit_planes(&ctx->p, ctx->d, a.exit_planes);                    // ... and by value, from the values context_create uploaded
     a.tol_x = 0.5001 * d.dx; a.tol_y = 0.5001 * d.dy; a.tol_z = 0.5001 * d.dz;  // :164-176
     a.xconst = xconst; a.yconst = yconst; a.zconst = zconst;
     a.nt = d.nt; a.absorption = p->absorption;

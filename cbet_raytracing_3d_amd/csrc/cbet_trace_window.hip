@@ -14,7 +14,8 @@
 //     (:282-292) is a function of g = f - cell alone and every difference it forms is exact, so it is
 //     evaluated with two comparisons (cbet_relocate.h, relocate_deep_interior; fuzzed against the
 //     literal loop on the CPU).  Whether a wave is "deep inside" is decided on the SCALAR unit from the
-//     deposit windows' origins; near the faces the wave takes the closed form with the face rules.
+//     deposit windows' origins, AXIS BY AXIS (three bits): along an axis near a face the wave takes the closed form
+//     with the face rules and compares that axis's two exit planes -- scalar operands from the argument segment.
 //   * deposit: wave-private dense LDS tiles of fp64 accumulators ("boxes") whose origins follow the
 //     bundle.  A lane sums its ray's deposits in eight registers while the ray's eight target nodes stay the
 //     same; when they change it issues eight ds_add_f64 into its box (plain trace; the CBET kernels
@@ -41,6 +42,7 @@
 // the deposit windows' diagnostics (cbet_params.window_stats).
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <type_traits>
 
 // The hand-counted vmcnt waits below assume ONE in-order vector-memory counter shared by loads, stores and atomics
@@ -150,8 +152,18 @@ template <class T, int AX, int COUNT, class G>
 __device__ __forceinline__ void retire_planes(const TraceArgs &a, double *tile, const Origin &o, int coord, int step,
                                               int lane, G edep, int sXh, int sYh, WaveCounters &wc)
 {
-    constexpr int WO = AX == 0 ? T::WY : T::WX;
+    constexpr int WO = AX == 0 ? T::WY : T::WX, OM = WO - 1;
     constexpr int IT = (WO * T::WZ + kWave - 1) / kWave;
+    // A lane's second entry of a plane (idx + 64) lies RS rows of the other lateral axis beyond its first: in the other
+    // half of the box.  In the grid that is RS rows up or down (the box is toroidal), in the exclusive-or layout a constant
+    // exclusive-or of the slot: the row index gains its top bit and, along y, the swizzle (2 y) bit 3 of the z field.
+    constexpr int RS = kWave / T::WZ;
+    static_assert(IT == 1 || (IT == 2 && 2 * RS == WO), "a plane is one entry per lane, or two in the halves of the other axis");
+    static_assert(!T::XOR || IT == 1 || (RS == 4 && T::YS == 16 && T::XS == 128), "the second entry's slot is written for the 8 x 8 x 16 box");
+    constexpr int SLOT_X = AX == 0 ? (RS * T::YS) ^ ((2 * RS) & T::ZM) : RS * T::XS;
+    const int r0 = lane / T::WZ, r1 = lane & T::ZM, k = abs_in<T::ZM>(o.z, r1);   // (the lane's first entry)
+    const int d0 = (r0 - (AX == 0 ? o.y : o.x)) & OM, dnode = ((d0 & RS) ? -RS : RS) * (AX == 0 ? sYh : sXh);
+    const bool in_plane = !(WO * T::WZ < kWave) || lane < WO * T::WZ;
     double v[COUNT * IT];
     int slot[COUNT * IT], node[COUNT * IT];
 #pragma unroll
@@ -160,16 +172,18 @@ __device__ __forceinline__ void retire_planes(const TraceArgs &a, double *tile, 
         const int fixed = c & (AX == 0 ? T::XM : T::YM);
 #pragma unroll
         for (int e = 0; e < IT; ++e) {
-            const int idx = e * kWave + lane, r0 = idx / T::WZ, r1 = idx & T::ZM, k = abs_in<T::ZM>(o.z, r1);
-            const int q = pl * IT + e;
-            if (AX == 0) {
-                slot[q] = fixed * T::XS + r0 * T::YS + T::zr(fixed, r0, r1);
-                node[q] = c * sXh + abs_in<T::YM>(o.y, r0) * sYh + k;
+            const int q = pl * IT + e, re = r0 + e * RS;
+            if (e == 1 && T::XOR) {
+                slot[q] = slot[q - 1] ^ SLOT_X;
+                node[q] = node[q - 1] + dnode;
+            } else if (AX == 0) {
+                slot[q] = fixed * T::XS + re * T::YS + T::zr(fixed, re, r1);
+                node[q] = c * sXh + __mul24(abs_in<T::YM>(o.y, re), sYh) + k;
             } else {
-                slot[q] = r0 * T::XS + fixed * T::YS + T::zr(r0, fixed, r1);
-                node[q] = abs_in<T::XM>(o.x, r0) * sXh + c * sYh + k;
+                slot[q] = re * T::XS + fixed * T::YS + T::zr(re, fixed, r1);
+                node[q] = __mul24(abs_in<T::XM>(o.x, re), sXh) + c * sYh + k;
             }
-            const bool ok = (!(WO * T::WZ < kWave) || idx < WO * T::WZ) && CBET_AUDIT(a, (unsigned)slot[q] < (unsigned)T::N);
+            const bool ok = in_plane && CBET_AUDIT(a, (unsigned)slot[q] < (unsigned)T::N);
             v[q] = ok ? tile[slot[q]] : 0.0;
         }
     }
@@ -201,11 +215,11 @@ __device__ __forceinline__ void retire_plane(const TraceArgs &a, double *tile, c
         if (AX == 0) {
             slot = fixed * T::XS + r0 * T::YS + T::zr(fixed, r0, r1);
             slot_d = T::slot_d(fixed, r0, r1);
-            node = coord * sXh + abs_in<T::YM>(o.y, r0) * sYh + k;
+            node = coord * sXh + __mul24(abs_in<T::YM>(o.y, r0), sYh) + k;
         } else {
             slot = r0 * T::XS + fixed * T::YS + T::zr(r0, fixed, r1);
             slot_d = T::slot_d(r0, fixed, r1);
-            node = abs_in<T::XM>(o.x, r0) * sXh + coord * sYh + k;
+            node = __mul24(abs_in<T::XM>(o.x, r0), sXh) + coord * sYh + k;
         }
         const bool ok = in_plane && CBET_AUDIT(a, (unsigned)slot < (unsigned)T::N);
         const double v = ok ? tile[slot] : 0.0;
@@ -239,7 +253,7 @@ __device__ __forceinline__ void retire_zplane(const TraceArgs &a, double *tile, 
     static_assert(T::WX * T::WY <= kWave, "one z-plane entry per lane");
     const int r0 = lane / T::WY, r1 = lane & T::YM, fixed = coord & T::ZM;
     const int slot = r0 * T::XS + r1 * T::YS + T::zr(r0, r1, fixed);
-    const int node = abs_in<T::XM>(o.x, r0) * sXh + abs_in<T::YM>(o.y, r1) * sYh + coord;
+    const int node = __mul24(abs_in<T::XM>(o.x, r0), sXh) + __mul24(abs_in<T::YM>(o.y, r1), sYh) + coord;
     const bool ok = (!(T::WX * T::WY < kWave) || lane < T::WX * T::WY) && CBET_AUDIT(a, (unsigned)slot < (unsigned)T::N);
     const double v = ok ? tile[slot] : 0.0;
     if (NC > 1) {
@@ -272,7 +286,7 @@ __device__ __forceinline__ void retire_zbrick(const TraceArgs &a, double *tile, 
     static_assert(T::WY == 8 && T::WZ == 16, "a brick is 8 rows of 8 planes per tile x index");
     const int ty = lane >> 3, kz = lane & 7;
     const int tz = (zb + kz) & T::ZM;
-    const int base_node = abs_in<T::YM>(o.y, ty) * sYh + zb + kz;
+    const int base_node = __mul24(abs_in<T::YM>(o.y, ty), sYh) + zb + kz;
     // all reads of a round first, one trip through the LDS queue per round (a read behind its own wait costs a trip each:
     // eight in a row were 2 % of the pass)
     constexpr int ROUND = 4;
@@ -405,16 +419,18 @@ __device__ __forceinline__ bool holds(const Origin &o, int lx, int ly, int lz)
            (unsigned)(lz - o.z) <= (unsigned)T::SZ;
 }
 
-// Is every cell a member of this box can occupy deep inside the grid (cbet_relocate.h, kRelocateDeep <= c <=
-// n - 3) -- and therefore also more than two cells from every exit plane?  A held lane's low corner lies in
-// [o, o + S], its cell index c is the low corner or one less.  Scalar arithmetic only.
+// Along which axes is a cell a member of this box can occupy NOT deep inside the grid (cbet_relocate.h, kRelocateDeep
+// <= c <= n - 3)?  Bit 0: x, bit 1: y, bit 2: z; 0 = deep along every axis -- and therefore also more than two cells
+// from every exit plane.  A held lane's low corner lies in [o, o + S], its cell index c is the low corner or one less.
+// Scalar arithmetic only.
 template <class T>
-__device__ __forceinline__ bool box_deep_inside(const Origin &o, int nx, int ny, int nz)
+__device__ __forceinline__ int box_near_axes(const Origin &o, int nx, int ny, int nz)
 {
-    // six differences that must all be >= 0: the OR of their sign bits in one compare (straight-line scalar code)
+    // two differences per axis that must both be >= 0: the sign bit of their OR (straight-line scalar code)
     const int lo = kRelocateDeep + 1;
-    const int t = (o.x - lo) | (nx - 3 - T::SX - o.x) | (o.y - lo) | (ny - 3 - T::SY - o.y) | (o.z - lo) | (nz - 3 - T::SZ - o.z);
-    return t >= 0;
+    const unsigned tx = (unsigned)((o.x - lo) | (nx - 3 - T::SX - o.x)), ty = (unsigned)((o.y - lo) | (ny - 3 - T::SY - o.y)),
+                   tz = (unsigned)((o.z - lo) | (nz - 3 - T::SZ - o.z));
+    return (int)((tx >> 31) | ((ty >> 31) << 1) | ((tz >> 31) << 2));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -492,6 +508,19 @@ __device__ __forceinline__ void record_wait_all(dbl2 &kxy, dbl2 &kzk)
     asm volatile("; CBET_RECORD_WAIT %0 %1\n\ts_waitcnt vmcnt(0)" : "+v"(kxy), "+v"(kzk) : : "memory");
 }
 
+// TraceArgs::exit_planes from the kernel-argument segment into scalar registers, HERE: read as plain members the six
+// values are loaded once in front of the loop and held -- twelve scalar registers the loop does not have (the calm path
+// then reloads other values from spill lanes).  Scalar loads return out of order: the wait is for all of them (it
+// covers the LDS adds of the step as well, issued a gather's latency earlier).
+__device__ __forceinline__ void exit_planes_load(dbl2 &bx, dbl2 &by, dbl2 &bz)
+{
+    const void *args = (const void *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("s_load_dwordx4 %0, %3, %4\n\ts_load_dwordx4 %1, %3, %5\n\ts_load_dwordx4 %2, %3, %6\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(bx), "=&s"(by), "=&s"(bz)
+                 : "s"(args), "i"(offsetof(TraceArgs, exit_planes)), "i"(offsetof(TraceArgs, exit_planes) + 16),
+                   "i"(offsetof(TraceArgs, exit_planes) + 32));
+}
+
 // a + b + c in one instruction (the compiler, left alone, shares partial sums instead: more instructions)
 __device__ __forceinline__ int add3(int a, int b, int c)
 {
@@ -529,6 +558,26 @@ __device__ __forceinline__ void commit(unsigned long long &var, unsigned long lo
 }
 __device__ __forceinline__ void commit_v(int &var, int value) { asm volatile("v_mov_b32 %0, %1" : "+v"(var) : "v"(value)); }
 
+// c + 1 on the lanes of `up`, c - 1 on those of `dn` (ballots), in place: two carry instructions.  The masks come from
+// vector compares: a vector instruction that reads an SGPR as a constant needs two wait states after the vector
+// instruction that wrote it, which the compiler does not track into inline assembly -- hence the s_nop (see mad24).
+__device__ __forceinline__ void cell_step(int &c, unsigned long long up, unsigned long long dn)
+{
+    asm("s_nop 1\n\tv_addc_co_u32_e64 %0, vcc, 0, %0, %1\n\tv_subbrev_co_u32_e64 %0, vcc, 0, %0, %2" : "+v"(c) : "s"(up), "s"(dn) : "vcc");
+}
+// ... along all three axes behind one s_nop (the calm step)
+__device__ __forceinline__ void cell_step3(int &ci, int &cj, int &ck, unsigned long long upx, unsigned long long dnx,
+                                           unsigned long long upy, unsigned long long dny, unsigned long long upz,
+                                           unsigned long long dnz)
+{
+    asm("s_nop 1\n\t"
+        "v_addc_co_u32_e64 %0, vcc, 0, %0, %3\n\tv_addc_co_u32_e64 %1, vcc, 0, %1, %5\n\tv_addc_co_u32_e64 %2, vcc, 0, %2, %7\n\t"
+        "v_subbrev_co_u32_e64 %0, vcc, 0, %0, %4\n\tv_subbrev_co_u32_e64 %1, vcc, 0, %1, %6\n\tv_subbrev_co_u32_e64 %2, vcc, 0, %2, %8"
+        : "+v"(ci), "+v"(cj), "+v"(ck)
+        : "s"(upx), "s"(dnx), "s"(upy), "s"(dny), "s"(upz), "s"(dnz)
+        : "vcc");
+}
+
 // a * b + c on 24-bit operands (the compiler picked the quarter-rate v_mad_u64_u32 for one of the two).  b is a scalar
 // register: on gfx940 / gfx950 a vector instruction that reads an SGPR needs two wait states after a vector instruction
 // that wrote it (a v_readlane reloading it from a spill lane), a hazard the compiler tracks for its own instructions
@@ -553,6 +602,11 @@ constexpr bool kAudited = false;
 constexpr bool kDiagClocks = true;
 #else
 constexpr bool kDiagClocks = false;
+#endif
+#ifdef CBET_DIAG_FACES
+constexpr bool kDiagFaces = true;
+#else
+constexpr bool kDiagFaces = false;
 #endif
 constexpr double kNearTol = 0.5001;   // launch_ray_XZ.cu:132, the nearest-node tolerance
 constexpr double kFarJump = 1.4998;   // relocate_deep_interior's validity bound on |f - cell|
@@ -625,8 +679,14 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         if (T::BRICK) oA.z &= ~7;
         __syncthreads();
     }
-    // wave-uniform flag: every live lane was held by a box after the last step and both boxes lie deep inside the grid
-    int deep = 0;
+    // wave-uniform, one bit per axis (box_near_axes): set unless every live lane was held by a box after the last step and
+    // both boxes lie deep inside the grid along that axis.  0 = the calm step.
+    int near = 7;
+#ifdef CBET_DIAG_FACES
+    // diagnostic build (never shipped): wave-steps that start near a face, the near axes summed over them, wave-steps that
+    // enter the window arm -- reported through the counter slots (see the end of the kernel)
+    unsigned dg_near = 0, dg_axes = 0, dg_arm = 0;
+#endif
 #ifdef CBET_DIAG_CLOCKS
     // diagnostic build (never shipped): shader-clock cycles this wave spends in the record wait and in the window-shift
     // path, reported through the counter slots (see the end of the kernel)
@@ -679,7 +739,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // dead lane's last" copy -- ~10 moves per step.
     double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;   // CBET = 4: the four field quantities a step deposits
 
-    bool slow = true;                        // wave-uniform: this step runs the general (face-aware) forms
+    int slow = 7;                            // wave-uniform: the axes along which this step runs the general (face-aware) forms
     // The loop is rotated: the dependent chain of a step is wait -> kick -> move -> relocate -> gather, everything else
     // fills the gather's shadow.
     double Fx0 = 0, Fx1 = 0, Fy0 = 0, Fy1 = 0, Fz0 = 0, Fz1 = 0;   // the step's six per-axis factors
@@ -883,14 +943,19 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     if (CBET >= 2) inc = q0;   // field passes deposit energy x path length
     if constexpr (ACC && !PIPE) accumulate();   // the step's deposit joins the lane's pending sums
     // ---- termination (:351-356) --------------------------------------------------------------------
-    // The six exit planes are compared only when the wave is not deep inside the grid: a lane held by a deep
-    // box is more than two cells from every face, far beyond the half cell of :352-354.  Ballots of plain
-    // compares over all lanes, masked with `live` on the scalar unit.
+    // An axis's two exit planes are compared only when the wave is not deep inside the grid along it: a lane held by
+    // a box that is deep along an axis is more than two cells from both of that axis's faces, far beyond the half cell
+    // of :352-354.  Ballots of plain compares over all lanes, masked with `live` on the scalar unit; the planes are
+    // scalar operands from the argument segment (TraceArgs::exit_planes: read through the device pointer they are vector
+    // loads the compiler waits for with vmcnt(0), i.e. together with every write-back atomic in flight).
     unsigned long long died = CBET_BALLOT(s.uray <= s.ustop);
-    if (slow || deep == 0) {   // scalar branch
-        const double *b = a.bounds;  // {xlo, xhi, ylo, yhi, zlo, zhi}
-        died |= CBET_BALLOT(s.px < b[0]) | CBET_BALLOT(s.px > b[1]) | CBET_BALLOT(s.py < b[2]) |
-                CBET_BALLOT(s.py > b[3]) | CBET_BALLOT(s.pz < b[4]) | CBET_BALLOT(s.pz > b[5]);
+    const int faces = slow | near;   // (a far jump keeps the cell: all six planes)
+    if (faces != 0) {   // scalar branch
+        dbl2 bx, by, bz;   // {xlo, xhi}, {ylo, yhi}, {zlo, zhi}
+        exit_planes_load(bx, by, bz);
+        if (faces & 1) died |= CBET_BALLOT(s.px < bx.x) | CBET_BALLOT(s.px > bx.y);
+        if (faces & 2) died |= CBET_BALLOT(s.py < by.x) | CBET_BALLOT(s.py > by.y);
+        if (faces & 4) died |= CBET_BALLOT(s.pz < bz.x) | CBET_BALLOT(s.pz > bz.y);
     }
     died &= live;
     if (died != 0ull) {   // scalar branch: some ray ended in this step, its tt + 1-th
@@ -917,7 +982,11 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     };
 
     for (int tt = 0; tt < a.nt; ++tt) {                        // :207  (live != 0 here: checked where lanes end)
-        if constexpr (STATS || kDiagClocks) wc.steps_miss += 1u << 16;
+        if constexpr (STATS || kDiagClocks || kDiagFaces) wc.steps_miss += 1u << 16;
+#ifdef CBET_DIAG_FACES
+        dg_near += near != 0 ? 1 : 0;
+        dg_axes += __builtin_popcount((unsigned)near);
+#endif
         // ---- move ------------------------------------------------------------------------------------------
         // :268-273 kick then drift (stencil values gathered during the previous step)
         s.vx -= rec_kxy.x;
@@ -933,24 +1002,27 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // :282-292 nearest-node update, deep-interior form (cbet_relocate.h relocate_deep_interior: exact for
         // kRelocateDeep <= cell <= n-3 unless the ray moved more than a cell, which sends the wave to the closed form)
         const double g0x = fx - fcx, g0y = fy - fcy, g0z = fz - fcz;
-        const bool upx = g0x >= kNearTol, dnx = g0x < kNearTol - 1.0, upy = g0y >= kNearTol, dny = g0y < kNearTol - 1.0,
-                   upz = g0z >= kNearTol, dnz = g0z < kNearTol - 1.0;
+        const unsigned long long upx = CBET_BALLOT(g0x >= kNearTol), dnx = CBET_BALLOT(g0x < kNearTol - 1.0),
+                                 upy = CBET_BALLOT(g0y >= kNearTol), dny = CBET_BALLOT(g0y < kNearTol - 1.0),
+                                 upz = CBET_BALLOT(g0z >= kNearTol), dnz = CBET_BALLOT(g0z < kNearTol - 1.0);
         // wave-uniform: this step runs the general (face-aware) forms.  One compare of the largest |g| (a NaN -- which
         // moves no cell in either form -- is ignored by the maximum)
-        slow = deep == 0 || (CBET_BALLOT(!(max_abs3(g0x, g0y, g0z) < kFarJump)) & live) != 0ull;
+        slow = ((CBET_BALLOT(!(max_abs3(g0x, g0y, g0z) < kFarJump)) & live) != 0ull) ? 7 : near;
         // ---- relocate, gather -------------------------------------------------------------------
-        // The deep-interior form updates the cell IN PLACE; the rare general form takes the update back first (kept as
-        // copies for it, the old cell costs the common path three moves).
-        const int di = (upx ? 1 : 0) - (dnx ? 1 : 0), dj = (upy ? 1 : 0) - (dny ? 1 : 0), dk = (upz ? 1 : 0) - (dnz ? 1 : 0);
-        s.ci += di;
-        s.cj += dj;
-        s.ck += dk;
-        if (slow) {                        // near a face (or a far jump): closed form with the candidate bounds
-            int oi = s.ci - di, oj = s.cj - dj, ok = s.ck - dk;
-            asm volatile("" : "+v"(oi), "+v"(oj), "+v"(ok));   // (recomputed here, not carried from above the update)
-            s.ci = relocate_closed(oi, fx, nx);
-            s.cj = relocate_closed(oj, fy, ny);
-            s.ck = relocate_closed(ok, fz, nz);
+        // The deep-interior form updates the cell IN PLACE.  Near a face (or after a far jump) the step goes axis by axis, by
+        // scalar branches: the closed form with the candidate bounds along the axes named in `slow`, the in-place form --
+        // exact there -- along the others.  (Two arms, each updating from the old cell, and the in-place form pinned to its
+        // two carry instructions per axis (cell_step): with one shared update that the rare arm takes back, or with the arms'
+        // common tails merged by the compiler, the old cell or the increment costs the common path a copy per axis.)
+        if (slow == 0) {
+            cell_step3(s.ci, s.cj, s.ck, upx, dnx, upy, dny, upz, dnz);
+        } else {
+            if (slow & 1) s.ci = relocate_closed(s.ci, fx, nx);
+            else cell_step(s.ci, upx, dnx);
+            if (slow & 2) s.cj = relocate_closed(s.cj, fy, ny);
+            else cell_step(s.cj, upy, dny);
+            if (slow & 4) s.ck = relocate_closed(s.ck, fz, nz);
+            else cell_step(s.ck, upz, dnz);
         }
         const unsigned new_cell = (unsigned)mad24(mad24(s.ci, ny, s.cj), nz, s.ck);
         // lanes whose ray changed cell (ACC: their pending sums must leave): one compare with the cell it had
@@ -1100,6 +1172,9 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // renews their mark: 1 % of the wave-steps)
         out_core |= miss_m;
         if (out_core != 0ull) {
+#ifdef CBET_DIAG_FACES
+            dg_arm += 1;
+#endif
 #ifdef CBET_DIAG_CLOCKS
             unsigned long long dg_t0;
             asm volatile("s_memtime %0" : "=&s"(dg_t0) : : "memory");
@@ -1113,7 +1188,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             asm volatile("" : "+v"(lx), "+v"(ly), "+v"(lz));      // (formed here: the old origin is not kept for them)
             Origin nA = oA, nB = oB;
             unsigned long long n_hbm = hbm, n_miss = 0ull;
-            int n_bact = b_active, n_deep, n_toff = tile_off;
+            int n_bact = b_active, n_near, n_toff = tile_off;
             // box A follows the lanes whose home it is
             follow_box<T, NC>(a, tileA, nA, memA, lx, ly, lz, lane, edep, sXh, sYh, wc, NSLOT, a.comp_stride);
             const unsigned long long lost_mask =
@@ -1121,7 +1196,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
                          CBET_BALLOT((unsigned)(lz - nA.z) <= (unsigned)T::SZ));
             if (lost_mask == 0ull && n_bact == 0) {
                 // the usual outcome: A moved and holds every live lane again (tile_off = 0 stands, nobody outside)
-                n_deep = box_deep_inside<T>(nA, nx, ny, nz) ? 1 : 0;
+                n_near = box_near_axes<T>(nA, nx, ny, nz);
             } else {
                 bool homeB = CBET_LANES(hbm);
                 const bool inA = alive && holds<T>(nA, lx, ly, lz);
@@ -1159,12 +1234,12 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
                     if (ACC && CBET_LANES(n_miss)) ++wc.n_miss;   // ray-steps whose deposit is bound for HBM (ACC: counted here,
                                                                  // the only place a lane can come to lie outside both boxes)
                 }
-                n_deep = (n_miss == 0ull && box_deep_inside<T>(nA, nx, ny, nz) && (n_bact == 0 || box_deep_inside<TB>(nB, nx, ny, nz))) ? 1 : 0;
+                n_near = n_miss != 0ull ? 7 : (box_near_axes<T>(nA, nx, ny, nz) | (n_bact == 0 ? 0 : box_near_axes<TB>(nB, nx, ny, nz)));
             }
             commit(oA.x, nA.x); commit(oA.y, nA.y); commit(oA.z, nA.z);
             commit(oB.x, nB.x); commit(oB.y, nB.y); commit(oB.z, nB.z);
             commit(hbm, n_hbm); commit(miss_m, n_miss);
-            commit(b_active, n_bact); commit(deep, n_deep);
+            commit(b_active, n_bact); commit(near, n_near);
             commit_v(tile_off, n_toff);
             // (the write-back paths keep the count in a vector register; the common path's stays scalar this way)
             wc.pend = __builtin_amdgcn_readfirstlane(wc.pend);
@@ -1176,9 +1251,8 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
                 dg_nshift += 1;
             }
 #endif
-        } else if (deep == 0) {
-            const int d = (box_deep_inside<T>(oA, nx, ny, nz) && (b_active == 0 || box_deep_inside<TB>(oB, nx, ny, nz))) ? 1 : 0;
-            commit(deep, d);
+        } else if (near != 0) {
+            commit(near, box_near_axes<T>(oA, nx, ny, nz) | (b_active == 0 ? 0 : box_near_axes<TB>(oB, nx, ny, nz)));
         }
         step_tail(tt);
     }
@@ -1210,6 +1284,17 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         atomicAdd(&a.counters[kCntSlabsRetired], dg_t_end - dg_t_start);
         atomicAdd(&a.counters[kCntRays], wc.dg_ret);              // (the ray count gives way to the write-backs' clocks ...)
         atomicAdd(&a.counters[kCntWaveStepsMiss], wc.dg_nret);    // (... and their number)
+    }
+    return;
+#endif
+#ifdef CBET_DIAG_FACES
+    if (lane == 0) {   // the diagnostic build reuses four slots
+        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
+        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
+        atomicAdd(&a.counters[kCntWaveSteps], (unsigned long long)(wc.steps_miss >> 16));
+        atomicAdd(&a.counters[kCntWaveStepsWide], (unsigned long long)dg_near);
+        atomicAdd(&a.counters[kCntWaveStepsMiss], (unsigned long long)dg_axes);
+        atomicAdd(&a.counters[kCntSlabsRetired], (unsigned long long)dg_arm);
     }
     return;
 #endif
