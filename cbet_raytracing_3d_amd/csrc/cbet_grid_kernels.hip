@@ -51,6 +51,24 @@ __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
     return c;
 }
 
+// The prefactor of a cell's pair gains, gain_const (ne / ncrit) / (iaw sqrt(eps)); zero at and above critical density.
+__device__ __forceinline__ double cell_pref(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? a.gain_const * c.frac * (1.0 / a.iaw) / c.rt : 0.0; }
+
+// The epilogue of both gain kernels: the wave's sums of |new - old| and |new| into GainArgs.change, two atomics per wave.
+__device__ __forceinline__ void report_change(const GainArgs &a, int lane, double sum_change, double sum_abs)
+{
+    if (!a.change) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sum_change += __shfl_xor(sum_change, off, kWave);
+        sum_abs += __shfl_xor(sum_abs, off, kWave);
+    }
+    if (lane == 0) {
+        atomicAdd(&a.change[0], sum_change);
+        atomicAdd(&a.change[1], sum_abs);
+    }
+}
+
 // Phase 1 of both gain kernels for one beam's entry of a cell that the beam's rays touched (E != 0): the deposited
 // (E, Dx, Dy, Dz) become (I, kx, ky, kz) in place.  I = E / (group speed x dt) where the beam is present (E > 0,
 // sub-critical plasma, a direction known), else 0; k = |k| D / |D|.  With GainArgs.frozen the three direction
@@ -120,7 +138,7 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
             if (__builtin_amdgcn_ballot_w64(E > 0.0) != 0ull) mask |= 1ull << b;
             if (E != 0.0) normalise_entry(a, c, kmag, ds_node, E, fI, fx, fy, fz, o);
         }
-        const double pref = c.eps > 0.0 ? a.gain_const * c.frac * (1.0 / a.iaw) / c.rt : 0.0;
+        const double pref = cell_pref(a, c);
         for (int bi = 0; bi < a.nbeams; ++bi) {
             const long oi = (long)bi * hsize;
             double raw = 0.0;
@@ -155,19 +173,8 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
             }
         }
     }
-    if (a.change) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sum_change += __shfl_xor(sum_change, off, kWave);
-            sum_abs += __shfl_xor(sum_abs, off, kWave);
-        }
-        if (lane == 0) {
-            atomicAdd(&a.change[0], sum_change);
-            atomicAdd(&a.change[1], sum_abs);
-        }
-    }
+    report_change(a, lane, sum_change, sum_abs);
 }
-
 
 struct BeamAtCell {
     double I, kx, ky, kz;
@@ -304,7 +311,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                 const int hk64 = LC * ibz + lane - sft;
                 const CellState c64 = cell_state<FLOW>(a, ((long)hi * HY + hj) * HZ + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
                 st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
-                st_pref = c64.eps > 0.0 ? a.gain_const * c64.frac * (1.0 / a.iaw) / c64.rt : 0.0;
+                st_pref = cell_pref(a, c64);
             }
             const int from = LC * (ibz & 3) + c;
             const double rt = __shfl(st_rt, from, kWave), ux = __shfl(st_ux, from, kWave), uy = __shfl(st_uy, from, kWave),
@@ -472,19 +479,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             }
         }
     }
-    if (a.change) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sum_change += __shfl_xor(sum_change, off, kWave);
-            sum_abs += __shfl_xor(sum_abs, off, kWave);
-        }
-        if (lane == 0) {
-            atomicAdd(&a.change[0], sum_change);
-            atomicAdd(&a.change[1], sum_abs);
-        }
-    }
+    report_change(a, lane, sum_change, sum_abs);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // main.cu:334-349 (commented out there): edepavg[i][j][k] = (27 haloed cells around node (i,j,k)) / 27,

@@ -84,10 +84,10 @@ __global__ void __launch_bounds__(256) k_step_table(const StepTableArgs a)
         const long ij = idx / a.nz;
         const int j = (int)(ij % a.ny);
         const int i = (int)(ij / a.ny);
-        // launch_ray_XZ.cu:212-238 : neighbours this+-1, one-sided on the faces (0 -> (0, 2), n-1 -> (n-3, n-1))
-        const long oxm = (i == 0) ? 0 : ((i == a.nx - 1) ? -2 * sX : -sX), oxp = (i == 0) ? 2 * sX : ((i == a.nx - 1) ? 0 : sX);
-        const long oym = (j == 0) ? 0 : ((j == a.ny - 1) ? -2 * sY : -sY), oyp = (j == 0) ? 2 * sY : ((j == a.ny - 1) ? 0 : sY);
-        const long ozm = (k == 0) ? 0 : ((k == a.nz - 1) ? -2 : -1), ozp = (k == 0) ? 2 : ((k == a.nz - 1) ? 0 : 1);
+        long oxm, oxp, oym, oyp, ozm, ozp;                           // :212-238
+        face_pair(i, a.nx, oxm, oxp, sX);
+        face_pair(j, a.ny, oym, oyp, sY);
+        face_pair(k, a.nz, ozm, ozp);
         StepRecord r;
         r.kx = a.xconst * (a.ne3d[idx + oxp] - a.ne3d[idx + oxm]);   // :268
         r.ky = a.yconst * (a.ne3d[idx + oyp] - a.ne3d[idx + oym]);   // :269
@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) k_step_table(const StepTableArgs a)
 // node_plasma for the tile's nodes (and, for planes of its own chunk, ne alone for the one-node cross halo in y and z)
 // into slot p % 3 of a three-plane LDS ring, writes ne3d / kappa3d for its own nodes, and -- as soon as the plane on
 // the far side of a node is in the ring -- forms the node's record from LDS with k_step_table's operands:
-// c * (ne(+1) - ne(-1)), one-sided on the faces (launch_ray_XZ.cu:212-226, 268-270: 0 -> (0, 2), n-1 -> (n-3, n-1)).
+// c * (ne(+1) - ne(-1)), one-sided on the faces (launch_ray_XZ.cu:212-226, 268-270: face_pair).
 // Tiles are CLAMPED into the grid (a partial last tile overlaps its neighbour and writes the same values again), so a
 // face node's one-sided pair (n-3, n-1) always lies in its own tile; planes 0 and nx-1 are emitted together with their
 // neighbours (at p = 2 and p = nx-1), when the ring holds both planes of their pair.
@@ -153,13 +153,14 @@ __global__ void __launch_bounds__(kPrThreads) k_plasma_records(const PlasmaRecor
             if (j >= ny || k >= nz) continue;
             const int c = (jr + 1) * kPrPZ + kr + 1;
             double v0, v1;
+            int m, p;
             if ((q & 1) == 0) {
-                const int ym = (j == 0) ? 0 : ((j == ny - 1) ? -2 : -1), yp = (j == 0) ? 2 : ((j == ny - 1) ? 0 : 1);
+                face_pair(j, ny, m, p);
                 v0 = a.xconst * (hi[c] - lo[c]);                                 // :268
-                v1 = a.yconst * (mid[c + yp * kPrPZ] - mid[c + ym * kPrPZ]);     // :269
+                v1 = a.yconst * (mid[c + p * kPrPZ] - mid[c + m * kPrPZ]);       // :269
             } else {
-                const int zm = (k == 0) ? 0 : ((k == nz - 1) ? -2 : -1), zp = (k == 0) ? 2 : ((k == nz - 1) ? 0 : 1);
-                v0 = a.zconst * (mid[c + zp] - mid[c + zm]);                     // :270
+                face_pair(k, nz, m, p);
+                v0 = a.zconst * (mid[c + p] - mid[c + m]);                       // :270
                 v1 = kap[n];
             }
             const long idx = ((long)i * ny + j) * nz + k;
@@ -336,11 +337,9 @@ __global__ void __launch_bounds__(kWave) k_trace_simple(const TraceArgs a)
     const bool absorb = a.absorption == 1;
 
     Ray s;
-    const int li = patch * kWave + lane;
-    const int pre_raynum = li < a.nlive ? a.live[li] : -1;  // -1: hole in the 8x8 patch
-    bool alive = pre_raynum >= 0;
-    if (alive) alive = launch_ray(a, beam, pre_raynum, s);
-    const int launched = alive ? 1 : 0;
+    int li;
+    const bool launched = launch_lane(a, beam, patch, lane, s, li);
+    bool alive = launched;
 
     const int nx = a.nx, ny = a.ny, nz = a.nz;
     const long sY = nz, sX = (long)ny * nz;                       // node-table strides (elements)
@@ -360,25 +359,18 @@ __global__ void __launch_bounds__(kWave) k_trace_simple(const TraceArgs a)
         unsigned slot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, node[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         double wgt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (alive) {
-            // :212-238 neighbours of the current node, one-sided on the faces
-            const int im = (s.ci == 0) ? 0 : ((s.ci == nx - 1) ? nx - 3 : s.ci - 1);
-            const int ip = (s.ci == 0) ? 2 : ((s.ci == nx - 1) ? nx - 1 : s.ci + 1);
-            const int jm = (s.cj == 0) ? 0 : ((s.cj == ny - 1) ? ny - 3 : s.cj - 1);
-            const int jp = (s.cj == 0) ? 2 : ((s.cj == ny - 1) ? ny - 1 : s.cj + 1);
-            const int km = (s.ck == 0) ? 0 : ((s.ck == nz - 1) ? nz - 3 : s.ck - 1);
-            const int kp = (s.ck == 0) ? 2 : ((s.ck == nz - 1) ? nz - 1 : s.ck + 1);
+            int im, ip, jm, jp, km, kp;                            // :212-238 neighbours of the current node, as offsets from it
+            face_pair(s.ci, nx, im, ip);
+            face_pair(s.cj, ny, jm, jp);
+            face_pair(s.ck, nz, km, kp);
             auto ne_at = [&](int i, int j, int k) { return node_load<true>(a, a.ne3d, (unsigned)(i * sX + j * sY + k), a.audit_nodes); };
-            // :254-273 six gathers, kick, drift
-            s.vx -= a.xconst * (ne_at(ip, s.cj, s.ck) - ne_at(im, s.cj, s.ck));
-            s.vy -= a.yconst * (ne_at(s.ci, jp, s.ck) - ne_at(s.ci, jm, s.ck));
-            s.vz -= a.zconst * (ne_at(s.ci, s.cj, kp) - ne_at(s.ci, s.cj, km));
-            s.px += s.vx * a.dt;
-            s.py += s.vy * a.dt;
-            s.pz += s.vz * a.dt;
-            // :276-292 position in cell units, nearest-node update (the literal loop)
-            const double fx = (s.px - a.xmin) * a.inv_dx;
-            const double fy = (s.py - a.ymin) * a.inv_dy;
-            const double fz = (s.pz - a.zmin) * a.inv_dz;
+            // :254-278 six gathers, kick, drift, position in cell units
+            s.vx -= a.xconst * (ne_at(s.ci + ip, s.cj, s.ck) - ne_at(s.ci + im, s.cj, s.ck));
+            s.vy -= a.yconst * (ne_at(s.ci, s.cj + jp, s.ck) - ne_at(s.ci, s.cj + jm, s.ck));
+            s.vz -= a.zconst * (ne_at(s.ci, s.cj, s.ck + kp) - ne_at(s.ci, s.cj, s.ck + km));
+            double fx, fy, fz;
+            drift(a, s, fx, fy, fz);
+            // :282-292 nearest-node update (the literal loop)
             s.ci = relocate_loop(s.ci, fx, nx);
             s.cj = relocate_loop(s.cj, fy, ny);
             s.ck = relocate_loop(s.ck, fz, nz);
@@ -416,21 +408,15 @@ __global__ void __launch_bounds__(kWave) k_trace_simple(const TraceArgs a)
             ++nsteps;
         }
         if (DEPOSIT == 2) lds_deposit8<WL>(tagged, alive, slot, node, wgt, edep, n_evict);
-        if (alive) {                                               // :351-356
-            const double *b = a.bounds;  // {xlo, xhi, ylo, yhi, zlo, zhi}
-            if (s.uray <= s.ustop || s.px < b[0] || s.px > b[1] || s.py < b[2] || s.py > b[3] || s.pz < b[4] || s.pz > b[5])
-                alive = false;
-        }
+        if (alive && stop_test(s, a.bounds) != 0) alive = false;   // :351-356
     }
     if (DEPOSIT == 2) {
         __syncthreads();
         n_atomics += tagged.flush(lane, edep) + n_evict;
     }
-    const int tot_steps = wave_sum(nsteps), tot_rays = wave_sum(launched), tot_at = wave_sum(n_atomics),
-              tot_ev = wave_sum(n_evict);
+    count_steps_and_rays(a, lane, nsteps, launched);
+    const int tot_at = wave_sum(n_atomics), tot_ev = wave_sum(n_evict);
     if (lane == 0) {
-        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
-        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
         atomicAdd(&a.counters[kCntGlobalAtomics], (unsigned long long)tot_at);
         atomicAdd(&a.counters[kCntEvictions], (unsigned long long)tot_ev);
         atomicAdd(&a.counters[kCntWaveSteps], (unsigned long long)wave_steps);

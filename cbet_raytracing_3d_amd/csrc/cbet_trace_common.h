@@ -1,5 +1,5 @@
-// cbet_trace_common.h -- device helpers shared by the ray-integrator kernels (cbet_kernels.hip: the two
-// cross-check formulations; cbet_trace_window.hip: the shipped one).  Citations are into /root/reference/.
+// cbet_trace_common.h -- what the ray-integrator kernels share, each piece of a ray step stated once (cbet_kernels.hip: the two
+// cross-check formulations; cbet_trace_window.hip: the shipped one; cbet_trace_exit.hip: the exit pass).  Citations are into /root/reference/.
 // Everything here is compiled with -ffp-contract=off: one IEEE operation per reference statement.
 #ifndef CBET_TRACE_COMMON_H_
 #define CBET_TRACE_COMMON_H_
@@ -124,6 +124,38 @@ __device__ __forceinline__ bool launch_ray(const TraceArgs &a, int beam, int pre
     return true;
 }
 
+// The bundle prologue of every integrator: the lane takes slot li of the launch list (whole bundles: the test against its
+// end is a guard only); -1 there is a hole in the 8x8 patch.  False for a hole and for a ray culled at :114.
+__device__ __forceinline__ bool launch_lane(const TraceArgs &a, int beam, int patch, int lane, Ray &s, int &li)
+{
+    li = patch * kWave + lane;
+    const int pre_raynum = li < a.nlive ? a.live[li] : -1;
+    return pre_raynum >= 0 && launch_ray(a, beam, pre_raynum, s);
+}
+
+// launch_ray_XZ.cu:212-238 -- the two nodes whose ne difference kicks a ray at node c of an axis of n nodes, as offsets from
+// c in units of `stride`: this -+ 1, one-sided on the faces (0 -> (0, 2), n-1 -> (n-3, n-1)).  Table kernels and k_trace_simple.
+template <class T = int> __device__ __forceinline__ void face_pair(int c, int n, T &m, T &p, T stride = 1)
+{
+    m = (c == 0) ? 0 : ((c == n - 1) ? -2 * stride : -stride);
+    p = (c == 0) ? 2 * stride : ((c == n - 1) ? 0 : stride);
+}
+
+// launch_ray_XZ.cu:271-278 -- drift with the kicked velocity, then the position in cell units.
+__device__ __forceinline__ void drift(const TraceArgs &a, Ray &s, double &fx, double &fy, double &fz)
+{
+    s.px += s.vx * a.dt; s.py += s.vy * a.dt; s.pz += s.vz * a.dt;
+    fx = (s.px - a.xmin) * a.inv_dx; fy = (s.py - a.ymin) * a.inv_dy; fz = (s.pz - a.zmin) * a.inv_dz;
+}
+
+// launch_ray_XZ.cu:351-356 -- the stop test's two conditions as status bits: the energy cut-off (CBET_RAY_CUTOFF), a position
+// outside the six exit planes b = {xlo, xhi, ylo, yhi, zlo, zhi} of TraceArgs::bounds (CBET_RAY_ESCAPED).  0: the ray goes on.
+__device__ __forceinline__ int stop_test(const Ray &s, const double *b)
+{
+    const bool out = s.px < b[0] || s.px > b[1] || s.py < b[2] || s.py > b[3] || s.pz < b[4] || s.pz > b[5];
+    return (s.uray <= s.ustop ? CBET_RAY_CUTOFF : 0) | (out ? CBET_RAY_ESCAPED : 0);
+}
+
 // Bounds-audited build (tests/test_gpu_bounds_audit.py, -DCBET_DEBUG_BOUNDS): every grid atomic, node-table
 // gather and LDS accumulate is range-checked against the limits the launch put into TraceArgs; a violation
 // is counted and the access skipped.  Never shipped.
@@ -154,6 +186,15 @@ __device__ __forceinline__ int wave_sum(int v)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+// Ray-steps and rays of a bundle into the device counters: one atomic per wave and counter.
+__device__ __forceinline__ void count_steps_and_rays(const TraceArgs &a, int lane, int steps, bool launched)
+{
+    const int tot_steps = wave_sum(launched ? steps : 0), tot_rays = wave_sum(launched ? 1 : 0);
+    if (lane == 0) {
+        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
+        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
+    }
 }
 
 // 8-byte gather from a node table, or from a beam's haloed gain grid (CBET hooks), by 32-bit element index: uniform base +
@@ -243,6 +284,51 @@ __device__ __forceinline__ double sqrt_speed(double v2)
     g = __builtin_fma(__builtin_fma(-g, g, v2), h, g);
     return __builtin_fma(__builtin_fma(-g, g, v2), h, g);
 }
+
+// ---- the CBET hook of a step: k_trace_window<., ., CBET >= 1> (the deposit passes) and k_trace_exit<true, .> (the exit pass)
+// both call the three functions below, so a ray's exit energy is what the deposition pass leaves it by construction
+// The two factors of an axis are d = 1 - |o| and 1 - d (:329-336); which of them comes first is the lane's
+// flip bit.  Without selects: F0 = +-(|o| - h), h = 1.0 with the sign flipped for a flipped lane (exactly
+// d), h = 0.0 otherwise (|o| itself: the reference's 1 - (1 - |o|) up to 1.1e-16), F1 = 1 - F0 (exactly
+// 1 - d, or exactly d).  Three instructions and one conversion per axis instead of six.
+__device__ __forceinline__ void factor_pair(double o, int flip, double &f0, double &f1)
+{
+    const double g = fabs(o) - (double)flip;
+    f0 = __hiloint2double(__double2hiint(g) ^ (flip << 31), __double2loint(g));
+    f1 = 1.0 - f0;
+}
+
+// The clamped exponent K ds of a step: K at the lane's eight deposit nodes X0..Z1 (haloed) of gain grid gk, weighted like the deposit (factor_pair's
+// F), times the path length ds.  The pairwise tree makes the sum independent of the corner order (the flips swap operands of commutative adds only).
+template <bool IDX64>
+__device__ __forceinline__ double gain_exponent(const TraceArgs &a, const double *gk, int X0, int X1, int Y0, int Y1, int Z0, int Z1, double Fx0,
+                                                double Fx1, double Fy0, double Fy1, double Fz0, double Fz1, int sXh, int sYh, double ds)
+{
+    const int nX0 = __mul24(X0, sXh), nX1 = __mul24(X1, sXh), nY0 = __mul24(Y0, sYh), nY1 = __mul24(Y1, sYh);
+    // The two z nodes of an (x, y) column are neighbours in memory: FOUR 16-byte gathers instead of eight 8-byte
+    // ones.  The column sums take the z factors by node (lower, upper), so nothing depends on the lane's z flip;
+    // the x and y flips swap operands of commutative adds.
+    const bool z0_low = Z0 < Z1;
+    const int zl = z0_low ? Z0 : Z1;
+    const double fz_lo = z0_low ? Fz0 : Fz1, fz_hi = z0_low ? Fz1 : Fz0;
+    const gain_pair_t c00 = gain_load2<IDX64>(a, gk, (unsigned)(nX0 + nY0 + zl)), c10 = gain_load2<IDX64>(a, gk, (unsigned)(nX1 + nY0 + zl));
+    const gain_pair_t c01 = gain_load2<IDX64>(a, gk, (unsigned)(nX0 + nY1 + zl)), c11 = gain_load2<IDX64>(a, gk, (unsigned)(nX1 + nY1 + zl));
+    // Fused multiply-adds, z then x then y: 14 operations for the 23 of the unfused pairwise tree the CPU checker
+    // evaluates (a relative 1e-16 per term; the kernels are held to the checker at 1e-9).  The sum does not depend
+    // on the corner order beyond that: the flips swap which of two products is the addend.
+    const double q00 = __builtin_fma(fz_hi, c00.y, fz_lo * c00.x), q10 = __builtin_fma(fz_hi, c10.y, fz_lo * c10.x);
+    const double q01 = __builtin_fma(fz_hi, c01.y, fz_lo * c01.x), q11 = __builtin_fma(fz_hi, c11.y, fz_lo * c11.x);
+    const double r0 = __builtin_fma(Fx1, q10, Fx0 * q00), r1 = __builtin_fma(Fx1, q11, Fx0 * q01);
+    const double ksum = __builtin_fma(Fy1, r1, Fy0 * r0);
+    double x = ksum * ds;
+    if (x > a.max_exponent) x = a.max_exponent;
+    if (x < -a.max_exponent) x = -a.max_exponent;
+    return x;
+}
+
+// phi(x) of the hook by the wave's vote (the caller's ballot, masked with ITS live lanes): phi_small when every live lane's |x| < kPhiSmallBelow
+constexpr double kPhiSmallBelow = 0.03125;
+__device__ __forceinline__ double gain_phi(double x, bool wave_is_small) { return wave_is_small ? phi_small(x) : phi_det(x); }
 
 // The work item of workgroup `w` of a launch: which (beam, patch) bundle.  The list is beam-major -- consecutive
 // workgroups are neighbouring patches of one beam and share table lines in L2/MALL -- with each beam's patches

@@ -7,8 +7,8 @@
 //     arithmetic, operation for operation (/root/reference/launch_ray_XZ.cu:207-357, built with -ffp-contract=off):
 //     kick from the step record of its node, drift, nearest-node update (cbet_relocate.h relocate_closed), absorption,
 //     the stop test of :351-356.  When the ray ends -- in the step where that test first holds, or after nt steps --
-//     its lane writes one cbet_ray_exit record.  GAIN: the CBET hook of k_trace_window<16, ., 1> (cbet_trace_window.hip,
-//     the `if (gk)` block) before the absorption, so that a ray's exit energy is what the CBET deposition pass leaves it.
+//     its lane writes one cbet_ray_exit record.  GAIN: the CBET hook of k_trace_window<16, ., 1> -- that kernel's own code,
+//     cbet_trace_common.h -- before the absorption, so that a ray's exit energy is what the CBET deposition pass leaves it.
 //   * k_exit_tally  : per-beam energy balance of the records, one workgroup per beam, fixed summation order (no atomics:
 //     bit-reproducible from run to run).
 //   * k_farfield    : the escaped rays' energy binned by exit direction (equal solid angle per polar bin), ADDED into a
@@ -38,16 +38,6 @@ __device__ __forceinline__ StepRecord load_record(const TraceArgs &a, unsigned c
     return *reinterpret_cast<const StepRecord *>(reinterpret_cast<const char *>(a.steprec) + (cell << 5));
 }
 
-// An axis's two deposit factors in the shipped kernel's lane-dependent order (cbet_trace_window.hip, `pair`): F0 = |o|
-// for an unflipped lane, 1 - |o| for a flipped one; F1 = 1 - F0.  The gain sum below then rounds exactly as the
-// shipped CBET kernel's does for the same lane.
-__device__ __forceinline__ void factor_pair(double o, int flip, double &f0, double &f1)
-{
-    const double g = fabs(o) - (double)flip;
-    f0 = __hiloint2double(__double2hiint(g) ^ (flip << 31), __double2loint(g));
-    f1 = 1.0 - f0;
-}
-
 template <bool GAIN, bool IDX64>
 __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
 {
@@ -55,17 +45,13 @@ __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
     int beam, patch;
     if (!work_item(a, blockIdx.x, beam, patch)) return;   // wave-uniform
 
-    const int li = patch * kWave + lane;
-    const bool has_slot = li < a.nlive;                   // the list is whole bundles; this is a guard only
-    const int pre_raynum = has_slot ? a.live[li] : -1;   // -1: idle lane of the bundle
     Ray s = {};
-    bool launched = pre_raynum >= 0;
-    if (launched) launched = launch_ray(a, beam, pre_raynum, s);
+    int li;
+    const bool launched = launch_lane(a, beam, patch, lane, s, li);
+    const bool has_slot = li < a.nlive;                   // (a record for every slot of the list, idle lanes' too)
     const double uray0 = s.uray;                          // :113
 
     const int nx = a.nx, ny = a.ny, nz = a.nz;
-    const double xlo = a.bounds[0], xhi = a.bounds[1], ylo = a.bounds[2], yhi = a.bounds[3], zlo = a.bounds[4],
-                 zhi = a.bounds[5];
     StepRecord rec = {0.0, 0.0, 0.0, 0.0};
     if (launched) rec = load_record<IDX64>(a, (unsigned)((s.ci * ny + s.cj) * nz + s.ck));   // :254-270 at the launch node
 
@@ -81,24 +67,20 @@ __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;
         double x = 0.0;                                   // GAIN: the clamped exponent K ds of the step
         if (alive) {
-            // :268-273 kick, drift
+            // :268-278 kick, drift, position in cell units
             s.vx -= rec.kx;
             s.vy -= rec.ky;
             s.vz -= rec.kz;
-            s.px += s.vx * a.dt;
-            s.py += s.vy * a.dt;
-            s.pz += s.vz * a.dt;
-            // :276-292 position in cell units, nearest-node update
-            const double fx = (s.px - a.xmin) * a.inv_dx;
-            const double fy = (s.py - a.ymin) * a.inv_dy;
-            const double fz = (s.pz - a.zmin) * a.inv_dz;
+            double fx, fy, fz;
+            drift(a, s, fx, fy, fz);
+            // :282-292 nearest-node update
             s.ci = relocate_closed(s.ci, fx, nx);
             s.cj = relocate_closed(s.cj, fy, ny);
             s.ck = relocate_closed(s.ck, fz, nz);
             // :296-305 the absorption coefficient now, the kicks of the next step
             rec = load_record<IDX64>(a, (unsigned)((s.ci * ny + s.cj) * nz + s.ck));
             if (GAIN) {
-                // K at the eight deposit nodes with the deposit weights (:319-339), as k_trace_window<16, ., 1> gathers it
+                // K at the eight deposit nodes with the deposit weights (:319-339)
                 const double ox = (fx - (double)s.ci) - 0.5, oy = (fy - (double)s.cj) - 0.5, oz = (fz - (double)s.ck) - 0.5;
                 const bool ngx = ox < 0, ngy = oy < 0, ngz = oz < 0;
                 const int lx = s.ci + 1 - (ngx ? 1 : 0), ly = s.cj + 1 - (ngy ? 1 : 0), lz = s.ck + 1 - (ngz ? 1 : 0);
@@ -111,26 +93,13 @@ __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
                 factor_pair(oy, pfy, Fy0, Fy1);
                 factor_pair(oz, pfz, Fz0, Fz1);
                 const double ds = sqrt_speed(__builtin_fma(s.vz, s.vz, __builtin_fma(s.vy, s.vy, s.vx * s.vx))) * a.dt;
-                const int nX0 = X0 * sXh, nX1 = X1 * sXh, nY0 = Y0 * sYh, nY1 = Y1 * sYh;
-                const bool z0_low = Z0 < Z1;
-                const int zl = z0_low ? Z0 : Z1;
-                const double fz_lo = z0_low ? Fz0 : Fz1, fz_hi = z0_low ? Fz1 : Fz0;
-                const gain_pair_t c00 = gain_load2<IDX64>(a, gk, (unsigned)(nX0 + nY0 + zl)), c10 = gain_load2<IDX64>(a, gk, (unsigned)(nX1 + nY0 + zl));
-                const gain_pair_t c01 = gain_load2<IDX64>(a, gk, (unsigned)(nX0 + nY1 + zl)), c11 = gain_load2<IDX64>(a, gk, (unsigned)(nX1 + nY1 + zl));
-                const double q00 = __builtin_fma(fz_hi, c00.y, fz_lo * c00.x), q10 = __builtin_fma(fz_hi, c10.y, fz_lo * c10.x);
-                const double q01 = __builtin_fma(fz_hi, c01.y, fz_lo * c01.x), q11 = __builtin_fma(fz_hi, c11.y, fz_lo * c11.x);
-                const double r0 = __builtin_fma(Fx1, q10, Fx0 * q00), r1 = __builtin_fma(Fx1, q11, Fx0 * q01);
-                const double ksum = __builtin_fma(Fy1, r1, Fy0 * r0);
-                x = ksum * ds;
-                if (x > a.max_exponent) x = a.max_exponent;
-                if (x < -a.max_exponent) x = -a.max_exponent;
+                x = gain_exponent<IDX64>(a, gk, X0, X1, Y0, Y1, Z0, Z1, Fx0, Fx1, Fy0, Fy1, Fz0, Fz1, sXh, sYh, ds);
             }
         }
         if (GAIN) {
-            // the shipped kernel's wave-wide choice of the series: the short one when every live lane's |x| is small
-            const bool small = __builtin_amdgcn_ballot_w64(alive && !(fabs(x) < 0.03125)) == 0ull;
+            const bool small = __builtin_amdgcn_ballot_w64(alive && !(fabs(x) < kPhiSmallBelow)) == 0ull;
             if (alive) {
-                const double phi = small ? phi_small(x) : phi_det(x);
+                const double phi = gain_phi(x, small);
                 const double dg = s.uray * (x * phi);
                 gained += dg;
                 s.uray = s.uray + dg;
@@ -139,12 +108,11 @@ __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
         if (alive) {
             s.uray -= rec.kap * s.uray;                   // :305-311 (absorbing mode only: checked on the host)
             // :351-356 the stop test; the record says which of its conditions held
-            const bool cut = s.uray <= s.ustop;
-            const bool out = s.px < xlo || s.px > xhi || s.py < ylo || s.py > yhi || s.pz < zlo || s.pz > zhi;
-            if (cut || out) {
+            const int end = stop_test(s, a.bounds);
+            if (end != 0) {
                 alive = false;
                 steps = tt + 1;
-                status = CBET_RAY_LAUNCHED | (cut ? CBET_RAY_CUTOFF : 0) | (out ? CBET_RAY_ESCAPED : 0);
+                status = CBET_RAY_LAUNCHED | end;
             }
         }
     }
@@ -172,11 +140,7 @@ __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
         *dst = e;
     }
 
-    const int tot_steps = wave_sum(launched ? steps : 0), tot_rays = wave_sum(launched ? 1 : 0);
-    if (lane == 0) {
-        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
-        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
-    }
+    count_steps_and_rays(a, lane, steps, launched);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -651,10 +651,8 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     const bool absorb = GENERIC ? (a.absorption == 1) : true;   // def.cuh:118
 
     Ray s = {};   // holes and culled rays keep zeros: their lanes run the arithmetic below on harmless values
-    const int li = patch * kWave + lane;
-    const int pre_raynum = li < a.nlive ? a.live[li] : -1;  // -1: hole in the 8x8 patch
-    bool launched = pre_raynum >= 0;
-    if (launched) launched = launch_ray(a, beam, pre_raynum, s);
+    int li;
+    const bool launched = launch_lane(a, beam, patch, lane, s, li);
     unsigned long long live = __ballot(launched);
     if (live == 0ull) return;  // whole bundle culled (cannot happen for a listed patch; cheap guard)
     const int tot_rays = __popcll(live);
@@ -1067,20 +1065,9 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             restart_m = fl_m;
             p_odd = !all_negative;
         }
-        {
-            // The two factors of an axis are d = 1 - |o| and 1 - d (:329-336); which of them comes first is the lane's
-            // flip bit.  Without selects: F0 = +-(|o| - h), h = 1.0 with the sign flipped for a flipped lane (exactly
-            // d), h = 0.0 otherwise (|o| itself: the reference's 1 - (1 - |o|) up to 1.1e-16), F1 = 1 - F0 (exactly
-            // 1 - d, or exactly d).  Three instructions and one conversion per axis instead of six.
-            auto pair = [](double o, int flip, double &f0, double &f1) {
-                const double g = fabs(o) - (double)flip;
-                f0 = __hiloint2double(__double2hiint(g) ^ (flip << 31), __double2loint(g));
-                f1 = 1.0 - f0;
-            };
-            pair(ox, pfx, Fx0, Fx1);
-            pair(oy, pfy, Fy0, Fy1);
-            pair(oz, pfz, Fz0, Fz1);
-        }
+        factor_pair(ox, pfx, Fx0, Fx1);
+        factor_pair(oy, pfy, Fy0, Fy1);
+        factor_pair(oz, pfz, Fz0, Fz1);
         // the lane's low corner (haloed) relative to box A's origin: what the common case tests; the corner itself is
         // rebuilt from it where a box has to move (as a value of its own it costs three copies per step)
         int rx, ry, rz;
@@ -1112,29 +1099,9 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             if (gk || CBET >= 2) ds = sqrt_speed(__builtin_fma(s.vz, s.vz, __builtin_fma(s.vy, s.vy, s.vx * s.vx))) * a.dt;
             double u_eff = s.uray;
             if (gk) {
-                // K at the eight deposit nodes, weighted like the deposit.  The pairwise tree makes the
-                // sum independent of the corner order (the flips swap operands of commutative adds only).
-                const int nX0 = __mul24(X0, sXh), nX1 = __mul24(X1, sXh), nY0 = __mul24(Y0, sYh), nY1 = __mul24(Y1, sYh);
-                // The two z nodes of an (x, y) column are neighbours in memory: FOUR 16-byte gathers instead of eight 8-byte
-                // ones.  The column sums take the z factors by node (lower, upper), so nothing depends on the lane's z flip;
-                // the x and y flips swap operands of commutative adds.
-                const bool z0_low = Z0 < Z1;
-                const int zl = z0_low ? Z0 : Z1;
-                const double fz_lo = z0_low ? Fz0 : Fz1, fz_hi = z0_low ? Fz1 : Fz0;
-                const gain_pair_t c00 = gain_load2<IDX64>(a, gk, (unsigned)(nX0 + nY0 + zl)), c10 = gain_load2<IDX64>(a, gk, (unsigned)(nX1 + nY0 + zl));
-                const gain_pair_t c01 = gain_load2<IDX64>(a, gk, (unsigned)(nX0 + nY1 + zl)), c11 = gain_load2<IDX64>(a, gk, (unsigned)(nX1 + nY1 + zl));
-                // Fused multiply-adds, z then x then y: 14 operations for the 23 of the unfused pairwise tree the CPU checker
-                // evaluates (a relative 1e-16 per term; the kernels are held to the checker at 1e-9).  The sum does not depend
-                // on the corner order beyond that: the flips swap which of two products is the addend.
-                const double q00 = __builtin_fma(fz_hi, c00.y, fz_lo * c00.x), q10 = __builtin_fma(fz_hi, c10.y, fz_lo * c10.x);
-                const double q01 = __builtin_fma(fz_hi, c01.y, fz_lo * c01.x), q11 = __builtin_fma(fz_hi, c11.y, fz_lo * c11.x);
-                const double r0 = __builtin_fma(Fx1, q10, Fx0 * q00), r1 = __builtin_fma(Fx1, q11, Fx0 * q01);
-                const double ksum = __builtin_fma(Fy1, r1, Fy0 * r0);
-                double x = ksum * ds;
-                if (x > a.max_exponent) x = a.max_exponent;
-                if (x < -a.max_exponent) x = -a.max_exponent;
+                const double x = gain_exponent<IDX64>(a, gk, X0, X1, Y0, Y1, Z0, Z1, Fx0, Fx1, Fy0, Fy1, Fz0, Fz1, sXh, sYh, ds);
                 // (dead lanes excluded from the vote: a.max_exponent bounds |x|, not the garbage a dead lane carries)
-                const double phi = (CBET_BALLOT(!(fabs(x) < 0.03125)) & live) == 0ull ? phi_small(x) : phi_det(x);
+                const double phi = gain_phi(x, (CBET_BALLOT(!(fabs(x) < kPhiSmallBelow)) & live) == 0ull);
                 const double dg = s.uray * (x * phi);
                 u_eff = s.uray * phi;
                 gained += dg;

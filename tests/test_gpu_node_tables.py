@@ -1,7 +1,8 @@
 """The three device paths that fill a context's plain node tables -- k_tabulate (cbet_tabulate_plasma), k_plasma_records
 (cbet_prepare_plasma) and k_tabulate_target with a zero target (cbet_tabulate_target) -- on a DESCENDING profile: the
 reversed s83177 arrays take the other branch of the shared bracket's clamp tests and go-low rule (csrc/cbet_node_model.h).
-Each path's tables equal the host twin's bit for bit, and the fused kernel's records equal k_step_table's.  No trace."""
+Each path's tables equal the host twin's bit for bit, and the fused kernel's records equal k_step_table's.  And on any
+profile the records of both paths equal the reference's stencil with its edge rule, restated here in numpy.  No trace."""
 import numpy as np
 import pytest
 
@@ -76,3 +77,57 @@ def test_descending_profile_fills_equal_the_host_twin_bitwise(api, inputs, torch
     torch_cuda.cuda.synchronize()
     check("tabulate_target", context_tables(api, ctx, p, 0))
     ctx.close()
+
+
+def _reference_stencil(ne, consts):
+    """launch_ray_XZ.cu:212-238, 268-270 restated in numpy: per axis const * (ne[plus] - ne[minus]) with (minus, plus) =
+    (c - 1, c + 1), one-sided on the faces: (0, 2) at 0 and (n - 3, n - 1) at n - 1.  One IEEE subtraction and one
+    multiplication per word, as on the device (built without fused multiply-adds): [nx, ny, nz, 3]."""
+    kicks = []
+    for axis, const in enumerate(consts):
+        n = ne.shape[axis]
+        c = np.arange(n)
+        minus = np.where(c == 0, 0, np.where(c == n - 1, n - 3, c - 1))
+        plus = np.where(c == 0, 2, np.where(c == n - 1, n - 1, c + 1))
+        kicks.append(np.float64(const) * (np.take(ne, plus, axis) - np.take(ne, minus, axis)))
+    return np.stack(kicks, axis=-1)
+
+
+# Every axis is 3 nodes long once -- there (0, 2) and (n - 3, n - 1) are the same pair and a wrong branch of the rule picks
+# a node outside it -- and 70 long once: more than one k_plasma_records tile or chunk (64 in z, 8 in y, 16 in x).
+@pytest.mark.parametrize("shape", [(3, 9, 70), (70, 3, 9), (9, 70, 3)], ids=["3x9x70", "70x3x9", "9x70x3"])
+def test_step_records_equal_the_reference_stencil(api, inputs, torch_cuda, shape):
+    _, r, ne, te = inputs
+    p = api.default_params(shape[0], nbeams=4)
+    p.ny, p.nz = shape[1], shape[2]
+    d = api.derive(p)
+    d_r, d_ne, d_te = (torch_cuda.from_numpy(np.ascontiguousarray(v)).cuda() for v in (r, ne, te))
+    stream = torch_cuda.cuda.current_stream().cuda_stream
+    n = p.nx * p.ny * p.nz
+
+    def two(ctx):
+        api.tabulate_plasma(ctx, p, d_te, d_r, d_ne, stream)
+        api.prepare_step_records(ctx, p, None, None, d.xconst, d.yconst, d.zconst, stream)
+
+    def fused(ctx):
+        api.prepare_plasma(ctx, p, d_te, d_r, d_ne, d.xconst, d.yconst, d.zconst, stream)
+
+    face = np.zeros(shape, dtype=bool)
+    for axis in range(3):
+        for side in (0, -1):
+            sl = [slice(None)] * 3
+            sl[axis] = side
+            face[tuple(sl)] = True
+    for path, fill in (("tabulate_plasma + prepare_step_records", two), ("prepare_plasma", fused)):
+        ctx = api.Context(p, 0)
+        api.moveToAndFromGPU(ctx.step_records()[0], np.full(4 * n, np.nan), 8 * 4 * n, 0)   # a fill that wrote nothing fails
+        fill(ctx)
+        torch_cuda.cuda.synchronize()
+        ne3d, kap3d, rec = context_tables(api, ctx, p, 0, records=True, bits=False)
+        ctx.close()
+        want = np.concatenate([_reference_stencil(ne3d, (d.xconst, d.yconst, d.zconst)), kap3d[..., None]], axis=-1)
+        diff = rec.view(np.int64) != want.view(np.int64)
+        print("%s %s: %d of %d record words differ; non-zero kicks on the faces: %s" % (
+            shape, path, int(diff.sum()), diff.size, [int((rec[face][:, c] != 0).sum()) for c in range(3)]))
+        assert not diff.any(), (path, np.argwhere(diff)[:5].tolist())
+        assert (rec[face][:, :3] != 0).any(), path
