@@ -608,6 +608,11 @@ constexpr bool kDiagFaces = true;
 #else
 constexpr bool kDiagFaces = false;
 #endif
+#ifdef CBET_DIAG_CHAIN
+constexpr bool kDiagChain = true;
+#else
+constexpr bool kDiagChain = false;
+#endif
 constexpr double kNearTol = 0.5001;   // launch_ray_XZ.cu:132, the nearest-node tolerance
 constexpr double kFarJump = 1.4998;   // relocate_deep_interior's validity bound on |f - cell|
 
@@ -691,18 +696,33 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     unsigned long long dg_wait = 0, dg_shift = 0, dg_nshift = 0, dg_t_start;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_t_start) : : "memory");
 #endif
+#ifdef CBET_DIAG_CHAIN
+    // diagnostic build (never shipped): shader-clock cycles of the dependent chain, from right behind the record wait to
+    // right behind the issue of the next gather (so that whatever the compiler puts in front of the gather is inside),
+    // summed per wave and reported through a counter slot (see the end of the kernel).  The two stamps and their waits
+    // cost time themselves: compare builds that carry the same stamps with each other only (scripts/diag_chain.py).
+    unsigned long long dg_c0 = 0, dg_chain = 0;
+#endif
 
     // A step's record (cbet_device.h StepRecord: the three kicks and the absorption coefficient at the ray's node) is
     // gathered as soon as the new node is known; the absorption coefficient is used at the end of the same step,
     // the kicks by the NEXT step's move.  One aligned 32-byte gather per lane and step.
     dbl2 rec_kxy, rec_kzk;                   // {kx, ky}, {kz, kappa} of the ray's node
+    // The table's base and the time step, RESIDENT: read as members of `a` the compiler rematerialises them -- the base by a
+    // scalar load of the argument segment and its lgkmcnt(0) wait right in front of every step's gather, the time step as
+    // three copies of one scalar pair, one per drift multiply.  Passed through an empty assembly statement each is one
+    // opaque value in scalar registers (the time step's stands at the top of the loop: in front of it the compiler still
+    // keeps a second copy for the third multiply).
+    const StepRecord *rec_base = a.steprec;
+    asm volatile("" : "+s"(rec_base));
+    double dt = a.dt;
     auto gather_record = [&]() {             // all lanes (a dead lane reads node 0); see record_issue
         unsigned c = CBET_LANES(live) ? cell : 0u;
         asm("" : "+v"(c));   // (keeps the select a 32-bit one, in front of the address arithmetic)
 #ifdef CBET_DEBUG_BOUNDS
         if (!(c < a.audit_nodes)) { audit_fail(a); c = 0u; }
 #endif
-        record_issue<IDX64>(a.steprec, c, rec_kxy, rec_kzk);
+        record_issue<IDX64>(rec_base, c, rec_kxy, rec_kzk);
         wc.pend = 0;
     };
     // The wait, counted: the vector-memory instructions the step really issued behind the gather (the window pass's
@@ -720,6 +740,9 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
 #ifdef CBET_DIAG_CLOCKS
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(t1) : "s"(t0) : "memory");
         dg_wait += t1 - t0;
+#endif
+#ifdef CBET_DIAG_CHAIN
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_c0) : : "memory");
 #endif
     };
     gather_record();
@@ -931,6 +954,9 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // ---- the rest of a step: wait for the record, absorb, add the deposit to the pending sums, end rays -------------
     auto step_tail = [&](int &tt) {
     // ---- absorption (:305-311) ---------------------------------------------------------------------
+    // (the six factors depend on the offsets only: pinned HERE they are formed in the gather's shadow; left alone the
+    // compiler sinks their nine instructions below the wait, in front of the next step's kick)
+    asm volatile("" : "+v"(Fx0), "+v"(Fx1), "+v"(Fy0), "+v"(Fy1), "+v"(Fz0), "+v"(Fz1));
     await_record();   // the record gathered after the relocation: kappa now, the kicks at the top of the next step
     if (absorb) {
         inc = rec_kzk.y * s.uray;
@@ -980,7 +1006,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     };
 
     for (int tt = 0; tt < a.nt; ++tt) {                        // :207  (live != 0 here: checked where lanes end)
-        if constexpr (STATS || kDiagClocks || kDiagFaces) wc.steps_miss += 1u << 16;
+        if constexpr (STATS || kDiagClocks || kDiagFaces || kDiagChain) wc.steps_miss += 1u << 16;
 #ifdef CBET_DIAG_FACES
         dg_near += near != 0 ? 1 : 0;
         dg_axes += __builtin_popcount((unsigned)near);
@@ -990,9 +1016,10 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         s.vx -= rec_kxy.x;
         s.vy -= rec_kxy.y;
         s.vz -= rec_kzk.x;
-        s.px += s.vx * a.dt;
-        s.py += s.vy * a.dt;
-        s.pz += s.vz * a.dt;
+        asm volatile("" : "+s"(dt));
+        s.px += s.vx * dt;
+        s.py += s.vy * dt;
+        s.pz += s.vz * dt;
         // :276-278 position in cell units
         const double fx = (s.px - a.xmin) * a.inv_dx;
         const double fy = (s.py - a.ymin) * a.inv_dy;
@@ -1029,9 +1056,17 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         cell = new_cell;
         // :296-298 absorption coefficient at the new node and the NEXT step's kicks
         gather_record();
+#ifdef CBET_DIAG_CHAIN
+        {
+            unsigned long long dg_c1;
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_c1) : "s"(dg_c0) : "memory");
+            dg_chain += dg_c1 - dg_c0;
+        }
+#endif
         // (everything below reads the cell through this barrier, i.e. is scheduled BEHIND the gather's issue: left alone the
-        // compiler puts the offsets' nine instructions in front of it, on the dependent chain)
-        asm volatile("" : "+v"(s.ci), "+v"(s.cj), "+v"(s.ck));
+        // compiler puts the offsets' nine instructions in front of it, on the dependent chain -- and, without `inc`, which
+        // every product of the pending deposit depends on, six of that deposit's fp64 multiplies)
+        asm volatile("" : "+v"(s.ci), "+v"(s.cj), "+v"(s.ck), "+v"(inc));
         fcx = (double)s.ci;
         fcy = (double)s.cj;
         fcz = (double)s.ck;
@@ -1251,6 +1286,15 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         atomicAdd(&a.counters[kCntSlabsRetired], dg_t_end - dg_t_start);
         atomicAdd(&a.counters[kCntRays], wc.dg_ret);              // (the ray count gives way to the write-backs' clocks ...)
         atomicAdd(&a.counters[kCntWaveStepsMiss], wc.dg_nret);    // (... and their number)
+    }
+    return;
+#endif
+#ifdef CBET_DIAG_CHAIN
+    if (lane == 0) {   // the diagnostic build reuses one slot: the chain's cycles
+        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
+        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
+        atomicAdd(&a.counters[kCntWaveSteps], (unsigned long long)(wc.steps_miss >> 16));
+        atomicAdd(&a.counters[kCntGlobalAtomics], dg_chain);
     }
     return;
 #endif
