@@ -1,45 +1,43 @@
 // cbet_trace_window.hip -- the shipped ray integrator for gfx950 (CDNA4): CBET_KERNEL_LDS_WINDOW.
 //
-// One wavefront (64 lanes, one workgroup) = one ray bundle = one 8x8-ray patch of a beam's cross
-// section.  Everything that decides where a ray goes and when it stops -- position, velocity, energy, cell --
-// is the reference's arithmetic, operation for operation (/root/reference/launch_ray_XZ.cu:207-357; the
-// file is built with -ffp-contract=off); the deposit is the reference's up to the last bits of its terms (14
-// products for 20, see `accumulate`).  What is MI355X-specific is everything around it:
+// One wavefront (64 lanes, one workgroup) = one ray bundle = one 8x8-ray patch of a beam's cross section.  Everything that
+// decides where a ray goes and when it stops -- position, velocity, energy, cell -- is the reference's arithmetic, operation
+// for operation (launch_ray_XZ.cu:207-357; the file is built with -ffp-contract=off); the deposit is the reference's up to
+// the last bits of its terms (14 products for 20, see `accumulate`).  What is MI355X-specific is everything around it:
 //
-//   * plasma: one 32-byte record per node (k_step_table: the three kicks with the reference's edge rule baked in,
-//     and the absorption coefficient), gathered once per step from inline assembly and waited for with a counted
-//     vmcnt (record_issue / record_wait); the loop is rotated so that the flush of the pending sums, this step's
-//     weights and the window logic all run between a gather and its wait.
-//   * relocation: for cells deep inside the grid the reference's mutating-bound candidate loop
-//     (:282-292) is a function of g = f - cell alone and every difference it forms is exact, so it is
-//     evaluated with two comparisons (cbet_relocate.h, relocate_deep_interior; fuzzed against the
-//     literal loop on the CPU).  Whether a wave is "deep inside" is decided on the SCALAR unit from the
-//     deposit windows' origins, AXIS BY AXIS (three bits): along an axis near a face the wave takes the closed form
-//     with the face rules and compares that axis's two exit planes -- scalar operands from the argument segment.
-//   * deposit: wave-private dense LDS tiles of fp64 accumulators ("boxes") whose origins follow the
-//     bundle.  A lane sums its ray's deposits in eight registers while the ray's eight target nodes stay the
-//     same; when they change it issues eight ds_add_f64 into its box (plain trace; the CBET kernels
-//     deposit every step).  The plane (or, along z, the 64-byte-aligned brick of 8 planes) that leaves a
-//     box when its origin moves is written back with global fp64 atomics -- z-bricks make every such
-//     atomic request a full 64-B line (the memory-side atomic path is priced per 64-B request,
-//     MI355X_MICROARCH.md "Global float atomics").  A second box adopts lanes that leave the first
-//     (bundles fan out after the turning point).  Corner order is lane-dependent so that rays sharing all
-//     8 nodes hit different LDS addresses in any one ds_add_f64; the first box stores its rows densely
-//     with a swizzled z index (Tile::zr), which spreads a bundle's nodes over the banks in 8 KB: with the second box
-//     10,240 B per wave, 16 waves per CU.
+//   * plasma: one 32-byte record per node (k_step_table: the three kicks with the reference's edge rule baked in, and the
+//     absorption coefficient), gathered once per step from inline assembly and waited for with a counted vmcnt
+//     (record_issue / record_wait); the loop is rotated so that the flush of the pending sums, this step's weights and the
+//     window logic all run between a gather and its wait.  What the wait may skip is counted where it is issued, in ONE
+//     place per kind: write_back, write_back_far, miss_add8.
+//   * relocation: for cells deep inside the grid the reference's mutating-bound candidate loop (:282-292) is a function of
+//     g = f - cell alone and every difference it forms is exact, so it is evaluated with two comparisons (cbet_relocate.h,
+//     relocate_deep_interior; fuzzed against the literal loop on the CPU).  Whether a wave is "deep inside" is decided on
+//     the SCALAR unit from the deposit windows' origins, AXIS BY AXIS (three bits): along an axis near a face the wave takes
+//     the closed form with the face rules and compares that axis's two exit planes -- scalar operands from the argument
+//     segment.
+//   * deposit: wave-private dense LDS tiles of fp64 accumulators ("boxes") whose origins follow the bundle.  A lane sums
+//     its ray's deposits in eight registers while the ray's eight target nodes stay the same; when they change it issues
+//     eight ds_add_f64 into its box (plain trace; the CBET kernels deposit every step).  The plane (or, along z, the
+//     64-byte-aligned brick of 8 planes) that leaves a box when its origin moves is written back with global fp64 atomics
+//     -- z-bricks make every such atomic request a full 64-B line (the memory-side atomic path is priced per 64-B request).
+//     A second box adopts lanes that leave the first (bundles fan out after the turning point).  The corner order (Corner)
+//     is lane-dependent so that rays sharing all 8 nodes hit different LDS addresses in any one ds_add_f64; the first box
+//     stores its rows densely with a swizzled z index (Tile::zr), which spreads a bundle's nodes over the banks in 8 KB:
+//     with the second box 10,240 B per wave, 16 waves per CU.
 //   * control: every lane predicate that steers the step is a 64-bit mask in scalar registers (live rays, box B's lanes,
-//     lanes outside both boxes, who moved, who flushes), combined with scalar instructions and turned into a lane
-//     condition only where lanes diverge (CBET_LANES); the loop's branches are all wave-uniform and the file is built
-//     with -mllvm -structurizecfg-skip-uniform-regions=true, so they stay plain branches (structurised, their flow
-//     blocks cost the common path ~40 scalar copies per step); one loop exit; the rare window arm works on copies and
-//     writes back through moves tied to the variables' registers (commit).
+//     lanes outside both boxes, who moved, who flushes), combined with scalar instructions and turned into a lane condition
+//     only where lanes diverge (CBET_LANES); the loop's branches are all wave-uniform and the file is built with -mllvm
+//     -structurizecfg-skip-uniform-regions=true, so they stay plain branches (structurised, their flow blocks cost the
+//     common path ~40 scalar copies per step); one loop exit; the rare window arm works on copies and writes back through
+//     moves tied to the variables' registers (commit).
+//   * diagnostics: the three diagnostic builds hang on one hook, WaveDiag (cbet_trace_diag.h), empty in shipped builds.
 //
-// Template parameters: WZ = z extent of a tile (16: aligned z-bricks; 8: single z-planes, used by the
-// CBET field pass whose three extra component tiles would not fit otherwise); GENERIC = run-time
-// absorption flag and 64-bit table indexing (grids of >= 2^32 table bytes, bookkeeping mode) instead
-// of the compiled-in common case; CBET = 0 none, 1 gain hooks, 2 gain hooks + the energy field deposited,
-// 4 fused four-component field pass (no reference counterpart: DESIGN.md section 9); STATS = also count
-// the deposit windows' diagnostics (cbet_params.window_stats).
+// Template parameters: WZ = z extent of a tile (16: aligned z-bricks; 8: single z-planes, used by the CBET field pass whose
+// three extra component tiles would not fit otherwise); GENERIC = run-time absorption flag and 64-bit table indexing (grids
+// of >= 2^32 table bytes, bookkeeping mode) instead of the compiled-in common case; CBET = 0 none, 1 gain hooks, 2 gain
+// hooks + the energy field deposited, 4 fused four-component field pass (no reference counterpart:
+// DESIGN.md section 9); STATS = also count the deposit windows' diagnostics (cbet_params.window_stats).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -52,11 +50,14 @@
 #endif
 
 #include "cbet_trace_common.h"
+#include "cbet_trace_diag.h"
 
 namespace cbet {
 namespace {
 
 #define CBET_BALLOT(cond) __builtin_amdgcn_ballot_w64(cond)
+// a per-lane predicate FROM a wave-uniform 64-bit mask (no instruction: the mask is used as the condition register)
+#define CBET_LANES(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
 
 // A wave-private tile of fp64 accumulators covering WX x WY x WZ nodes (powers of two), addressed toroidally.
 template <int WX_, int WY_, int WZ_, bool PAD, bool XORSW = false>
@@ -110,15 +111,33 @@ struct Origin {
 template <int M>
 __device__ __forceinline__ int abs_in(int o, int r) { return o + ((r - o) & M); }
 
+// The corner order, ONE definition.  A lane's eight (node, value) pairs are enumerated x fastest, then z, then y: corner C
+// takes the second of x's two values iff C & 1, of z's iff C & 2, of y's iff C & 4 -- (x,y,z) = (0,0,0) (1,0,0) (0,0,1)
+// (1,0,1) (0,1,0) (1,1,0) (0,1,1) (1,1,1), :341-348 without the flips (the weights are written in it: deposit_step,
+// accumulate).  Resolved at compile time: no arrays, no run-time index.
+template <int C>
+struct Corner {
+    static constexpr int index = C;
+    template <class V> static __device__ __forceinline__ V x(V v0, V v1) { return (C & 1) ? v1 : v0; }
+    template <class V> static __device__ __forceinline__ V z(V v0, V v1) { return (C & 2) ? v1 : v0; }
+    template <class V> static __device__ __forceinline__ V y(V v0, V v1) { return (C & 4) ? v1 : v0; }
+};
+// f(corner) for the eight corners in order
+template <class F>
+__device__ __forceinline__ void each_corner(F f)
+{
+    f(Corner<0>{}); f(Corner<1>{}); f(Corner<2>{}); f(Corner<3>{}); f(Corner<4>{}); f(Corner<5>{}); f(Corner<6>{}); f(Corner<7>{});
+}
+
 struct WaveCounters {
     int n_atomics = 0;        // per lane
     int n_miss = 0;           // per lane: ray-steps deposited straight to HBM
     unsigned steps_miss = 0;  // wave-uniform, packed: wave-steps << 16 | wave-steps with a window miss
     unsigned slabs_bsteps = 0;// wave-uniform, packed: planes / bricks retired << 16 | wave-steps with box B live
-    int pend = 0;             // wave-uniform: vector-memory instructions issued since the step's record gather
-#ifdef CBET_DIAG_CLOCKS
-    unsigned long long dg_ret = 0, dg_nret = 0;   // diagnostic build: shader clocks inside the write-backs of follow_box, their number
-#endif
+    int pend = 0;             // wave-uniform: vector-memory instructions issued since the step's record gather (write_back)
+    // The diagnostic builds' hook rides HERE, where every path that counts already reaches it: an object of its own, captured
+    // by the kernel's lambdas, renumbers the shipped kernel's registers although it is empty.
+    [[no_unique_address]] WaveDiag dg;
 };
 
 // The deposit grid as the write-back paths see it.  W32: the grid is smaller than 2^32 bytes (checked on the host,
@@ -138,15 +157,48 @@ __device__ __forceinline__ void grid_add(const TraceArgs &a, Grid<W32> g, int no
 template <bool W32>
 __device__ __forceinline__ void grid_add_far(const TraceArgs &a, Grid<W32> g, long index, double v) { global_add(a, &g.p[index], v); }
 
-// Take the plane `coord` (absolute, inside the box) of axis AX (0: x, 1: y) out of a tile: read the sums, zero the
-// non-zero ones and add them to HBM.  A plane is W x WZ entries (W = the other lateral extent), z fastest across
-// lanes, so one wave instruction covers whole rows -- 64-B lines when the z origin is brick-aligned.  Every vector
-// memory instruction that is really issued (some lane has a non-zero sum) is counted in wc.pend: the step's wait
-// for its record gather skips exactly that many younger instructions (see the kernel).
-template <class T, int AX, int NC, class G>
-__device__ __forceinline__ void retire_plane(const TraceArgs &a, double *tile, const Origin &o, int coord, int lane,
-                                             G edep, int sXh, int sYh, WaveCounters &wc, int coff, long gstride);
+// THE write-back: a tile entry's sum v leaves for its node -- the entry is zeroed and v added to HBM where v is non-zero
+// (only nodes that received deposits are, hence valid).  The home of the counted wait's invariant: a step's wait for its
+// record gather skips wc.pend younger vector-memory instructions (record_wait), so wc.pend must never exceed the number
+// really issued.  It grows by one exactly when some lane has a non-zero sum, i.e. when the atomic below is issued -- here,
+// in the two forms below, and nowhere else.  (Issued but not counted, an instruction only makes the wait longer; counted
+// but not issued, it would let the step read a record that has not arrived.)
+template <class G>
+__device__ __forceinline__ void write_back(const TraceArgs &a, double *tile, int slot, G edep, int node, double v, WaveCounters &wc)
+{
+    wc.pend += (CBET_BALLOT(v != 0.0) != 0ull) ? 1 : 0;
+    if (v != 0.0) {
+        tile[slot] = 0.0;
+        ++wc.n_atomics;
+        grid_add(a, edep, node, v);
+    }
+}
+// ... of a component tile's entry (the field pass), at a 64-bit index
+template <class G>
+__device__ __forceinline__ void write_back_far(const TraceArgs &a, double *tile, int slot, G edep, long index, double v, WaveCounters &wc)
+{
+    wc.pend += (CBET_BALLOT(v != 0.0) != 0ull) ? 1 : 0;
+    if (v != 0.0) {
+        grid_add_far(a, edep, index, v);
+        tile[slot] = 0.0;
+        ++wc.n_atomics;
+    }
+}
 
+// ... of a window miss: the lanes in hbm_m lie outside both boxes and add their eight values straight to HBM (add8: the
+// kernel's hbm_add8 and nothing else that touches memory) -- eight atomics, counted when some lane misses.
+template <class F>
+__device__ __forceinline__ void miss_add8(unsigned long long hbm_m, WaveCounters &wc, F add8)
+{
+    if (hbm_m != 0ull) {
+        wc.pend += 8;
+        if (CBET_LANES(hbm_m)) add8();
+    }
+}
+
+// Taking the plane `coord` (absolute, inside the box) of axis AX (0: x, 1: y) out of a tile: read the sums, write the
+// non-zero ones back.  A plane is W x WZ entries (W = the other lateral extent), z fastest across lanes, so one wave
+// instruction covers whole rows -- 64-B lines when the z origin is brick-aligned.
 // COUNT neighbouring planes (coord, coord + step, ...) of a single-component tile at once: all reads first, one wait.
 template <class T, int AX, int COUNT, class G>
 __device__ __forceinline__ void retire_planes(const TraceArgs &a, double *tile, const Origin &o, int coord, int step,
@@ -188,16 +240,10 @@ __device__ __forceinline__ void retire_planes(const TraceArgs &a, double *tile, 
         }
     }
 #pragma unroll
-    for (int q = 0; q < COUNT * IT; ++q) {
-        wc.pend += (CBET_BALLOT(v[q] != 0.0) != 0ull) ? 1 : 0;
-        if (v[q] != 0.0) {
-            tile[slot[q]] = 0.0;
-            ++wc.n_atomics;
-            grid_add(a, edep, node[q], v[q]);
-        }
-    }
+    for (int q = 0; q < COUNT * IT; ++q) write_back(a, tile, slot[q], edep, node[q], v[q], wc);
 }
 
+// ... one plane, of a tile with NC components (components 1.. dense, coff doubles behind the tile, gstride apart in the grid)
 template <class T, int AX, int NC, class G>
 __device__ __forceinline__ void retire_plane(const TraceArgs &a, double *tile, const Origin &o, int coord, int lane,
                                              G edep, int sXh, int sYh, WaveCounters &wc, int coff, long gstride)
@@ -226,21 +272,11 @@ __device__ __forceinline__ void retire_plane(const TraceArgs &a, double *tile, c
         if (NC > 1) {
 #pragma unroll
             for (int q = 1; q < NC; ++q) {
-                const double vq = ok ? tile[coff + (q - 1) * T::DT + slot_d] : 0.0;
-                wc.pend += (CBET_BALLOT(vq != 0.0) != 0ull) ? 1 : 0;
-                if (vq != 0.0) {
-                    grid_add_far(a, edep, q * gstride + node, vq);
-                    tile[coff + (q - 1) * T::DT + slot_d] = 0.0;
-                    ++wc.n_atomics;
-                }
+                const int sq = coff + (q - 1) * T::DT + slot_d;
+                write_back_far(a, tile, sq, edep, q * gstride + node, ok ? tile[sq] : 0.0, wc);
             }
         }
-        wc.pend += (CBET_BALLOT(v != 0.0) != 0ull) ? 1 : 0;
-        if (v != 0.0) {  // only nodes that received deposits are non-zero, hence valid
-            tile[slot] = 0.0;
-            ++wc.n_atomics;
-            grid_add(a, edep, node, v);
-        }
+        write_back(a, tile, slot, edep, node, v, wc);
     }
 }
 
@@ -260,21 +296,11 @@ __device__ __forceinline__ void retire_zplane(const TraceArgs &a, double *tile, 
         const int slot_d = T::slot_d(r0, r1, fixed);
 #pragma unroll
         for (int q = 1; q < NC; ++q) {
-            const double vq = ok ? tile[coff + (q - 1) * T::DT + slot_d] : 0.0;
-            wc.pend += (CBET_BALLOT(vq != 0.0) != 0ull) ? 1 : 0;
-            if (vq != 0.0) {
-                grid_add_far(a, edep, q * gstride + node, vq);
-                tile[coff + (q - 1) * T::DT + slot_d] = 0.0;
-                ++wc.n_atomics;
-            }
+            const int sq = coff + (q - 1) * T::DT + slot_d;
+            write_back_far(a, tile, sq, edep, q * gstride + node, ok ? tile[sq] : 0.0, wc);
         }
     }
-    wc.pend += (CBET_BALLOT(v != 0.0) != 0ull) ? 1 : 0;
-    if (v != 0.0) {
-        tile[slot] = 0.0;
-        ++wc.n_atomics;
-        grid_add(a, edep, node, v);
-    }
+    write_back(a, tile, slot, edep, node, v, wc);
 }
 
 // z, bricks (WZ = 16): the 8 planes [zb, zb + 8), zb a multiple of 8, leave together.  One wave instruction per
@@ -300,14 +326,7 @@ __device__ __forceinline__ void retire_zbrick(const TraceArgs &a, double *tile, 
             v[q] = CBET_AUDIT(a, (unsigned)slot[q] < (unsigned)T::N) ? tile[slot[q]] : 0.0;
         }
 #pragma unroll
-        for (int q = 0; q < ROUND; ++q) {
-            wc.pend += (CBET_BALLOT(v[q] != 0.0) != 0ull) ? 1 : 0;
-            if (v[q] != 0.0) {
-                tile[slot[q]] = 0.0;
-                ++wc.n_atomics;
-                grid_add(a, edep, abs_in<T::XM>(o.x, t0 + q) * sXh + base_node, v[q]);
-            }
-        }
+        for (int q = 0; q < ROUND; ++q) write_back(a, tile, slot[q], edep, abs_in<T::XM>(o.x, t0 + q) * sXh + base_node, v[q], wc);
     }
 }
 
@@ -379,26 +398,14 @@ __device__ __forceinline__ bool follow_box(const TraceArgs &a, double *tile, Ori
     };
     const int dx = follow_plane_axis(lx - o.x, mm, T::SX);
     const int dy = follow_plane_axis(ly - o.y, mm, T::SY);
-#ifdef CBET_DIAG_CLOCKS
-    unsigned long long dg_a, dg_b;
-    auto dg_in = [&]() { asm volatile("s_memtime %0" : "=&s"(dg_a) : : "memory"); };
-    auto dg_out = [&]() {
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_b) : "s"(dg_a) : "memory");
-        wc.dg_ret += dg_b - dg_a;
-        wc.dg_nret += 1;
-    };
-#else
-    auto dg_in = []() {};
-    auto dg_out = []() {};
-#endif
-    if (dx != 0) { dg_in(); leave(std::integral_constant<int, 0>{}, dx, o.x, o.x + T::WX - 1); dg_out(); }
+    if (dx != 0) { wc.dg.retire_begin(); leave(std::integral_constant<int, 0>{}, dx, o.x, o.x + T::WX - 1); wc.dg.retire_end(); }
     o.x += dx;
-    if (dy != 0) { dg_in(); leave(std::integral_constant<int, 1>{}, dy, o.y, o.y + T::WY - 1); dg_out(); }
+    if (dy != 0) { wc.dg.retire_begin(); leave(std::integral_constant<int, 1>{}, dy, o.y, o.y + T::WY - 1); wc.dg.retire_end(); }
     o.y += dy;
     int dz;
     if constexpr (T::BRICK) {
         dz = 8 * follow_brick_axis(lz - o.z, mm);
-        if (dz != 0) { dg_in(); retire_zbrick<T>(a, tile, o, dz < 0 ? o.z + 8 : o.z, lane, edep, sXh, sYh, wc); dg_out(); }
+        if (dz != 0) { wc.dg.retire_begin(); retire_zbrick<T>(a, tile, o, dz < 0 ? o.z + 8 : o.z, lane, edep, sXh, sYh, wc); wc.dg.retire_end(); }
     } else {
         dz = follow_plane_axis(lz - o.z, mm, T::SZ);
         if (dz != 0)
@@ -438,7 +445,7 @@ __device__ __forceinline__ int box_near_axes(const Origin &o, int nx, int ny, in
 // CDNA: a wait for a load also waits for every vector-memory instruction issued before it, and the compiler, which
 // cannot count the conditionally issued write-back atomics of a step, waits with vmcnt(0) -- i.e. for the atomics
 // issued AFTER the gather as well, a full round trip to the memory-side atomic unit in every step that moved a box.
-// So the gather is issued from inline assembly (the compiler inserts no wait for it), the write-back paths count
+// So the gather is issued from inline assembly (the compiler inserts no wait for it), write_back and miss_add8 count
 // the vector-memory instructions they really issue (WaveCounters::pend, wave-uniform), and the step waits with the
 // largest vmcnt(N), N <= pend, of a small ladder: the gather has arrived, the younger atomics stay in flight and have
 // until the next step's wait -- a whole step -- to complete.
@@ -598,26 +605,8 @@ constexpr bool kAudited = true;
 #else
 constexpr bool kAudited = false;
 #endif
-#ifdef CBET_DIAG_CLOCKS
-constexpr bool kDiagClocks = true;
-#else
-constexpr bool kDiagClocks = false;
-#endif
-#ifdef CBET_DIAG_FACES
-constexpr bool kDiagFaces = true;
-#else
-constexpr bool kDiagFaces = false;
-#endif
-#ifdef CBET_DIAG_CHAIN
-constexpr bool kDiagChain = true;
-#else
-constexpr bool kDiagChain = false;
-#endif
 constexpr double kNearTol = 0.5001;   // launch_ray_XZ.cu:132, the nearest-node tolerance
 constexpr double kFarJump = 1.4998;   // relocate_deep_interior's validity bound on |f - cell|
-
-// a per-lane predicate FROM a wave-uniform 64-bit mask (no instruction: the mask is used as the condition register)
-#define CBET_LANES(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
 
 // Lane predicates of the step loop are kept as 64-bit masks in scalar registers and combined there explicitly: `live`
 // (the ray is still traced), `hbm` (its home is box B), `miss_m` (its pending deposit goes straight to HBM instead of an
@@ -685,24 +674,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // wave-uniform, one bit per axis (box_near_axes): set unless every live lane was held by a box after the last step and
     // both boxes lie deep inside the grid along that axis.  0 = the calm step.
     int near = 7;
-#ifdef CBET_DIAG_FACES
-    // diagnostic build (never shipped): wave-steps that start near a face, the near axes summed over them, wave-steps that
-    // enter the window arm -- reported through the counter slots (see the end of the kernel)
-    unsigned dg_near = 0, dg_axes = 0, dg_arm = 0;
-#endif
-#ifdef CBET_DIAG_CLOCKS
-    // diagnostic build (never shipped): shader-clock cycles this wave spends in the record wait and in the window-shift
-    // path, reported through the counter slots (see the end of the kernel)
-    unsigned long long dg_wait = 0, dg_shift = 0, dg_nshift = 0, dg_t_start;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_t_start) : : "memory");
-#endif
-#ifdef CBET_DIAG_CHAIN
-    // diagnostic build (never shipped): shader-clock cycles of the dependent chain, from right behind the record wait to
-    // right behind the issue of the next gather (so that whatever the compiler puts in front of the gather is inside),
-    // summed per wave and reported through a counter slot (see the end of the kernel).  The two stamps and their waits
-    // cost time themselves: compare builds that carry the same stamps with each other only (scripts/diag_chain.py).
-    unsigned long long dg_c0 = 0, dg_chain = 0;
-#endif
+    wc.dg.begin();
 
     // A step's record (cbet_device.h StepRecord: the three kicks and the absorption coefficient at the ray's node) is
     // gathered as soon as the new node is known; the absorption coefficient is used at the end of the same step,
@@ -731,19 +703,10 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // wait in each arm the register allocator is free to give the record different registers in the arms and to copy
     // it -- before it has arrived -- where they meet (tests/test_isa_audit.py).
     auto await_record = [&]() {
-#ifdef CBET_DIAG_CLOCKS
-        unsigned long long t0, t1;
-        asm volatile("s_memtime %0" : "=&s"(t0) : : "memory");
-#endif
+        wc.dg.wait_begin();
         if (CBET == 0 && !kAudited) record_wait(rec_kxy, rec_kzk, wc.pend);
         else record_wait_all(rec_kxy, rec_kzk);
-#ifdef CBET_DIAG_CLOCKS
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(t1) : "s"(t0) : "memory");
-        dg_wait += t1 - t0;
-#endif
-#ifdef CBET_DIAG_CHAIN
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_c0) : : "memory");
-#endif
+        wc.dg.wait_end();
     };
     gather_record();
     await_record();
@@ -800,14 +763,9 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
                 cz0 = (Z0 & zm) << 3; cz1 = (Z1 & zm) << 3;
             }
             auto at = [](int ax, int by, int cz) { return (int)__builtin_amdgcn_bitop3_b32(ax, by, cz, 0x96); };
-            add(at(ax0, by0, cz0), w[0]);
-            add(at(ax1, by0, cz0), w[1]);
-            add(at(ax0, by0, cz1), w[2]);
-            add(at(ax1, by0, cz1), w[3]);
-            add(at(ax0, by1, cz0), w[4]);
-            add(at(ax1, by1, cz0), w[5]);
-            add(at(ax0, by1, cz1), w[6]);
-            add(at(ax1, by1, cz1), w[7]);
+            // (the six terms captured by VALUE: by reference they stay in memory until the lambda is inlined, and the plain
+            // kernels come out four instructions different)
+            each_corner([=](auto c) { add(at(c.x(ax0, ax1), c.y(by0, by1), c.z(cz0, cz1)), w[c.index]); });
         } else {
             // 24-bit multiplies by the byte strides; rot = 1: the z index rotated by 7 x + 3 y (box A of the CBET kernels)
             auto add8 = [&](int xm, int ym, int zm, int xs, int ys, int off, int rot) {
@@ -821,23 +779,13 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
                     // byte offset, so a node's offset is (z term & mask) | (x | y) -- one v_and_or_b32 behind the z sum
                     const int xy00 = x0 | y0, xy10 = x1 | y0, xy01 = x0 | y1, xy11 = x1 | y1, zm8 = zm * 8;
                     auto at = [&](int xy, int z, int r) { return (((z + r) * 8) & zm8) | xy; };
-                    add(at(xy00, Z0, ra + sa), w[0]);
-                    add(at(xy10, Z0, rb + sa), w[1]);
-                    add(at(xy00, Z1, ra + sa), w[2]);
-                    add(at(xy10, Z1, rb + sa), w[3]);
-                    add(at(xy01, Z0, ra + sb), w[4]);
-                    add(at(xy11, Z0, rb + sb), w[5]);
-                    add(at(xy01, Z1, ra + sb), w[6]);
-                    add(at(xy11, Z1, rb + sb), w[7]);
+                    each_corner([&](auto c) {
+                        add(at(c.y(c.x(xy00, xy10), c.x(xy01, xy11)), c.z(Z0, Z1), c.x(ra, rb) + c.y(sa, sb)), w[c.index]);
+                    });
                 } else {
-                    add(add3(x0, y0, zb(Z0, ra + sa)), w[0]);
-                    add(add3(x1, y0, zb(Z0, rb + sa)), w[1]);
-                    add(add3(x0, y0, zb(Z1, ra + sa)), w[2]);
-                    add(add3(x1, y0, zb(Z1, rb + sa)), w[3]);
-                    add(add3(x0, y1, zb(Z0, ra + sb)), w[4]);
-                    add(add3(x1, y1, zb(Z0, rb + sb)), w[5]);
-                    add(add3(x0, y1, zb(Z1, ra + sb)), w[6]);
-                    add(add3(x1, y1, zb(Z1, rb + sb)), w[7]);
+                    each_corner([&](auto c) {
+                        add(add3(c.x(x0, x1), c.y(y0, y1), zb(c.z(Z0, Z1), c.x(ra, rb) + c.y(sa, sb))), w[c.index]);
+                    });
                 }
             };
             if (b_active == 0) {   // scalar branch: everything goes to box A, compile-time masks and strides
@@ -852,14 +800,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // eight values to the lane's eight nodes X0..Z1 in HBM (a lane outside both boxes)
     auto hbm_add8 = [&](const double *w) {
         const int nX0 = __mul24(X0, sXh), nX1 = __mul24(X1, sXh), nY0 = __mul24(Y0, sYh), nY1 = __mul24(Y1, sYh);
-        grid_add(a, edep, nX0 + nY0 + Z0, w[0]);
-        grid_add(a, edep, nX1 + nY0 + Z0, w[1]);
-        grid_add(a, edep, nX0 + nY0 + Z1, w[2]);
-        grid_add(a, edep, nX1 + nY0 + Z1, w[3]);
-        grid_add(a, edep, nX0 + nY1 + Z0, w[4]);
-        grid_add(a, edep, nX1 + nY1 + Z0, w[5]);
-        grid_add(a, edep, nX0 + nY1 + Z1, w[6]);
-        grid_add(a, edep, nX1 + nY1 + Z1, w[7]);
+        each_corner([&](auto c) { grid_add(a, edep, c.x(nX0, nX1) + c.y(nY0, nY1) + c.z(Z0, Z1), w[c.index]); });
         wc.n_atomics += 8;
     };
 
@@ -875,7 +816,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // cell: everything that decides where it goes and when it stops) keeps the reference's operations one for one.
         const double zi0 = Fz0 * inc, zi1 = Fz1 * inc;
         const double zy00 = zi0 * Fy0, zy10 = zi1 * Fy0, zy01 = zi0 * Fy1, zy11 = zi1 * Fy1;
-        // order (x,y,z) = (0,0,0) (1,0,0) (0,0,1) (1,0,1) (0,1,0) (1,1,0) (0,1,1) (1,1,1) -- :341-348 without the flips
+        // in corner order (Corner), written out: every spelling through it moved the plain kernels' schedule
         double wgt[8];
         wgt[0] = zy00 * Fx0;
         wgt[1] = zy00 * Fx1;
@@ -886,14 +827,10 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         wgt[6] = zy11 * Fx0;
         wgt[7] = zy11 * Fx1;
         if (CBET_LANES(lds_m)) lds_add8(wgt);
-        // window misses: eight atomics, younger than the record gather just issued -- counted for its wait
-        if (hbm_m != 0ull) {
-            wc.pend += 8;
-            if (CBET_LANES(hbm_m)) {
-                hbm_add8(wgt);
-                ++wc.n_miss;
-            }
-        }
+        miss_add8(hbm_m, wc, [&]() {
+            hbm_add8(wgt);
+            ++wc.n_miss;
+        });
         if (CBET == 4) {
             // Displacement components: the ray's own node only -- box A's tiles, or HBM for a lane of
             // box B / outside the boxes.
@@ -944,11 +881,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // the pending sums of the lanes in lds_m go to their LDS box, those of the lanes in hbm_m straight to HBM
     auto flush_sums = [&](unsigned long long lds_m, unsigned long long hbm_m) {
         if (CBET_LANES(lds_m)) lds_add8(S);
-        // window misses: eight atomics, younger than the record gather just issued -- counted for its wait
-        if (hbm_m != 0ull) {
-            wc.pend += 8;
-            if (CBET_LANES(hbm_m)) hbm_add8(S);
-        }
+        miss_add8(hbm_m, wc, [&]() { hbm_add8(S); });
     };
 
     // ---- the rest of a step: wait for the record, absorb, add the deposit to the pending sums, end rays -------------
@@ -1006,11 +939,8 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     };
 
     for (int tt = 0; tt < a.nt; ++tt) {                        // :207  (live != 0 here: checked where lanes end)
-        if constexpr (STATS || kDiagClocks || kDiagFaces || kDiagChain) wc.steps_miss += 1u << 16;
-#ifdef CBET_DIAG_FACES
-        dg_near += near != 0 ? 1 : 0;
-        dg_axes += __builtin_popcount((unsigned)near);
-#endif
+        if constexpr (STATS || WaveDiag::kCountsWaveSteps) wc.steps_miss += 1u << 16;
+        wc.dg.step_begin(near);
         // ---- move ------------------------------------------------------------------------------------------
         // :268-273 kick then drift (stencil values gathered during the previous step)
         s.vx -= rec_kxy.x;
@@ -1056,13 +986,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         cell = new_cell;
         // :296-298 absorption coefficient at the new node and the NEXT step's kicks
         gather_record();
-#ifdef CBET_DIAG_CHAIN
-        {
-            unsigned long long dg_c1;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_c1) : "s"(dg_c0) : "memory");
-            dg_chain += dg_c1 - dg_c0;
-        }
-#endif
+        wc.dg.chain_end();
         // (everything below reads the cell through this barrier, i.e. is scheduled BEHIND the gather's issue: left alone the
         // compiler puts the offsets' nine instructions in front of it, on the dependent chain -- and, without `inc`, which
         // every product of the pending deposit depends on, six of that deposit's fp64 multiplies)
@@ -1174,13 +1098,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // renews their mark: 1 % of the wave-steps)
         out_core |= miss_m;
         if (out_core != 0ull) {
-#ifdef CBET_DIAG_FACES
-            dg_arm += 1;
-#endif
-#ifdef CBET_DIAG_CLOCKS
-            unsigned long long dg_t0;
-            asm volatile("s_memtime %0" : "=&s"(dg_t0) : : "memory");
-#endif
+            wc.dg.arm_begin();
             // The wave-uniform state this arm changes -- box origins, masks, flags -- is worked on in COPIES and written back
             // at the end through commit(): an assembly move TIED to the variable's register, so that the value the arm leaves
             // and the one the common path carries meet in one register (left to the compiler every such variable costs the
@@ -1245,14 +1163,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             commit_v(tile_off, n_toff);
             // (the write-back paths keep the count in a vector register; the common path's stays scalar this way)
             wc.pend = __builtin_amdgcn_readfirstlane(wc.pend);
-#ifdef CBET_DIAG_CLOCKS
-            {
-                unsigned long long dg_t1;
-                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_t1) : "s"(dg_t0) : "memory");
-                dg_shift += dg_t1 - dg_t0;
-                dg_nshift += 1;
-            }
-#endif
+            wc.dg.arm_end();
         } else if (near != 0) {
             commit(near, box_near_axes<T>(oA, nx, ny, nz) | (b_active == 0 ? 0 : box_near_axes<TB>(oB, nx, ny, nz)));
         }
@@ -1274,41 +1185,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, kWave);
         if (lane == 0 && t != 0.0) atomicAdd(&a.beam_gain[beam], t);
     }
-#ifdef CBET_DIAG_CLOCKS
-    if (lane == 0) {   // the diagnostic build reuses four slots: record-wait cycles, shift-path cycles, shift entries, wave cycles
-        unsigned long long dg_t_end;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dg_t_end) : : "memory");
-        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
-        atomicAdd(&a.counters[kCntWaveSteps], (unsigned long long)(wc.steps_miss >> 16));
-        atomicAdd(&a.counters[kCntGlobalAtomics], dg_wait);
-        atomicAdd(&a.counters[kCntEvictions], dg_shift);
-        atomicAdd(&a.counters[kCntWaveStepsWide], dg_nshift);
-        atomicAdd(&a.counters[kCntSlabsRetired], dg_t_end - dg_t_start);
-        atomicAdd(&a.counters[kCntRays], wc.dg_ret);              // (the ray count gives way to the write-backs' clocks ...)
-        atomicAdd(&a.counters[kCntWaveStepsMiss], wc.dg_nret);    // (... and their number)
-    }
-    return;
-#endif
-#ifdef CBET_DIAG_CHAIN
-    if (lane == 0) {   // the diagnostic build reuses one slot: the chain's cycles
-        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
-        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
-        atomicAdd(&a.counters[kCntWaveSteps], (unsigned long long)(wc.steps_miss >> 16));
-        atomicAdd(&a.counters[kCntGlobalAtomics], dg_chain);
-    }
-    return;
-#endif
-#ifdef CBET_DIAG_FACES
-    if (lane == 0) {   // the diagnostic build reuses four slots
-        atomicAdd(&a.counters[kCntSteps], (unsigned long long)tot_steps);
-        atomicAdd(&a.counters[kCntRays], (unsigned long long)tot_rays);
-        atomicAdd(&a.counters[kCntWaveSteps], (unsigned long long)(wc.steps_miss >> 16));
-        atomicAdd(&a.counters[kCntWaveStepsWide], (unsigned long long)dg_near);
-        atomicAdd(&a.counters[kCntWaveStepsMiss], (unsigned long long)dg_axes);
-        atomicAdd(&a.counters[kCntSlabsRetired], (unsigned long long)dg_arm);
-    }
-    return;
-#endif
+    if (wc.dg.report(a, lane, tot_steps, tot_rays, wc.steps_miss >> 16)) return;   // a diagnostic build: the slots are its own
     // counters: one atomic per wave and counter
     if constexpr (STATS) {
         const int tot_at = wave_sum(wc.n_atomics), tot_miss = wave_sum(wc.n_miss);

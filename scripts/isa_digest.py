@@ -6,8 +6,9 @@ commit can be digested with today's flags.  Per kernel, one line:
 
     <demangled name>  body=<sha256/16>  insts=<count>  hist=<sha256/16>  vgpr=.. sgpr=.. lds=.. scratch=..
 
-body: the kernel's instructions, labels and directives with comments and blank lines dropped and the function number
-taken out of the compiler's block labels (.LBB<n>_<k>); hist: the sorted "mnemonic count" table; the four resource
+body: the kernel's instructions, labels and directives with comments and blank lines dropped, the function number
+taken out of the compiler's block labels (.LBB<n>_<k>) and the statement number that `%=` puts at the end of an
+inline-assembly label (.Lrw_0_<n>) replaced by N -- it counts the assembly statements in front, kernel or not; hist: the sorted "mnemonic count" table; the four resource
 fields are next_free_vgpr, next_free_sgpr, group_segment_fixed_size and private_segment_fixed_size.
 
     python scripts/isa_digest.py FILE.hip [FILE.hip ...] [--hist NAME_PART]     (--hist: also print that kernel's table)
@@ -24,6 +25,10 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from cbet_raytracing_3d_amd import build  # noqa: E402
+
+
+# a label of an inline-assembly block, `.Lrw_0_%=` and the like: `%=` becomes the statement's number in the file
+LABEL_UID = re.compile(r"(\.L(?!BB)[A-Za-z]\w*?_)\d+\b")
 
 
 def listing(path):
@@ -52,7 +57,7 @@ def kernels(text):
     for name in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M):
         m = re.search(r"^%s:[^\n]*\n(.*?)^\s*\.amdhsa_kernel %s\n(.*?)^\s*\.end_amdhsa_kernel" % (re.escape(name), re.escape(name)),
                       text, re.S | re.M)
-        code = [re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].strip()) for l in m.group(1).splitlines()]
+        code = [LABEL_UID.sub(r"\1N", re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].strip())) for l in m.group(1).splitlines()]
         out[name] = ([l for l in code if l], dict(re.findall(r"\.amdhsa_(\w+)\s+(\S+)", m.group(2))))
     return out
 

@@ -84,26 +84,57 @@ def test_in_flight_record_is_never_moved(listing):
                 assert not (_touched(code) & record), (name, l)
 
 
+def _braces(text, start):
+    """(start, end) of the brace pair that opens at text[start]."""
+    depth = 0
+    for at in range(start, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[at], 0)
+        if depth == 0:
+            return start, at
+    raise AssertionError(text[start:start + 80])
+
+
+def _body(text, name):
+    """... of the function or lambda `name` defined in `text` (comments already stripped)."""
+    (m,) = re.finditer(r"(?:\bvoid %s\(|\bauto %s = \[)" % (name, name), text)
+    start = text.index("{", m.end())
+    assert ";" not in text[m.end():start], name                    # a definition, not a declaration
+    return _braces(text, start)
+
+
 def test_every_write_back_atomic_is_counted():
-    """record_wait(vmcnt(N <= pend)) is only right while every vector-memory instruction issued after a gather is
-    counted in WaveCounters::pend: every global_add / grid_add call site of the shipped kernel sits behind a `wc.pend +=` of its
-    own (the four-component field pass waits with vmcnt(0) and is exempt).  The file refuses targets other than gfx950
-    (one in-order vmcnt shared by loads, stores and atomics)."""
-    src = open(os.path.join(CSRC, "cbet_trace_window.hip")).read().splitlines()
-    # (grid_add / grid_add_far: global_add through the grid handle; their own bodies -- `g.p` -- are not call sites)
-    sites = [i for i, l in enumerate(src) if re.search(r"\b(global_add|grid_add|grid_add_far)\(a,", l) and "__device__" not in l and "g.p" not in l]
-    assert len(sites) >= 12
-    helper = [i for i, l in enumerate(src) if "auto hbm_add8 = " in l]          # eight adds of a lane outside both boxes:
-    assert len(helper) == 1                                                      # counted where the helper is CALLED
-    for i in sites:
-        window = "\n".join(src[max(0, i - 12):i + 1])
-        assert ("wc.pend +=" in window or "comp_stride + own_node" in window or
-                helper[0] < i <= helper[0] + 10), (i + 1, src[i])
-    calls = [i for i, l in enumerate(src) if "hbm_add8(" in l and "auto hbm_add8" not in l]
+    """record_wait(vmcnt(N <= pend)) is only right while WaveCounters::pend never EXCEEDS the number of vector-memory
+    instructions really issued behind the gather: an instruction issued but not counted only makes the wait longer, one
+    counted but not issued lets the step read a record that has not arrived.  So counting and issuing live together: every
+    add to the grid is made by write_back, write_back_far or hbm_add8 -- which only miss_add8 is handed -- and each of
+    write_back, write_back_far and miss_add8 counts in its own body, in front of its add (the own-node deposit of the
+    four-component field pass waits with vmcnt(0) and is exempt).  The file refuses targets other than gfx950 (one in-order
+    vmcnt shared by loads, stores and atomics)."""
+    text = open(os.path.join(CSRC, "cbet_trace_window.hip")).read()
+    code = re.sub(r"//[^\n]*", "", text)
+    homes = {n: _body(code, n) for n in ("grid_add", "grid_add_far", "write_back", "write_back_far", "hbm_add8")}
+    # (the exempt one: the `if (CBET == 4)` block of deposit_step, in a kernel that waits for everything)
+    lo, hi = _body(code, "deposit_step")
+    (own,) = [m.end() - 1 for m in re.finditer(r"if \(CBET == 4\) \{", code[lo:hi])]
+    homes["own-node deposit"] = _braces(code, lo + own)
+    assert len(re.findall(r"\brecord_wait\(", code)) == 2 and "if (CBET == 0 && !kAudited) record_wait(" in code   # (definition, one use)
+    # every add to the grid lies inside one of the counted helpers (grid_add / grid_add_far themselves call global_add)
+    adds = [m.start() for m in re.finditer(r"\b(?:global_add|grid_add|grid_add_far)\(", code) if not code[:m.start()].endswith("void ")]
+    assert len(adds) >= 8
+    for at in adds:
+        assert [n for n, (lo, hi) in homes.items() if lo < at < hi], code[at:at + 80]
+    # ... hbm_add8 is called only as the adder of miss_add8
+    calls = [m.start() for m in re.finditer(r"\bhbm_add8\(", code)]
     assert len(calls) == 2
-    for i in calls:
-        assert "wc.pend +=" in "\n".join(src[max(0, i - 4):i + 1]), (i + 1, src[i])
-    text = "\n".join(src)
+    for at in calls:
+        assert re.search(r"miss_add8\(hbm_m, wc, \[&\]\(\) \{\s*$", code[:at]), code[at - 80:at + 20]
+    # ... and each helper counts in its own body, in front of its add
+    for name, add in (("write_back", "grid_add("), ("write_back_far", "grid_add_far("), ("miss_add8", "add8()")):
+        lo, hi = _body(code, name)
+        body = code[lo:hi]
+        assert body.count("wc.pend +=") == 1 and body.count(add) == 1, name
+        assert body.index("wc.pend +=") < body.index(add), name
+    assert code.count("wc.pend +=") == 3                            # ... and nothing else counts
     assert "#error" in text and "__gfx950__" in text
 
 
