@@ -241,6 +241,96 @@ class Mesh(C.Structure):
         return m
 
 
+# ---- deposit on the hydro mesh (cbet_mesh_deposit) ----------------------------
+MESH_MAX_SUBSAMPLES = 4
+MESH_DEPOSIT_AUTO, MESH_DEPOSIT_GLOBAL, MESH_DEPOSIT_LDS = 0, 1, 2
+
+
+class MeshCellsStruct(C.Structure):
+    """cbet_mesh_cells: the argument of cbet_mesh_cells_create (HOST edge arrays)."""
+    _fields_ = [("center", C.c_double * 3), ("nr", C.c_int), ("ntheta", C.c_int), ("nphi", C.c_int),
+                ("r_edges", C.c_void_p), ("theta_edges", C.c_void_p), ("phi_edges", C.c_void_p)]
+
+
+class MeshCells:
+    """The cells of a spherical-polar mesh about `center` (cm) that deposit grids are binned into: r_edges [nr+1],
+    theta_edges [ntheta+1] from 0 to pi (None: one row), phi_edges [nphi+1] over one period (None: one column).  Wraps a
+    cbet_mesh_cells_handle: the library validates the edges (CbetError names the first offence), builds the lookup tables
+    and, with gpu a device index, uploads them once; gpu None makes a host-only handle (mesh_deposit_host).  close(), or
+    the object's end, frees it."""
+
+    def __init__(self, r_edges, theta_edges=None, phi_edges=None, center=(0.0, 0.0, 0.0), subsamples_max=4, gpu=None):
+        self._h = C.c_void_p()
+
+        def edges(a):
+            if a is None:
+                return None
+            a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
+            return np.ascontiguousarray(a, dtype=np.float64).reshape(-1).copy()
+
+        self.r_edges, self.theta_edges, self.phi_edges = edges(r_edges), edges(theta_edges), edges(phi_edges)
+        self.center = tuple(float(v) for v in center)
+        self.subsamples_max = int(subsamples_max)
+        self.gpu = -1 if gpu is None else int(gpu)
+        self.shape = tuple(1 if e is None else e.size - 1 for e in (self.r_edges, self.theta_edges, self.phi_edges))
+        self.column_shift = 0           # from_nodes: column k is node (k + column_shift) % nphi's cell
+        c = MeshCellsStruct()
+        c.center = (C.c_double * 3)(*self.center)
+        c.nr, c.ntheta, c.nphi = self.shape
+        c.r_edges, c.theta_edges, c.phi_edges = _addr(self.r_edges), _addr(self.theta_edges), _addr(self.phi_edges)
+        _check(lib().cbet_mesh_cells_create(C.byref(self._h), C.byref(c), self.subsamples_max, self.gpu))
+
+    @classmethod
+    def from_nodes(cls, r, theta=None, phi=None, center=(0.0, 0.0, 0.0), **kw):
+        """The dual cells of a node mesh (api.Mesh's coordinates): edges at the midpoints between nodes; the first r edge
+        max(0, r[0] - (r[1] - r[0]) / 2), the last r[-1] + (r[-1] - r[-2]) / 2; the theta edges closed with 0 and pi;
+        the phi edges periodic (the first lies half-way between the last node, one period back, and the first).  theta /
+        phi None or of one node: one row / one column.  Column k is node k's cell, except where the first phi edge would fall
+        below -pi (the library wants it in [-pi, pi)): the edges then start one column later and column k is node
+        (k + column_shift) % nphi's cell, column_shift = 1; RayTracer.deposit_on_mesh rolls its outputs back."""
+        r = np.asarray(r, dtype=np.float64).reshape(-1)
+        if r.size < 2:
+            raise ValueError("from_nodes: r needs two nodes or more")
+        mid = 0.5 * (r[1:] + r[:-1])
+        r_edges = np.concatenate(([max(0.0, r[0] - (r[1] - r[0]) / 2)], mid, [r[-1] + (r[-1] - r[-2]) / 2]))
+        theta_edges = phi_edges = None
+        shift = 0
+        if theta is not None and np.size(theta) > 1:
+            t = np.asarray(theta, dtype=np.float64).reshape(-1)
+            theta_edges = np.concatenate(([0.0], 0.5 * (t[1:] + t[:-1]), [np.pi]))
+        if phi is not None and np.size(phi) > 1:
+            f = np.asarray(phi, dtype=np.float64).reshape(-1)
+            first = 0.5 * ((f[-1] - 6.283185307179586) + f[0])
+            phi_edges = np.concatenate(([first], 0.5 * (f[1:] + f[:-1]), [first + 6.283185307179586]))
+            if phi_edges[0] < -np.pi:        # the same columns, named one period later
+                shift = 1
+                phi_edges = np.concatenate((phi_edges[1:], [phi_edges[1] + 6.283185307179586]))
+        cells = cls(r_edges, theta_edges, phi_edges, center, **kw)
+        cells.column_shift = shift
+        return cells
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            lib().cbet_mesh_cells_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # Every symbol include/cbet_mi355x.h declares; tests check the library exports all of them.
 EXPORTS = [
     "cbet_last_error", "cbet_version", "cbet_params_default", "cbet_derive",
@@ -258,6 +348,7 @@ EXPORTS = [
     "cbet_tabulate_target", "cbet_target_tables",
     "cbet_tabulate_flow", "cbet_context_set_flow", "cbet_context_flow", "cbet_flow_table",
     "cbet_tabulate_mesh", "cbet_tabulate_mesh_flow", "cbet_mesh_check", "cbet_mesh_tables", "cbet_mesh_flow_table",
+    "cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit",
 ]
 
 _lib = None
@@ -354,6 +445,12 @@ def lib():
     L.cbet_mesh_check.argtypes = [C.POINTER(Mesh)]
     L.cbet_mesh_tables.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp, dp]
     L.cbet_mesh_flow_table.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp]
+    L.cbet_mesh_cells_create.argtypes = [C.POINTER(vp), C.POINTER(MeshCellsStruct), C.c_int, C.c_int]
+    L.cbet_mesh_cells_destroy.argtypes = [vp]
+    L.cbet_mesh_cells_destroy.restype = None
+    deposit = [vp, vp, C.c_int, C.c_long, C.POINTER(Params), C.c_int, C.c_int, vp, vp, vp, vp]
+    L.cbet_mesh_deposit_device.argtypes = deposit
+    L.cbet_mesh_deposit.argtypes = deposit
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -788,6 +885,38 @@ def sph_modes_host(edep, params, center, r_edges, lmax):
     _check(lib().cbet_sph_modes(_addr(a), ngrids, stride, C.byref(p), _dptr(c), _dptr(e), nshell, lmax, _addr(coeffs),
                                 _addr(energy), _addr(nodes), None))
     return coeffs, energy, nodes
+
+
+# ---- deposit on the hydro mesh (cbet_mesh_deposit) --------------------------------------------
+def mesh_deposit(cells, edep, ngrids, grid_stride, params, subsamples, method, cell_energy, outside, cell_samples, stream=None):
+    """cbet_mesh_deposit_device: device grids (edep None: counts alone) binned into `cells` (a MeshCells made with a gpu);
+    outputs OVERWRITTEN -- cell_energy [ngrids][nr][ntheta][nphi], outside [ngrids], cell_samples int64 [nr][ntheta][nphi].
+    method: MESH_DEPOSIT_AUTO, _GLOBAL or _LDS.  Enqueued on `stream`."""
+    _check(lib().cbet_mesh_deposit_device(cells.handle, _addr(edep), ngrids, grid_stride, C.byref(params), subsamples, method,
+                                          _addr(cell_energy), _addr(outside), _addr(cell_samples), _addr(stream)))
+
+
+def mesh_deposit_host(cells, edep, params, subsamples=2):
+    """cbet_mesh_deposit, the host twin, on host arrays: edep as sph_modes_host takes it -- a float64 numpy grid
+    (nx+2, ny+2, row), a stack (G, nx+2, ny+2, row), or None (counts alone).  Returns numpy (cell_energy [G][nr][ntheta][nphi],
+    outside [G], cell_samples int64 [nr][ntheta][nphi])."""
+    p = params.copy(edep_zpitch=0)
+    if edep is None:
+        a, ngrids, stride = None, 1, 0
+    else:
+        a = np.ascontiguousarray(edep, dtype=np.float64)
+        grid = a.shape[-3:]
+        if a.ndim not in (3, 4) or grid[:2] != (p.nx + 2, p.ny + 2) or grid[2] < p.nz + 2:
+            raise ValueError("edep grids must be (nx+2, ny+2, >= nz+2), got %s" % (a.shape,))
+        if grid[2] > p.nz + 2:
+            p.edep_zpitch = grid[2]
+        ngrids, stride = (a.shape[0] if a.ndim == 4 else 1), int(np.prod(grid))
+    energy = np.zeros((ngrids,) + cells.shape)
+    outside = np.zeros(ngrids)
+    samples = np.zeros(cells.shape, dtype=np.int64)
+    _check(lib().cbet_mesh_deposit(cells.handle, _addr(a), ngrids, stride, C.byref(p), subsamples, 0, _addr(energy),
+                                   _addr(outside), _addr(samples), None))
+    return energy, outside, samples
 
 
 def ray_tracing(te_profile, r_profile, ne_profile, edep, params, beam_norm=None, gpus=None, ngpu=1):

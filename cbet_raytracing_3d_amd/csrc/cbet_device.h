@@ -218,5 +218,26 @@ struct MeshArgs {
 hipError_t launch_tabulate_mesh(const MeshArgs &a, hipStream_t stream);   // k_tabulate_mesh: a.ne3d / a.kap3d
 hipError_t launch_mesh_flow(const MeshArgs &a, hipStream_t stream);       // k_mesh_flow: a.flow
 
+// Deposit on the hydro mesh (cbet_mesh_deposit.hip, cbet_mesh_deposit_host.cpp, cbet_mesh_deposit_model.h; DESIGN.md
+// section 15).  The four lookup tables are the handle's: device copies for the kernel, host copies for the twin.
+struct MeshDepositArgs {
+    const double *edep;                     // [ngrids] haloed grids grid_stride doubles apart, or NULL (counts only)
+    long grid_stride, row_pitch;            // doubles between grids / per (I, J) row
+    int ngrids, nx, ny, nz;
+    double xmin, ymin, zmin, dx, dy, dz;
+    double ox, oy, oz;                      // the cells' centre
+    int nr, nth, nph;                       // cells
+    int S;                                  // sub-samples per axis
+    double inv;                             // 1.0 / (S*S*S)
+    const double *re, *ct, *pe, *off;       // r_edges [nr+1], cos of the interior theta edges [nth-1], diamond angles of the first nph phi edges, offsets [S]
+    double *cell_energy, *outside;          // [ngrids][nr][nth][nph], [ngrids]; launch_mesh_deposit zeroes them first
+    long long *cell_samples;                // [nr][nth][nph]; likewise
+    int chunk;                              // grids per workgroup: blockIdx.y takes the chunk-th part of the stack
+};
+constexpr int kMeshDepositChunks = 8;               // the LDS arm splits a stack into at most this many parts
+constexpr size_t kMeshDepositLds = 40960;           // ... and takes at most this much LDS: four workgroups per CU
+size_t mesh_deposit_lds(const MeshDepositArgs &a, bool lds_arm);   // dynamic LDS of a launch with a.chunk, bytes
+hipError_t launch_mesh_deposit(const MeshDepositArgs &a, bool lds_arm, hipStream_t stream);
+
 }  // namespace cbet
 #endif

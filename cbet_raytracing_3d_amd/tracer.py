@@ -66,6 +66,8 @@ class RayTracer:
         self._launch_list = None        # set_launch_list(): the regrouped list (ray_ids())
         self.target = None              # set_target(): api.Target, or None = the spherical target about the origin
         self.mesh = None                # set_plasma_mesh(): the DEVICE api.Mesh the tables come from, or None = the profiles
+        self._mesh_nodes = None         # ... its host (r, theta, phi, center), and the dual cells deposit_on_mesh builds from them
+        self._mesh_cells = None
         self.flow = None                # set_flow(): None, "target", "mesh" or the caller's [3, nx, ny, nz] table
         self._flow_gp = None            # the gain parameters a "target" flow is tabulated from
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
@@ -122,6 +124,7 @@ class RayTracer:
         each other.  The CBET stage refuses a mesh while no flow is set, as it refuses a target: set_flow("mesh") gives it
         the mesh's own velocity."""
         if r is None:
+            self._drop_mesh_cells()
             self.mesh = None
             if self._flow_is("mesh"):
                 self.set_flow(None)
@@ -137,7 +140,14 @@ class RayTracer:
             raise ValueError(str(e)) from None
         if self._flow_is("mesh") and not host.has_velocity:
             raise ValueError('set_plasma_mesh: set_flow("mesh") is in force and this mesh has no velocity')
+        self._drop_mesh_cells()
         self.mesh = host.to(self.device)
+        self._mesh_nodes = tuple(a.copy() for a in host._keep[:3]) + (tuple(host.center),)
+
+    def _drop_mesh_cells(self):
+        if self._mesh_cells is not None:
+            self._mesh_cells.close()
+        self._mesh_nodes = self._mesh_cells = None
 
     # ---- perturbed targets (include/cbet_mi355x.h cbet_tabulate_target) ------------------------
     def set_target(self, offset=(0.0, 0.0, 0.0), coeffs=None, lmax=None):
@@ -439,6 +449,46 @@ class RayTracer:
             coeffs, energy = coeffs[0], energy[0]
         return coeffs, energy, nodes
 
+    # ---- deposit on the hydro mesh (include/cbet_mi355x.h cbet_mesh_deposit) -------------------
+    def deposit_on_mesh(self, grid, cells=None, subsamples=2, method=0):
+        """The energy of a deposit grid binned into the cells of a spherical-polar mesh, on torch's current stream.  grid:
+        as sph_modes takes it -- one grid, a padded one or a [G, ...] stack.  cells: an api.MeshCells made for this
+        tracer's device (gpu=tracer.gpu); None: the dual cells of the mesh given to set_plasma_mesh
+        (api.MeshCells.from_nodes), built at the first call and kept -- column k is then node k's cell.  subsamples: S in
+        1 .. 4, each node's energy spread over S^3 samples of its box.  method: api.MESH_DEPOSIT_AUTO, _GLOBAL or _LDS.
+        Returns (cell_energy [nr, ntheta, nphi], outside scalar tensor, cell_samples int64 [nr, ntheta, nphi]), with a
+        leading [G] on the first two for a stack; sum(cell_energy) + outside = sum(grid) up to rounding."""
+        if cells is None:
+            if self._mesh_nodes is None:
+                raise ValueError("deposit_on_mesh: no cells given and no plasma mesh is set (set_plasma_mesh)")
+            if self._mesh_cells is None:
+                r, theta, phi, center = self._mesh_nodes
+                self._mesh_cells = api.MeshCells.from_nodes(r, theta, phi, center, gpu=self.gpu)
+            cells = self._mesh_cells
+        gs = self.grid_shape
+        _require(grid, grid.shape, "grid")          # (which shapes: below)
+        if grid.device != self.device:
+            raise ValueError("grid must be on %s" % self.device)
+        p = self.params.copy(edep_zpitch=0)
+        stack = False
+        if grid.dim() == 4 and tuple(grid.shape[1:]) == gs:
+            stack, ngrids, stride = True, grid.shape[0], int(np.prod(gs))
+        elif grid.dim() == 3 and tuple(grid.shape[:2]) == gs[:2] and grid.shape[2] >= gs[2]:
+            ngrids, stride = 1, 0
+            if grid.shape[2] > gs[2]:
+                p.edep_zpitch = int(grid.shape[2])
+        else:
+            raise ValueError("grid must be %s, a padded grid or a [G, ...] stack of them, got %s" % (gs, tuple(grid.shape)))
+        energy = torch.empty((ngrids,) + cells.shape, dtype=torch.float64, device=self.device)
+        outside = torch.empty(ngrids, dtype=torch.float64, device=self.device)
+        samples = torch.empty(cells.shape, dtype=torch.int64, device=self.device)
+        api.mesh_deposit(cells, grid, ngrids, stride, p, subsamples, method, energy, outside, samples, self._stream())
+        if cells.column_shift:
+            energy, samples = torch.roll(energy, cells.column_shift, -1), torch.roll(samples, cells.column_shift, -1)
+        if not stack:
+            energy, outside = energy[0], outside[0]
+        return energy, outside, samples
+
     def node_tables(self):
         """Copies of the context's node tables (ne3d, kappa3d) as numpy arrays, for tests."""
         n = self.params.nx * self.params.ny * self.params.nz
@@ -451,6 +501,7 @@ class RayTracer:
         return out
 
     def close(self):
+        self._drop_mesh_cells()
         self.ctx.close()
 
 

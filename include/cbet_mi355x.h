@@ -773,6 +773,94 @@ int cbet_sph_modes(const double *edep, int ngrids, long grid_stride, const cbet_
                    const double *r_edges, int nshell, int lmax, double *coeffs, double *shell_energy,
                    long long *shell_nodes, void *stream);
 
+/* ---- deposit on the hydro mesh: conservative remap to spherical-polar cells --------------- */
+/*
+ * The way back to a hydrodynamics code: the energy of one deposit grid, or of a stack of per-beam grids, binned into the
+ * CELLS of a spherical-polar mesh about a centre o.  Every sample of the grid lands in exactly one cell or in `outside`,
+ * so sum(cell_energy) + outside = sum(grid) up to rounding.
+ *
+ * Cells (cbet_mesh_cells, HOST arrays, captured by cbet_mesh_cells_create): nr >= 1 shells, ntheta >= 1 rows, nphi >= 1
+ * columns between the edges
+ *     r_edges[nr+1]          strictly ascending, finite, r_edges[0] >= 0
+ *     theta_edges[ntheta+1]  strictly ascending, |theta_edges[0]| <= 1e-12, |theta_edges[ntheta] - pi| <= 1e-12;
+ *                            may be NULL when ntheta == 1
+ *     phi_edges[nphi+1]      strictly ascending, -pi <= phi_edges[0] < pi,
+ *                            |phi_edges[nphi] - phi_edges[0] - TWO_PI| <= 1e-12; may be NULL when nphi == 1
+ * Only the interior theta edges and the first nphi phi edges enter the lookup, so every direction belongs to exactly one
+ * (row, column).  nr + ntheta + nphi + 3 <= CBET_MESH_MAX_COORDS and nr * ntheta * nphi < 2^31.
+ *
+ * Samples.  The input is cbet_sph_modes's: the haloed grid edep[I][J][K], halo nodes included, rows of nz + 2 doubles or
+ * p->edep_zpitch, ngrids grids grid_stride doubles apart.  The energy E of node (I, J, K) is spread evenly over the box
+ * dx dy dz centred on the node, as S^3 sub-samples, S = subsamples in {1, 2, 3, 4}.  Every statement below is ONE IEEE
+ * fp64 operation per written operator, in the written order, no fused multiply-add:
+ *     off[a] = (2a + 1 - S) / (2.0 * S)   a = 0 .. S-1     (a table the host makes)
+ *     xs = ((I - 1) * dx + xmin) + off[a] * dx,  sx = xs - ox;      y with (J, b) and z with (K, c) alike
+ *     rho = sqrt(sx*sx + sy*sy + sz*sz)                             squares summed x, y, z
+ * and each sample carries E * inv, inv = 1.0 / (S*S*S) (host-made).  With S = 1, off = 0 and the sample is the node with
+ * cbet_sph_modes's coordinates, bit for bit.
+ *
+ * Cell of a sample.  No trigonometric function is evaluated per sample on either side, so the device and the host twin
+ * put every sample into the same cell, bit for bit (the atan2 caveat of the hydro-mesh plasma does not apply here, where it
+ * would move a whole node's energy):
+ *     shell m:  r_edges[m] <= rho < r_edges[m+1]; a sample in no shell (a NaN rho included) goes to `outside`
+ *     row:      c = sz / rho;  row = the number of interior theta edges e with c <= ct[e],
+ *               ct[e] = cos(theta_edges[e]), a table the host makes (descending)
+ *     column:   the "diamond angle" of (sx, sy):  a = |sx| + |sy|;  d = 0 if a == 0, else t = sx / a and
+ *               d = (sy >= 0) ? 1.0 - t : 3.0 + t, in [0, 4), ascending with phi.  The host makes
+ *               pe[k] = d(cos(phi_edges[k]), sin(phi_edges[k])) for k < nphi, + 4.0 wherever pe[k] < pe[0], and refuses
+ *               cells whose pe is not strictly ascending (columns thinner than the rounding of cos and sin).
+ *               d = d + 4.0 if d < pe[0];  column = the last k with pe[k] <= d
+ * Degenerate samples: rho == 0 (the sample is the centre) is counted in row 0 and column 0 of its shell.  A sample on the
+ * polar axis (a == 0, rho > 0) has d = 0: the column that holds phi = 0; its row is 0 above the centre (c = 1) and
+ * ntheta - 1 below (c = -1).  sy == -0.0 counts as sy >= 0.
+ * Every index lies inside its table whatever the grid and the cells hold, NaN included.
+ *
+ * Outputs, OVERWRITTEN:
+ *     cell_energy  double [ngrids][nr][ntheta][nphi]   sum of E * inv over the cell's samples
+ *     outside      double [ngrids]                     the same over the samples in no shell
+ *     cell_samples int64  [nr][ntheta][nphi]           samples in the cell; times dx dy dz / S^3: the sampled volume, which
+ *                                                      turns an energy into a power density
+ * edep == NULL with ngrids == 1 writes cell_samples only (cell_energy and outside may then be NULL).
+ * Limits: 1 <= ngrids <= CBET_SPH_MAX_GRIDS, 1 <= subsamples <= the handle's subsamples_max <= CBET_MESH_MAX_SUBSAMPLES;
+ * with ngrids > 1, grid_stride >= one grid's doubles.  Anything else is CBET_EINVAL before any device work.
+ *
+ * Sums.  The counts are integers and exact.  The device adds the energies with floating-point atomics, in any order, and
+ * books a run of consecutive samples of one node that share a cell as ONE contribution (E * inv) * n: like the deposit it
+ * remaps, and like cbet_farfield, the energies are NOT bit-reproducible from run to run; they agree with the host twin
+ * within the rounding of sums taken in another order.  A sample with E == 0 issues no energy atomic.
+ *
+ * cbet_mesh_cells_create validates the cells (CBET_EINVAL names the first offence), builds ct, pe and off, keeps host
+ * copies and, with gpu >= 0, uploads them once to that device (allocates and synchronises here); gpu == -1 makes a
+ * host-only handle, which cbet_mesh_deposit accepts and cbet_mesh_deposit_device refuses.
+ * cbet_mesh_deposit_device: DEVICE grids and outputs; enqueues the zero-fill of the outputs and one kernel on `stream`:
+ * no allocation, no synchronisation, graph-capturable.  method: CBET_MESH_DEPOSIT_AUTO, _GLOBAL (every contribution a
+ * global atomic: meshes with many cells, where few contributions meet) or _LDS (workgroup-private accumulators in LDS,
+ * flushed once: the 1-D and coarse 2-D meshes, where millions of nodes would meet at a few hundred addresses).  The LDS
+ * arm handles ceil(ngrids / 8) grids per workgroup and needs
+ *     8 (nr + ntheta + nphi + subsamples + ngrids') + nr ntheta nphi (8 ceil(ngrids / 8) + 4) <= 40960 bytes
+ * (ngrids' = ceil(ngrids / 8)); where that does not hold _LDS is CBET_EINVAL and _AUTO takes _GLOBAL.
+ * cbet_mesh_deposit: the host twin on HOST arrays: plain loops in logical node order, a node's samples in (a, b, c)
+ * order, c fastest, one addition per sample; its sums are the same bits from call to call.  method and stream are ignored.
+ */
+#define CBET_MESH_MAX_SUBSAMPLES 4
+#define CBET_MESH_DEPOSIT_AUTO 0
+#define CBET_MESH_DEPOSIT_GLOBAL 1
+#define CBET_MESH_DEPOSIT_LDS 2
+typedef struct cbet_mesh_cells {
+    double center[3];                       /* o (cm)                                                             */
+    int nr, ntheta, nphi;                   /* cells                                                              */
+    const double *r_edges, *theta_edges, *phi_edges;   /* HOST, nr + 1, ntheta + 1 (or NULL), nphi + 1 (or NULL) */
+} cbet_mesh_cells;
+typedef struct cbet_mesh_cells_handle cbet_mesh_cells_handle;
+int cbet_mesh_cells_create(cbet_mesh_cells_handle **out, const cbet_mesh_cells *cells, int subsamples_max, int gpu);
+void cbet_mesh_cells_destroy(cbet_mesh_cells_handle *handle);
+int cbet_mesh_deposit_device(const cbet_mesh_cells_handle *handle, const double *edep, int ngrids, long grid_stride,
+                             const cbet_params *p, int subsamples, int method, double *cell_energy, double *outside,
+                             long long *cell_samples, void *stream);
+int cbet_mesh_deposit(const cbet_mesh_cells_handle *handle, const double *edep, int ngrids, long grid_stride,
+                      const cbet_params *p, int subsamples, int method, double *cell_energy, double *outside,
+                      long long *cell_samples, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
