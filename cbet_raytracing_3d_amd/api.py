@@ -180,17 +180,26 @@ class Target(C.Structure):
 MESH_MAX_COORDS = 2560
 
 
+class MeshIons(C.Structure):
+    """cbet_mesh_ions: ion temperature (eV) and mean charge on a mesh's nodes, each an address or None (the gain
+    parameters' ti_ev / z_ion everywhere).  api.Mesh(..., ti=, zbar=) builds it (Mesh.ions) and keeps the arrays alive."""
+    _fields_ = [("ti", C.c_void_p), ("zbar", C.c_void_p)]
+
+
 class Mesh(C.Structure):
     """cbet_mesh: ne, te and optionally the velocity of a plasma on a spherical-polar mesh about `center` (cm).
     r [nr], theta [ntheta], phi [nphi]: node coordinates (theta / phi None: the state does not depend on that angle);
     ne, te: [nr, ntheta, nphi] (a 1-D or 2-D array is taken as [nr] / [nr, ntheta]); velocity: None, three arrays
-    (ur, uth, uph), each of the fields' shape or None (zero), or one array [3, nr, ntheta, nphi].  Numpy arrays make a HOST
-    mesh (mesh_check, mesh_tables, mesh_flow_table); to(device) uploads it once and returns the DEVICE mesh
-    (tabulate_mesh, tabulate_mesh_flow).  The struct keeps its arrays alive.  The library checks the values."""
+    (ur, uth, uph), each of the fields' shape or None (zero), or one array [3, nr, ntheta, nphi].  ti (eV), zbar: the ion
+    temperature and the mean charge for the gain kernels' state table, each of the fields' shape or None (the gain
+    parameters' value everywhere); they travel beside the struct (Mesh.ions, a MeshIons), which keeps cbet_mesh's layout.
+    Numpy arrays make a HOST mesh (mesh_check, mesh_tables, mesh_flow_table, mesh_state_table); to(device) uploads it once
+    and returns the DEVICE mesh (tabulate_mesh, tabulate_mesh_flow, tabulate_mesh_state).  The struct keeps its arrays
+    alive.  The library checks the values."""
     _fields_ = [("center", C.c_double * 3), ("nr", C.c_int), ("ntheta", C.c_int), ("nphi", C.c_int)] + \
                [(name, C.c_void_p) for name in ("r", "theta", "phi", "ne", "te", "ur", "uth", "uph")]
 
-    def __init__(self, r, theta, phi, ne, te, velocity=None, center=(0.0, 0.0, 0.0)):
+    def __init__(self, r, theta, phi, ne, te, velocity=None, center=(0.0, 0.0, 0.0), ti=None, zbar=None):
         super().__init__()
 
         def host(a):
@@ -215,14 +224,17 @@ class Mesh(C.Structure):
         if len(velocity) != 3:
             raise ValueError("mesh: velocity is (ur, uth, uph)")
         u = [None if c is None else field(c, name) for c, name in zip(velocity, ("ur", "uth", "uph"))]
-        self._set(center, shape, [r, theta, phi, field(ne, "ne"), field(te, "te")] + u)
+        self._set(center, shape, [r, theta, phi, field(ne, "ne"), field(te, "te")] + u,
+                  [None if a is None else field(a, name) for a, name in ((ti, "ti"), (zbar, "zbar"))])
 
-    def _set(self, center, shape, arrays):
+    def _set(self, center, shape, arrays, ions=(None, None)):
         self.center = (C.c_double * 3)(*[float(v) for v in center])
         self.nr, self.ntheta, self.nphi = shape
         self._keep = arrays
         for name, a in zip(("r", "theta", "phi", "ne", "te", "ur", "uth", "uph"), arrays):
             setattr(self, name, _addr(a))
+        self._ions = list(ions)         # (ti, zbar) beside the struct
+        self.ions = MeshIons(_addr(self._ions[0]), _addr(self._ions[1]))
 
     @property
     def shape(self):
@@ -237,7 +249,8 @@ class Mesh(C.Structure):
         import torch
         m = Mesh.__new__(Mesh)
         C.Structure.__init__(m)
-        m._set(self.center, self.shape, [None if a is None else torch.as_tensor(a).to(device) for a in self._keep])
+        up = lambda arrays: [None if a is None else torch.as_tensor(a).to(device) for a in arrays]      # noqa: E731
+        m._set(self.center, self.shape, up(self._keep), up(self._ions))
         return m
 
 
@@ -348,6 +361,7 @@ EXPORTS = [
     "cbet_tabulate_target", "cbet_target_tables",
     "cbet_tabulate_flow", "cbet_context_set_flow", "cbet_context_flow", "cbet_flow_table",
     "cbet_tabulate_mesh", "cbet_tabulate_mesh_flow", "cbet_mesh_check", "cbet_mesh_tables", "cbet_mesh_flow_table",
+    "cbet_tabulate_mesh_state", "cbet_context_set_state", "cbet_context_state", "cbet_mesh_state_table",
     "cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit",
 ]
 
@@ -445,6 +459,10 @@ def lib():
     L.cbet_mesh_check.argtypes = [C.POINTER(Mesh)]
     L.cbet_mesh_tables.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp, dp]
     L.cbet_mesh_flow_table.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp]
+    L.cbet_tabulate_mesh_state.argtypes = [vp, C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Mesh), C.POINTER(MeshIons), vp]
+    L.cbet_context_set_state.argtypes = [vp, vp]
+    L.cbet_context_state.argtypes = [vp, C.POINTER(vp)]
+    L.cbet_mesh_state_table.argtypes = [C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Mesh), C.POINTER(MeshIons), dp]
     L.cbet_mesh_cells_create.argtypes = [C.POINTER(vp), C.POINTER(MeshCellsStruct), C.c_int, C.c_int]
     L.cbet_mesh_cells_destroy.argtypes = [vp]
     L.cbet_mesh_cells_destroy.restype = None
@@ -587,6 +605,7 @@ class Context:
         self._h = C.c_void_p()
         self.gpu = gpu
         self._flow_ref = None           # set_flow(): the caller's table, kept alive
+        self._state_ref = None          # set_state(): likewise
         _check(lib().cbet_context_create(C.byref(self._h), C.byref(params), gpu))
 
     @property
@@ -631,6 +650,19 @@ class Context:
         """Device address of the flow table in use (tabulate_flow's or set_flow's), None if none -- for tests."""
         a = C.c_void_p()
         _check(lib().cbet_context_flow(self._h, C.byref(a)))
+        return a.value
+
+    def set_state(self, state):
+        """cbet_context_set_state: the gain updates of this context read the sound speed and gain_const from `state`, a
+        device table [2][nx][ny][nz] of doubles (a torch tensor, kept referenced here, or an address the caller keeps
+        alive); None = back to the scalars of the gain parameters."""
+        _check(lib().cbet_context_set_state(self._h, _addr(state)))
+        self._state_ref = state
+
+    def state(self):
+        """Device address of the state table in use (tabulate_mesh_state's or set_state's), None if none -- for tests."""
+        a = C.c_void_p()
+        _check(lib().cbet_context_state(self._h, C.byref(a)))
         return a.value
 
     def close(self):
@@ -716,6 +748,23 @@ def tabulate_mesh_flow(ctx, params, mesh, stream=None):
     updates then read.  The first call on a context allocates."""
     _check(lib().cbet_tabulate_mesh_flow(ctx.handle, C.byref(params), C.byref(mesh), _addr(stream)))
     ctx._flow_ref = None
+
+
+def tabulate_mesh_state(ctx, params, gain_params, mesh, stream=None, ions=True):
+    """cbet_tabulate_mesh_state: a DEVICE mesh's Te -- and its ti / zbar (Mesh.ions), where it has them; ions=False: the
+    gain parameters' ti_ev / z_ion whatever the mesh carries -- into the context's own state table (cs, gain_const), which
+    the context's gain updates then read.  The first call on a context allocates."""
+    _check(lib().cbet_tabulate_mesh_state(ctx.handle, C.byref(params), C.byref(gain_params), C.byref(mesh),
+                                          C.byref(mesh.ions) if ions else None, _addr(stream)))
+    ctx._state_ref = None
+
+
+def mesh_state_table(params, gain_params, mesh, ions=True):
+    """cbet_mesh_state_table, the host twin: numpy (2, nx, ny, nz) -- cs, gain_const at the nodes -- from a HOST mesh."""
+    out = np.empty((2, params.nx, params.ny, params.nz))
+    _check(lib().cbet_mesh_state_table(C.byref(params), C.byref(gain_params), C.byref(mesh),
+                                       C.byref(mesh.ions) if ions else None, _dptr(out)))
+    return out
 
 
 def mesh_check(mesh):

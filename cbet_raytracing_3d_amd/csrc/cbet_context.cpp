@@ -111,6 +111,7 @@ int cbet_context_destroy(cbet_context *ctx)
     (void)hipFree(ctx->live);
     (void)hipFree(ctx->counters);
     (void)hipFree(ctx->flow_own);
+    (void)hipFree(ctx->state_own);
     delete ctx;
     return CBET_OK;
 }
@@ -262,6 +263,20 @@ int cbet_context_flow(cbet_context *ctx, void **out)
 {
     if (!ctx || !out) return fail(CBET_EINVAL, "NULL context/out");
     *out = const_cast<double *>(ctx->flow);
+    return CBET_OK;
+}
+
+int cbet_context_set_state(cbet_context *ctx, const double *state)
+{
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    ctx->state = state;
+    return CBET_OK;
+}
+
+int cbet_context_state(cbet_context *ctx, void **out)
+{
+    if (!ctx || !out) return fail(CBET_EINVAL, "NULL context/out");
+    *out = const_cast<double *>(ctx->state);
     return CBET_OK;
 }
 

@@ -126,6 +126,7 @@ struct GainArgs {
     int frozen;                             // the direction entries already hold k (cbet_gain_params.directions_frozen)
     long store0, bstride;                   // whole-grid arrays: 0, hsize; slab-packed arrays: hx_lo * (ny+2)(nz+2), slab entries
     const double *flow;                     // [3][nx*ny*nz] node flow table (ux, uy, uz; cbet_tabulate_flow), or NULL: the closed-form ramp about the origin
+    const double *state;                    // [2][nx*ny*nz] node state table (cs, gain_const; cbet_tabulate_mesh_state), or NULL: the scalars cs / gain_const above
 };
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);
@@ -203,6 +204,11 @@ hipError_t launch_tabulate_flow(const FlowArgs &a, int inst, hipStream_t stream)
 // Plasma on a spherical-polar mesh (cbet_mesh.hip, cbet_mesh_host.cpp, cbet_mesh_model.h).
 // The kernels stage r, theta and phi in LDS; CBET_MESH_MAX_COORDS doubles (20 KiB) let eight 256-thread workgroups share
 // a CU's 160 KiB, which is the 32 waves a CU holds at most: the staging never costs occupancy.
+// The node-independent factors of the state model (cbet_state_model.h), cbet_gain_constants' own: E2 = pow(estat, 2),
+// A = 4 (1.0e3 me) c omega kb, F = 8 pi 1.0e7 / c and the ion mass in kg.
+struct StateConsts {
+    double e2, a, f, mi_kg;
+};
 struct MeshArgs {
     int nx, ny, nz;
     double xmin, ymin, zmin, dx, dy, dz, dt;
@@ -214,9 +220,15 @@ struct MeshArgs {
     const double *ur, *uth, *uph;           // the same shape, each may be NULL (zero)
     double *ne3d, *kap3d;                   // out of the table kernel, nx*ny*nz each
     double *flow;                           // out of the flow kernel, [3][nx*ny*nz]: ux, uy, uz
+    // the state kernel's (appended: the members above keep their places)
+    const double *ti, *zbar;                // the fields' shape, each may be NULL (ti0 / z0 everywhere)
+    double ti0, z0;                         // cbet_gain_params.ti_ev / z_ion
+    StateConsts sc;
+    double *state;                          // out of the state kernel, [2][nx*ny*nz]: cs, gain_const
 };
 hipError_t launch_tabulate_mesh(const MeshArgs &a, hipStream_t stream);   // k_tabulate_mesh: a.ne3d / a.kap3d
 hipError_t launch_mesh_flow(const MeshArgs &a, hipStream_t stream);       // k_mesh_flow: a.flow
+hipError_t launch_mesh_state(const MeshArgs &a, hipStream_t stream);      // k_mesh_state: a.state
 
 // Deposit on the hydro mesh (cbet_mesh_deposit.hip, cbet_mesh_deposit_host.cpp, cbet_mesh_deposit_model.h; DESIGN.md
 // section 15).  The four lookup tables are the handle's: device copies for the kernel, host copies for the twin.

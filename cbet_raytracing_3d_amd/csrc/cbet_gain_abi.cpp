@@ -31,6 +31,7 @@ int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, doub
     a.frozen = g->directions_frozen ? 1 : 0;
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
     a.flow = ctx->flow;
+    a.state = ctx->state;
     a.store0 = packed ? (long)hx_lo * plane : 0;
     a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
     if (hx_hi == hx_lo) return CBET_OK;   // an empty slab (more ranks than planes)
@@ -115,6 +116,9 @@ int cbet_cbet_solve(double *te_data_g, double *r_data_g, double *ne_data_g, doub
     if (ctx->flow)   // this loop tabulates the radial plasma about the origin itself: it does not mix that with another flow
         return fail(CBET_EINVAL, "cbet_cbet_solve models a spherical target about the origin: the context has a flow table "
                                  "selected (cbet_context_set_flow(ctx, NULL), or the loop above the C ABI: tracer.cbet_solve)");
+    if (ctx->state)   // ... and its gain constants are cbet_gain_params' own, everywhere
+        return fail(CBET_EINVAL, "cbet_cbet_solve takes the sound speed and the gain constant from the gain parameters: the context "
+                                 "has a state table selected (cbet_context_set_state(ctx, NULL), or the loop above the C ABI: tracer.cbet_solve)");
     const cbet_derived &d = ctx->d;
     hipStream_t s = (hipStream_t)stream;
     CBET_ENTER_DEVICE(ctx);

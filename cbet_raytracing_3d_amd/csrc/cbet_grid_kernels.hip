@@ -19,11 +19,13 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 struct CellState {
     double frac, eps, rt, ux, uy, uz;   // ne/ncrit, 1 - ne/ncrit, sqrt(eps), flow velocity
+    double cs, gc;                      // sound speed and gain_const: the node's (STATE) or the uniform ones
 };
 
 // FLOW: the flow velocity is read from GainArgs.flow (a node table, cbet_target.hip k_tabulate_flow) instead of the closed-form radial
-// ramp about the origin.
-template <bool FLOW>
+// ramp about the origin.  STATE: the sound speed and gain_const are read from GainArgs.state (a node table, cbet_mesh.hip k_mesh_state)
+// instead of the uniform GainArgs.cs / gain_const.
+template <bool FLOW, bool STATE>
 __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
 {
     const int sYh = a.nz + 2;
@@ -38,6 +40,14 @@ __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
     c.frac = a.ne3d[((long)i * a.ny + j) * a.nz + k] / a.ncrit;
     c.eps = 1.0 - c.frac;
     c.rt = c.eps > 0.0 ? sqrt(c.eps) : 0.0;
+    if (STATE) {
+        const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
+        c.cs = a.state[node];
+        c.gc = a.state[node + nodes];
+    } else {
+        c.cs = a.cs;
+        c.gc = a.gain_const;
+    }
     if (FLOW) {
         const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
         c.ux = a.flow[node];
@@ -52,7 +62,7 @@ __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
 }
 
 // The prefactor of a cell's pair gains, gain_const (ne / ncrit) / (iaw sqrt(eps)); zero at and above critical density.
-__device__ __forceinline__ double cell_pref(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? a.gain_const * c.frac * (1.0 / a.iaw) / c.rt : 0.0; }
+__device__ __forceinline__ double cell_pref(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? c.gc * c.frac * (1.0 / a.iaw) / c.rt : 0.0; }
 
 // The epilogue of both gain kernels: the wave's sums of |new - old| and |new| into GainArgs.change, two atomics per wave.
 __device__ __forceinline__ void report_change(const GainArgs &a, int lane, double sum_change, double sum_abs)
@@ -104,7 +114,7 @@ __device__ __forceinline__ void normalise_entry(const GainArgs &a, const CellSta
 //            beam is not present (E <= 0); with GainArgs.frozen only the energy entry (normalise_entry).
 //   phase 2: K_i = sum_{j != i} G_ij I_j, beams in increasing order; gain <- gain + relax (K - gain),
 //            stored only where it changes.
-template <bool FLOW>
+template <bool FLOW, bool STATE>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
     const int HY = a.ny + 2, HZ = a.nz + 2;
@@ -127,7 +137,7 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
         const long h = valid ? ((long)hi * HY + hj) * HZ + hk : a.store0;
         const long hs = h - a.store0;               // index into the (possibly slab-packed) arrays
         double *fI = a.fields + hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
-        const CellState c = cell_state<FLOW>(a, h);
+        const CellState c = cell_state<FLOW, STATE>(a, h);
         const double kmag = a.k0 * c.rt;
         const double ds_node = (kC * c.rt) * a.dt;  // group speed x dt: energy x length -> intensity
         unsigned long long mask = 0ull;             // beams present in some cell of this brick
@@ -155,7 +165,7 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
                     const double qx = fx[oj] - kxi, qy = fy[oj] - kyi, qz = fz[oj] - kzi;
                     const double kiaw = sqrt(qx * qx + qy * qy + qz * qz);
                     if (valid && Ii > 0.0 && Ij > 0.0 && kiaw > 0.0) {
-                        const double eta = (0.0 - (qx * c.ux + qy * c.uy + qz * c.uz)) / (kiaw * a.cs + 1e-10);
+                        const double eta = (0.0 - (qx * c.ux + qy * c.uy + qz * c.uz)) / (kiaw * c.cs + 1e-10);
                         const double e2 = eta * eta;
                         const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
                         acc += pref * P * Ij;
@@ -253,9 +263,16 @@ __device__ __forceinline__ void lds_order()
     __builtin_amdgcn_wave_barrier();
 }
 
-template <bool FROZEN, bool FLOW>
+// STATE (the cell's own sound speed, cell_state): cs is one more per-lane value of the 64-cell state block and of the pair
+// loop, where the uniform one sits in scalar registers.  The 168 registers have no room for it -- the instantiations without
+// STATE already keep some loop invariants in scratch -- so the STATE arm gives registers back where they are cheapest: the
+// sixteen per-lane beam offsets of the mask loads are formed per run instead of once per kernel (hs0, the trick of hs1 and
+// hs3), and the first call's arm (not FROZEN: once per solve) keeps three rounds of phase 1 and four of phase 3 in flight
+// instead of four and eight.  None of this reorders a sum: no scratch in any STATE instantiation.
+template <bool FROZEN, bool FLOW, bool STATE>
 __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 {
+    constexpr int PCH = (STATE && !FROZEN) ? 3 : LCH, QCH = (STATE && !FROZEN) ? 4 : LCH3;
     static_assert(5 * LCAP * LC >= 64 * (LC + 1), "the slot arrays double as the staging area of the presence masks");
     __shared__ double lds[5 * LCAP * LC];
     double *const sI = lds, *const sX = sI + LCAP * LC, *const sY = sX + LCAP * LC, *const sZ = sY + LCAP * LC,
@@ -268,7 +285,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
     const double iaw2 = a.iaw * a.iaw;
     const int rounds = (a.nbeams + LG - 1) / LG;
     double sum_change = 0.0, sum_abs = 0.0;
-    double st_rt = 0.0, st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_pref = 0.0;
+    double st_rt = 0.0, st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_pref = 0.0, st_cs = 0.0;
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {
         const int hi = a.hx_lo + (int)(row / HY), hj = (int)(row % HY);
         // runs start on 128-byte lines of the arrays, not at z = 16 k of the row: the row's first entry sits `sft` doubles into
@@ -289,10 +306,12 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             unsigned long long mask = 0ull, touched = 0ull;
             {
                 double E[LROUNDS];
+                long hs0 = hsize;
+                if (STATE) asm volatile("" : "+s"(hs0));   // opaque: the sixteen offsets below are formed here, not kept across the kernel
 #pragma unroll
                 for (int r = 0; r < LROUNDS; ++r) {
                     const int b = LG * r + g;
-                    E[r] = (r < rounds && b < a.nbeams && valid) ? fI[(long)b * hsize] : 0.0;
+                    E[r] = (r < rounds && b < a.nbeams && valid) ? fI[(long)b * hs0] : 0.0;
                 }
                 __syncthreads();                 // the previous run's LDS reads are done
 #pragma unroll
@@ -309,14 +328,16 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             // the plasma state of 64 cells at a time (lane = cell), handed to the four runs they make up
             if ((ibz & 3) == 0) {
                 const int hk64 = LC * ibz + lane - sft;
-                const CellState c64 = cell_state<FLOW>(a, ((long)hi * HY + hj) * HZ + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                const CellState c64 = cell_state<FLOW, STATE>(a, ((long)hi * HY + hj) * HZ + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
                 st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
                 st_pref = cell_pref(a, c64);
+                if (STATE) st_cs = c64.cs;
             }
             const int from = LC * (ibz & 3) + c;
             const double rt = __shfl(st_rt, from, kWave), ux = __shfl(st_ux, from, kWave), uy = __shfl(st_uy, from, kWave),
                          uz = __shfl(st_uz, from, kWave);
             const double pref = valid ? __shfl(st_pref, from, kWave) : 0.0;
+            const double cs = STATE ? __shfl(st_cs, from, kWave) : a.cs;   // the cell's own, or the uniform one (scalar registers)
             const bool subcritical = rt > 0.0;   // eps > 0
             const double kmag = a.k0 * rt;
             const double ds_node = (kC * rt) * a.dt;
@@ -333,10 +354,10 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                     asm volatile("" : "+s"(hs1));
                     unsigned long long tm = touched;
                     while (tm != 0ull) {
-                        int bb[LCH];
-                        double E[LCH], X[LCH], Y[LCH], Z[LCH];
+                        int bb[PCH];
+                        double E[PCH], X[PCH], Y[PCH], Z[PCH];
 #pragma unroll
-                        for (int u = 0; u < LCH; ++u) {
+                        for (int u = 0; u < PCH; ++u) {
                             int bq[LG];
 #pragma unroll
                             for (int q = 0; q < LG; ++q) {
@@ -354,7 +375,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             Z[u] = in ? fz[o] : 0.0;
                         }
 #pragma unroll
-                        for (int u = 0; u < LCH; ++u) {
+                        for (int u = 0; u < PCH; ++u) {
                             const int b = bb[u];
                             const long o = (long)b * hs1;
                             double I = 0.0;
@@ -405,8 +426,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             S.I = sI[self]; S.kx = sX[self]; S.ky = sY[self]; S.kz = sZ[self];
                             P1.I = sI[p1]; P1.kx = sX[p1]; P1.ky = sY[p1]; P1.kz = sZ[p1];
                             P2.I = sI[p2]; P2.kx = sX[p2]; P2.ky = sY[p2]; P2.kz = sZ[p2];
-                            const double g1 = pair_gain_fast(S, P1, ux, uy, uz, a.cs, iaw2, pref_iaw2);
-                            const double g2 = g < 2 ? pair_gain_fast(S, P2, ux, uy, uz, a.cs, iaw2, pref_iaw2) : 0.0;
+                            const double g1 = pair_gain_fast(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2);
+                            const double g2 = g < 2 ? pair_gain_fast(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2) : 0.0;
                             sR[self] += g1 * P1.I + g2 * P2.I;
                             lds_order();             // the next statement's entries are other lanes' `self`
                             sR[p1] -= g1 * S.I;
@@ -430,7 +451,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             double KB = 0.0;
 #pragma unroll
                             for (int s_ = 0; s_ < LG; ++s_) {
-                                const double gn = pair_gain_fast(A[s_], B, ux, uy, uz, a.cs, iaw2, pref_iaw2);
+                                const double gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
                                 KA[s_] += gn * B.I;
                                 KB -= gn * A[s_].I;
                             }
@@ -453,15 +474,15 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                 if (mine_ && valid) {
                     long hs3 = hsize;
                     asm volatile("" : "+s"(hs3));
-                    for (int r0 = 0; r0 < rounds; r0 += LCH3) {
-                        double old[LCH3];
+                    for (int r0 = 0; r0 < rounds; r0 += QCH) {
+                        double old[QCH];
 #pragma unroll
-                        for (int u = 0; u < LCH3; ++u) {
+                        for (int u = 0; u < QCH; ++u) {
                             const int b = LG * (r0 + u) + g;
                             old[u] = b < a.nbeams ? a.gain[(long)b * hs3 + hs] : 0.0;
                         }
 #pragma unroll
-                        for (int u = 0; u < LCH3; ++u) {
+                        for (int u = 0; u < QCH; ++u) {
                             const int b = LG * (r0 + u) + g;
                             if (b >= a.nbeams) continue;
                             double raw = 0.0;
@@ -589,20 +610,32 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
         const dim3 grid((unsigned)rows), block(64);
-        if (a.flow) {
-            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, true>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((k_gain_field_sym<false, true>), grid, block, 0, stream, a);
+        if (a.state) {
+            if (a.flow) {
+                if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, true, true>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((k_gain_field_sym<false, true, true>), grid, block, 0, stream, a);
+            } else {
+                if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, false, true>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((k_gain_field_sym<false, false, true>), grid, block, 0, stream, a);
+            }
+        } else if (a.flow) {
+            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, true, false>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_gain_field_sym<false, true, false>), grid, block, 0, stream, a);
         } else {
-            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, false>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((k_gain_field_sym<false, false>), grid, block, 0, stream, a);
+            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, false, false>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_gain_field_sym<false, false, false>), grid, block, 0, stream, a);
         }
         return hipGetLastError();
     }
     const long bricks = (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8);  // 2 x 4 x 8 cells of the haloed grid each
     long blocks = (bricks + 3) / 4;                                                    // four wavefronts per workgroup
     if (blocks > 256 * 64) blocks = 256 * 64;
-    if (a.flow) hipLaunchKernelGGL(k_gain_field<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(k_gain_field<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (a.state) {
+        if (a.flow) hipLaunchKernelGGL((k_gain_field<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_gain_field<false, true>), grid, block, 0, stream, a);
+    } else if (a.flow) hipLaunchKernelGGL((k_gain_field<true, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((k_gain_field<false, false>), grid, block, 0, stream, a);
     return hipGetLastError();
 }
 

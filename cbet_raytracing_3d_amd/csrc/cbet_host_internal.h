@@ -30,6 +30,9 @@ struct cbet_context {
     // flow table of the gain kernels (cbet_tabulate_flow / cbet_context_set_flow): NULL = the closed-form ramp
     double *flow_own = nullptr;         // the context's own [3][nx*ny*nz] table, allocated by the first cbet_tabulate_flow
     const double *flow = nullptr;       // the table in use: flow_own, a caller's, or NULL
+    // state table of the gain kernels (cbet_tabulate_mesh_state / cbet_context_set_state): NULL = the scalars cs, gain_const
+    double *state_own = nullptr;        // the context's own [2][nx*ny*nz] table, allocated by the first cbet_tabulate_mesh_state
+    const double *state = nullptr;      // the table in use: state_own, a caller's, or NULL
 };
 
 namespace cbet {
@@ -80,6 +83,8 @@ int validate_gain(const cbet_params *p, const cbet_gain_params *g);
 int derive_grid(const cbet_params *p, cbet_derived *d);
 int derive_launch(const cbet_params *p, cbet_derived *d, std::vector<double> &xl, std::vector<double> &yl,
                   std::vector<int> &live);
+// The state model's four host factors (cbet_state_model.h), beside cbet_gain_constants; validates p and g.
+int state_consts(const cbet_params *p, const cbet_gain_params *g, StateConsts *out);
 
 // ---- cbet_context.cpp -------------------------------------------------------------------------------------
 int check_geometry(const cbet_context *ctx, const cbet_params *p);  // the launch describes the geometry ctx was sized for
@@ -122,14 +127,20 @@ TabulateArgs tabulate_args(const cbet_params *p, const cbet_derived &d, double *
 // k_tabulate_flow's and its host twin's (cbet_target_host.cpp); target NULL = the sphere about the origin.
 FlowArgs flow_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs,
                    const cbet_target *target, double *out);
-// k_tabulate_mesh's, k_mesh_flow's and their host twins' (cbet_mesh_host.cpp): the outputs a launch does not write stay NULL.
+// k_tabulate_mesh's, k_mesh_flow's, k_mesh_state's and their host twins' (cbet_mesh_host.cpp): the outputs a launch does
+// not write stay NULL.  mesh_state_args: the state kernel's members on top (ions may be NULL).
 MeshArgs mesh_args(const cbet_params *p, const cbet_derived &d, const cbet_mesh *mesh, double *ne3d, double *kap3d,
                    double *flow);
+MeshArgs mesh_state_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, const StateConsts &sc,
+                         const cbet_mesh *mesh, const cbet_mesh_ions *ions, double *state);
 // The mesh's sizes and NULL pointers (all a device entry can check); whole: the values too (HOST arrays).
 int mesh_check(const cbet_mesh *mesh, bool whole);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
-int flow_own_table(cbet_context *ctx, const cbet_params *p);   // cbet_tabulate_flow's and cbet_tabulate_mesh_flow's first call
+// The context's own table of `components` doubles per node in *slot, allocated on the first call (not capturable).
+int own_node_table(double **slot, const cbet_params *p, int components, const char *what);
+inline int flow_own_table(cbet_context *ctx, const cbet_params *p) { return own_node_table(&ctx->flow_own, p, 3, "flow table"); }     // cbet_tabulate_flow, cbet_tabulate_mesh_flow
+inline int state_own_table(cbet_context *ctx, const cbet_params *p) { return own_node_table(&ctx->state_own, p, 2, "state table"); }  // cbet_tabulate_mesh_state
 int step_records(cbet_context *ctx, const cbet_params *p, const double *ne3d, const double *kappa3d, double xconst,
                  double yconst, double zconst, void *stream, bool force);
 // CBET hooks of a trace launch (all zero: the reference path).

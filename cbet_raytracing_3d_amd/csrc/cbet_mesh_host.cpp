@@ -1,6 +1,7 @@
 // cbet_mesh_host.cpp -- plasma on a spherical-polar mesh (include/cbet_mi355x.h "hydro-mesh plasma", DESIGN.md section
-// 14): the checks of a mesh, the argument block, the entry points of k_tabulate_mesh and k_mesh_flow (cbet_mesh.hip) and
-// their host twins, plain loops over the nodes running the kernels' own statements (cbet_mesh_model.h).
+// 14, the state table of section 16): the checks of a mesh, the argument block, the entry points of k_tabulate_mesh,
+// k_mesh_flow and k_mesh_state (cbet_mesh.hip) and their host twins, plain loops over the nodes running the kernels' own
+// statements (cbet_mesh_model.h).
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -80,16 +81,31 @@ MeshArgs mesh_args(const cbet_params *p, const cbet_derived &d, const cbet_mesh 
     return a;
 }
 
+MeshArgs mesh_state_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, const StateConsts &sc,
+                         const cbet_mesh *m, const cbet_mesh_ions *ions, double *state)
+{
+    MeshArgs a = mesh_args(p, d, m, nullptr, nullptr, nullptr);
+    a.ti = ions ? ions->ti : nullptr;
+    a.zbar = ions ? ions->zbar : nullptr;
+    a.ti0 = g->ti_ev; a.z0 = g->z_ion;
+    a.sc = sc;
+    a.state = state;
+    return a;
+}
+
 namespace {
 
-template <bool FLOW>
+enum HostOut { kHostTables, kHostFlow, kHostState };
+
+template <HostOut OUT>
 void host_mesh(const MeshArgs &a)
 {
     const long nodes = (long)a.nx * a.ny * a.nz;
     for_each_node_host(a.nx, a.ny, a.nz, [&](int i, int j, int k, long idx) {
         MeshNode n;
         mesh_locate(a, a.r, a.theta, a.phi, i, j, k, n);
-        if (FLOW) mesh_velocity(a, n, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes]);
+        if (OUT == kHostFlow) mesh_velocity(a, n, a.flow[idx], a.flow[idx + nodes], a.flow[idx + 2 * nodes]);
+        else if (OUT == kHostState) mesh_state(a, n, a.state[idx], a.state[idx + nodes]);
         else mesh_tables(a, n, a.ne3d[idx], a.kap3d[idx]);
     });
 }
@@ -122,6 +138,20 @@ int cbet_tabulate_mesh_flow(cbet_context *ctx, const cbet_params *p, const cbet_
     return CBET_OK;
 }
 
+int cbet_tabulate_mesh_state(cbet_context *ctx, const cbet_params *p, const cbet_gain_params *g, const cbet_mesh *mesh,
+                             const cbet_mesh_ions *ions, void *stream)
+{
+    if (int rc = entry_checks(ctx, p)) return rc;
+    StateConsts sc;
+    if (int rc = state_consts(p, g, &sc)) return rc;   // (validates the gain parameters)
+    if (int rc = mesh_check(mesh, false)) return rc;
+    CBET_ENTER_DEVICE(ctx);
+    if (int rc = state_own_table(ctx, p)) return rc;
+    CBET_HIP(launch_mesh_state(mesh_state_args(p, ctx->d, g, sc, mesh, ions, ctx->state_own), (hipStream_t)stream));
+    ctx->state = ctx->state_own;
+    return CBET_OK;
+}
+
 int cbet_mesh_check(const cbet_mesh *mesh) { return mesh_check(mesh, true); }
 
 int cbet_mesh_tables(const cbet_params *p, const cbet_mesh *mesh, double *ne3d, double *kappa3d)
@@ -130,7 +160,7 @@ int cbet_mesh_tables(const cbet_params *p, const cbet_mesh *mesh, double *ne3d, 
     if (int rc = derive_grid(p, &d)) return rc;
     if (!ne3d || !kappa3d) return fail(CBET_EINVAL, "mesh_tables: NULL output");
     if (int rc = mesh_check(mesh, true)) return rc;
-    host_mesh<false>(mesh_args(p, d, mesh, ne3d, kappa3d, nullptr));
+    host_mesh<kHostTables>(mesh_args(p, d, mesh, ne3d, kappa3d, nullptr));
     return CBET_OK;
 }
 
@@ -140,7 +170,26 @@ int cbet_mesh_flow_table(const cbet_params *p, const cbet_mesh *mesh, double *fl
     if (int rc = derive_grid(p, &d)) return rc;
     if (!flow) return fail(CBET_EINVAL, "mesh_flow_table: NULL output");
     if (int rc = mesh_check(mesh, true)) return rc;
-    host_mesh<true>(mesh_args(p, d, mesh, nullptr, nullptr, flow));
+    host_mesh<kHostFlow>(mesh_args(p, d, mesh, nullptr, nullptr, flow));
+    return CBET_OK;
+}
+
+int cbet_mesh_state_table(const cbet_params *p, const cbet_gain_params *g, const cbet_mesh *mesh, const cbet_mesh_ions *ions,
+                          double *out)
+{
+    cbet_derived d;
+    if (int rc = derive_grid(p, &d)) return rc;
+    StateConsts sc;
+    if (int rc = state_consts(p, g, &sc)) return rc;   // (validates the gain parameters)
+    if (!out) return fail(CBET_EINVAL, "mesh_state_table: NULL output");
+    if (int rc = mesh_check(mesh, true)) return rc;
+    const long n = (long)mesh->nr * mesh->ntheta * mesh->nphi;
+    long bad;
+    if (ions && ions->ti && (bad = first_bad(ions->ti, n, 0.0, false)) >= 0)
+        return fail(CBET_EINVAL, "mesh ions: ti[%ld] = %g (finite and >= 0)", bad, ions->ti[bad]);
+    if (ions && ions->zbar && (bad = first_bad(ions->zbar, n, 0.0, true)) >= 0)
+        return fail(CBET_EINVAL, "mesh ions: zbar[%ld] = %g (finite and > 0)", bad, ions->zbar[bad]);
+    host_mesh<kHostState>(mesh_state_args(p, d, g, sc, mesh, ions, out));
     return CBET_OK;
 }
 

@@ -17,6 +17,7 @@
 
 #include "cbet_device.h"
 #include "cbet_node_model.h"
+#include "cbet_state_model.h"
 
 namespace cbet {
 
@@ -114,6 +115,16 @@ CBET_HD void mesh_velocity(const MeshArgs &a, const MeshNode &n, double &ux, dou
     ux = h * c1 - uph * s1;
     uy = h * s1 + uph * c1;
     uz = ur * ct - uth * st;
+}
+
+// The node's local plasma state for the gain kernels: Te of the mesh, Ti and Z of the mesh or (NULL arrays) of the gain
+// parameters, then the state model (cbet_state_model.h).
+CBET_HD void mesh_state(const MeshArgs &a, const MeshNode &n, double &cs, double &gc)
+{
+    const double te = mesh_value(a, a.te, n);
+    const double ti = a.ti ? mesh_value(a, a.ti, n) : a.ti0;
+    const double z = a.zbar ? mesh_value(a, a.zbar, n) : a.z0;
+    state_model(a.sc, te, ti, z, cs, gc);
 }
 
 }  // namespace cbet

@@ -408,6 +408,26 @@ int cbet_gain_constants(const cbet_params *p, const cbet_gain_params *g, double 
     return CBET_OK;
 }
 
+}  // extern "C"
+
+// The node-independent factors of the state model (cbet_state_model.h), each computed as cbet_gain_constants above computes it.
+int cbet::state_consts(const cbet_params *p, const cbet_gain_params *g, StateConsts *out)
+{
+    if (int rc = validate(p)) return rc;
+    if (int rc = validate_gain(p, g)) return rc;
+    cbet_derived d;
+    derive_core(p, &d);
+    const double estat = 4.80320427e-10;            // def.cuh:98
+    const double kb = 1.3806485279e-16;             // def.cuh:108
+    out->e2 = std::pow(estat, 2);
+    out->a = 4 * (1.0e3 * kMe) * kC * d.omega * kb;
+    out->f = 8.0 * M_PI * 1.0e7 / kC;
+    out->mi_kg = g->mi_over_me * kMe;               // def.cuh:102
+    return CBET_OK;
+}
+
+extern "C" {
+
 size_t cbet_cbet_slab_workspace_bytes_parts(const cbet_params *p, int own_beams, int own_planes, size_t staging_doubles)
 {
     if (!p || validate(p) != CBET_OK || own_beams < 0 || own_beams > p->nbeams || own_planes < 0 || own_planes > p->nx + 2) return 0;

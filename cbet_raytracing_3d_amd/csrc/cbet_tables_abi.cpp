@@ -48,15 +48,16 @@ int cbet::step_records(cbet_context *ctx, const cbet_params *p, const double *ne
     return CBET_OK;
 }
 
-// The context's own flow table, allocated by the first call on a context (not capturable).  The context's device is current.
-int cbet::flow_own_table(cbet_context *ctx, const cbet_params *p)
+// A context's own flow or state table, allocated by the first call on a context (not capturable).  The context's device is
+// current.
+int cbet::own_node_table(double **slot, const cbet_params *p, int components, const char *what)
 {
-    if (ctx->flow_own) return CBET_OK;
+    if (*slot) return CBET_OK;
     const size_t nodes = (size_t)p->nx * p->ny * p->nz;
-    hipError_t e = hipMalloc((void **)&ctx->flow_own, 3 * nodes * sizeof(double));
+    hipError_t e = hipMalloc((void **)slot, components * nodes * sizeof(double));
     if (e != hipSuccess) {
-        ctx->flow_own = nullptr;
-        return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(flow table): %s", hipGetErrorString(e));
+        *slot = nullptr;
+        return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(%s): %s", what, hipGetErrorString(e));
     }
     return CBET_OK;
 }

@@ -70,6 +70,8 @@ class RayTracer:
         self._mesh_cells = None
         self.flow = None                # set_flow(): None, "target", "mesh" or the caller's [3, nx, ny, nz] table
         self._flow_gp = None            # the gain parameters a "target" flow is tabulated from
+        self.gain_state = None          # set_gain_state(): None, "mesh" or the caller's [2, nx, ny, nz] table
+        self._state_gp = None           # the gain parameters a "mesh" state takes ti_ev, z_ion and mi_over_me from
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     # ---- the one spelling of what every launch repeats -------------------------------------------------------------
@@ -101,6 +103,7 @@ class RayTracer:
         else:
             api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
         self._tabulate_flow(ctx, params)
+        self._tabulate_state(ctx, params)
 
     def _tabulate_other(self, ctx, params):
         """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False
@@ -114,7 +117,8 @@ class RayTracer:
         return True
 
     # ---- hydro-mesh plasma (include/cbet_mi355x.h cbet_tabulate_mesh) -------------------------
-    def set_plasma_mesh(self, r, theta=None, phi=None, ne=None, te=None, velocity=None, center=(0.0, 0.0, 0.0)):
+    def set_plasma_mesh(self, r, theta=None, phi=None, ne=None, te=None, velocity=None, center=(0.0, 0.0, 0.0), ti=None,
+                        zbar=None):
         """Take the plasma from a hydrodynamics state on a spherical-polar mesh about `center` (cm) instead of the radial
         profiles: r [nr], theta [ntheta], phi [nphi] node coordinates (None: no dependence on that angle), ne (cm^-3) and
         te (the profiles' units) [nr, ntheta, nphi], velocity None or (ur, uth, uph) in cm/s (api.Mesh: numpy arrays or
@@ -122,20 +126,26 @@ class RayTracer:
         tabulate(), launch(), trace_exits() and the pipeline's passes then fill the context's node tables with
         cbet_tabulate_mesh and trace those.  set_plasma_mesh(None) goes back to the profiles.  A mesh and a target exclude
         each other.  The CBET stage refuses a mesh while no flow is set, as it refuses a target: set_flow("mesh") gives it
-        the mesh's own velocity."""
+        the mesh's own velocity.  ti (eV), zbar: the ion temperature and the mean charge on the mesh's nodes, each None or
+        of the fields' shape, for set_gain_state("mesh"), which gives the gain kernels the local sound speed and gain
+        constant; te must then be in eV (as the s83177 profile is) for that state to mean anything."""
         if r is None:
             self._drop_mesh_cells()
             self.mesh = None
             if self._flow_is("mesh"):
                 self.set_flow(None)
+            if self._state_is_mesh():
+                self.set_gain_state(None)
             return
         if self.target is not None:
             raise ValueError("set_plasma_mesh: a target is set (set_target(None) first): a mesh and a target exclude each other")
         if ne is None or te is None:
             raise ValueError("set_plasma_mesh: ne and te are required")
-        host = api.Mesh(r, theta, phi, ne, te, velocity, center)
+        host = api.Mesh(r, theta, phi, ne, te, velocity, center, ti=ti, zbar=zbar)
         try:
             api.mesh_check(host)
+            if ti is not None or zbar is not None:      # the host twin's checks of the two arrays, on a grid of a few nodes
+                api.mesh_state_table(api.default_params(8, nbeams=1), api.default_gain_params(), host)
         except api.CbetError as e:
             raise ValueError(str(e)) from None
         if self._flow_is("mesh") and not host.has_velocity:
@@ -211,6 +221,45 @@ class RayTracer:
         elif isinstance(self.flow, str):
             api.tabulate_flow(ctx, params, self._flow_gp, self.target, self._stream())
 
+    # ---- local plasma state of the CBET stage (include/cbet_mi355x.h cbet_tabulate_mesh_state) --
+    def set_gain_state(self, mode=None, gain_params=None):
+        """Where the gain kernels take the sound speed and the gain constant from.
+        None (the default): the scalars of the gain parameters (te_ev, ti_ev, z_ion: one state for the whole plasma).
+        "mesh": the local state of the current plasma mesh (set_plasma_mesh: its te in eV, its ti and zbar where it has
+        them; cbet_tabulate_mesh_state), tabulated whenever the node tables are -- tabulate(), the pipeline's preparation,
+        cbet_solve's start; ti_ev and z_ion for the arrays the mesh lacks, and mi_over_me, come from `gain_params` (default
+        api.default_gain_params(); cbet_solve puts its own in their place).  An error without a mesh.
+        A float64 tensor [2, nx, ny, nz] on this device: the caller's own table (cs in cm/s, gain_const), kept referenced
+        here and read as it is at every gain update.
+        The flow is a separate choice (set_flow): the closed-form ramp and a "target" flow keep the scalar sound speed."""
+        if mode is None:
+            self.gain_state, self._state_gp = None, None
+            self.ctx.set_state(None)
+            return
+        if isinstance(mode, str):
+            if mode != "mesh":
+                raise ValueError('set_gain_state: None, "mesh" or a [2, nx, ny, nz] tensor, got %r' % (mode,))
+            if self.mesh is None:
+                raise ValueError('set_gain_state("mesh"): no plasma mesh is set (set_plasma_mesh)')
+            self.ctx.set_state(None)                    # until the next tabulate() fills and selects the context's table
+            self.gain_state = "mesh"
+            self._state_gp = self._copy_gp(api.default_gain_params() if gain_params is None else gain_params)
+            return
+        _require(mode, (2, self.params.nx, self.params.ny, self.params.nz), "gain state")
+        if mode.device != self.device:
+            raise ValueError("gain state must be on %s" % self.device)
+        self.gain_state, self._state_gp = mode, None
+        self.ctx.set_state(mode)
+
+    def _state_is_mesh(self):
+        return isinstance(self.gain_state, str)
+
+    def _tabulate_state(self, ctx=None, params=None):
+        """A "mesh" state into `ctx` (default: this tracer's context) on torch's current stream; nothing otherwise."""
+        if self._state_is_mesh():
+            api.tabulate_mesh_state(self.ctx if ctx is None else ctx, self.params if params is None else params,
+                                    self._state_gp, self.mesh, self._stream())
+
     def _no_target(self, what):
         if self.flow is not None:
             return
@@ -270,6 +319,7 @@ class RayTracer:
         if not self._tabulate_other(self.ctx, self.params):
             api.tabulate_plasma(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self._stream())
         self._tabulate_flow()
+        self._tabulate_state()
 
     def launch_cbet(self, out, gain_params, fields=False, gain=None, beam_gain=None, shard_index=0,
                     shard_count=1, ne3d=None, kappa3d=None, beam_lo=0, beam_hi=None, grid_beam0=0, grid_beams=0):
@@ -316,7 +366,10 @@ class RayTracer:
         frozen: fields[1:4] already hold k from an earlier call; only fields[0] is read and normalised.
         With a flow set (set_flow) the update reads it; a "target" flow is the one the last tabulate() wrote, from the
         ramp of set_flow's gain parameters -- `gain_params` must carry the same ramp; a "mesh" flow is the mesh's velocity
-        as the last tabulate() wrote it."""
+        as the last tabulate() wrote it.  With a gain state set (set_gain_state) the update reads the sound speed and the gain
+        constant from it; a "mesh" state is the one the last tabulate() wrote."""
+        if self._state_is_mesh() and self.ctx.state() is None:
+            raise ValueError("gain_field: set_gain_state(\"mesh\") needs tabulate() before the first gain update")
         if isinstance(self.flow, str):
             ramp = lambda g: (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)  # noqa: E731
             if self._flow_is("target") and ramp(gain_params) != ramp(self._flow_gp):
@@ -340,6 +393,8 @@ class RayTracer:
         self._no_target("cbet_solve")
         if self._flow_is("target"):
             self._flow_gp = self._copy_gp(gain_params)      # the engine's tabulate() fills the flow table from this ramp
+        if self._state_is_mesh():
+            self._state_gp = self._copy_gp(gain_params)     # ... and the state table with these ti_ev, z_ion and mi_over_me
         engine = _DeviceCbetEngine(self, edep, gain_params, fields, gain)
         engine.force_collectives = force_collectives
         if slabs:

@@ -604,6 +604,60 @@ int cbet_tabulate_mesh_flow(cbet_context *ctx, const cbet_params *p, const cbet_
 int cbet_mesh_check(const cbet_mesh *mesh /* host pointers */);
 int cbet_mesh_tables(const cbet_params *p, const cbet_mesh *mesh /* host pointers */, double *ne3d, double *kappa3d);
 int cbet_mesh_flow_table(const cbet_params *p, const cbet_mesh *mesh /* host pointers */, double *flow);
+
+/* ---- local plasma state of the gain kernels -------------------------------------------- */
+/*
+ * By default both gain kernels take the sound speed cs and the prefactor gain_const from cbet_gain_constants: ONE Te, Ti
+ * and Z for the whole plasma (cbet_gain_params.te_ev, ti_ev, z_ion).  A context can instead hold a STATE TABLE,
+ * double [2][nx][ny][nz] on the device, component-major in ne3d's node order: component 0 is cs (cm/s), component 1 is
+ * gain_const.  Every entry that updates the gain with that context -- cbet_gain_field, cbet_gain_field_slab,
+ * cbet_gain_field_packed -- then reads both values at the cell's (clamped) node, the node it takes ne3d and the flow from,
+ * and uses them wherever the scalars stand otherwise: in eta's denominator |k_j - k_i| cs + 1e-10 and in the cell's
+ * prefactor gain_const (ne/ncrit) (1/iaw) / sqrt(1 - ne/ncrit).
+ * What stays uniform: iaw, mi_over_me and the Mach ramp's parameters.  The closed-form ramp of the gain kernels and
+ * cbet_tabulate_flow keep multiplying the Mach number with the SCALAR cs of cbet_gain_constants, with a state table selected
+ * too: a caller who wants the local state throughout supplies the flow as well (cbet_tabulate_mesh_flow,
+ * cbet_context_set_flow).  The trace kernels only gather the gain and need nothing.
+ *
+ * Model, for a node with Te = te, Ti = ti (both eV) and mean charge z; every written operator ONE IEEE fp64 operation in the
+ * written order, no fused multiply-add (csrc/cbet_state_model.h, compiled by the kernel and by the host twin):
+ *     te_k = te * 11604.5052;   ti_k = ti * 11604.5052
+ *     c1   = E2 / ((A * te_k) * (1 + 3 * ti_k / (z * te_k)))
+ *     gc   = c1 * F                                                  (component 1)
+ *     cs   = 1e2 * sqrt(kEc * (z * te + 3.0 * ti) / mi_kg)           (component 0)
+ * with E2 = pow(estat, 2), A = 4 * (1.0e3 * kMe) * kC * omega * kb (left to right), F = 8.0 * M_PI * 1.0e7 / kC and
+ * mi_kg = mi_over_me * kMe, all four computed once on the host exactly as cbet_gain_constants computes them.
+ * Identity: with te = te_ev, ti = ti_ev and z = z_ion at every node the table holds cbet_gain_constants' cs and gain_const
+ * bit for bit, and a gain update with that table selected gives, bit for bit, the update with none.
+ *
+ * Producer from the hydro mesh: te is the mesh's (cbet_mesh.te, which must be in eV for the state to mean anything), ti and
+ * z come from cbet_mesh_ions, each array of the mesh's shape or NULL = cbet_gain_params.ti_ev / z_ion everywhere (ions
+ * NULL: both).  The three are interpolated with the mesh's own statement (phi, then theta, r last), then the model above.
+ * cbet_tabulate_mesh_state: DEVICE arrays -> the context's OWN state table, which it selects; behaves exactly like
+ * cbet_tabulate_mesh_flow: the FIRST call on a context allocates the table (2 nx ny nz doubles: 268 MB at 256^3) and is
+ * not graph-capturable, every later call only enqueues the kernel on `stream` (no allocation, no synchronisation).  It
+ * checks sizes, NULL pointers and the gain parameters only.
+ * cbet_context_set_state: selects a CALLER's device table of the layout above; the caller keeps it alive and unchanged while
+ * gain updates that read it are in flight.  NULL = back to the scalars (the context's own table stays allocated).
+ * Host-side state only: it applies to launches made after it.
+ * cbet_context_state: *out = the table in use, NULL if none (for tests).
+ * cbet_mesh_state_table: the host twin, plain loops in node order over HOST arrays into HOST out of 2 nx ny nz doubles.
+ * It validates the whole mesh first (cbet_mesh_check's rules), then ti (finite, >= 0) and zbar (finite, > 0), and returns
+ * CBET_EINVAL naming the first offence.
+ * cbet_cbet_solve takes cs and gain_const from its gain parameters and returns CBET_EINVAL for a context that has a state
+ * table selected, as it does for a selected flow; the loop above the C ABI (tracer.cbet_solve) runs with both.
+ */
+typedef struct cbet_mesh_ions {
+    const double *ti;    /* [nr][ntheta][nphi] eV, or NULL: cbet_gain_params.ti_ev everywhere */
+    const double *zbar;  /* same shape, or NULL: cbet_gain_params.z_ion everywhere */
+} cbet_mesh_ions;
+int cbet_tabulate_mesh_state(cbet_context *ctx, const cbet_params *p, const cbet_gain_params *g,
+                             const cbet_mesh *mesh /* device pointers */, const cbet_mesh_ions *ions /* device pointers; may be NULL */,
+                             void *stream);
+int cbet_context_set_state(cbet_context *ctx, const double *state);
+int cbet_context_state(cbet_context *ctx, void **out);
+int cbet_mesh_state_table(const cbet_params *p, const cbet_gain_params *g, const cbet_mesh *mesh /* host pointers */,
+                          const cbet_mesh_ions *ions /* host pointers; may be NULL */, double *out);
 /*
  * The sparse exchange of the slab-owned CBET loop (tracer._Exchanger).  A segment is a 64-byte run of 8 doubles aligned
  * to 8 along z; `segments` is a DEVICE array of nseg {row of the array (beam), index of the run inside one beam's
