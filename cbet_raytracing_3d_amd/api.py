@@ -363,6 +363,7 @@ EXPORTS = [
     "cbet_tabulate_mesh", "cbet_tabulate_mesh_flow", "cbet_mesh_check", "cbet_mesh_tables", "cbet_mesh_flow_table",
     "cbet_tabulate_mesh_state", "cbet_context_set_state", "cbet_context_state", "cbet_mesh_state_table",
     "cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit",
+    "cbet_context_set_saturation", "cbet_context_saturation", "cbet_pair_amplitude",
 ]
 
 _lib = None
@@ -469,6 +470,9 @@ def lib():
     deposit = [vp, vp, C.c_int, C.c_long, C.POINTER(Params), C.c_int, C.c_int, vp, vp, vp, vp]
     L.cbet_mesh_deposit_device.argtypes = deposit
     L.cbet_mesh_deposit.argtypes = deposit
+    L.cbet_context_set_saturation.argtypes = [vp, C.c_double]
+    L.cbet_context_saturation.argtypes = [vp, dp]
+    L.cbet_pair_amplitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -665,6 +669,17 @@ class Context:
         _check(lib().cbet_context_state(self._h, C.byref(a)))
         return a.value
 
+    def set_saturation(self, dn_max):
+        """cbet_context_set_saturation: the gain updates of this context limit the ion-acoustic amplitude every beam pair's
+        gain corresponds to at `dn_max` (> 0); 0 = no limit, the default.  A negative, NaN or infinite value raises."""
+        _check(lib().cbet_context_set_saturation(self._h, float(dn_max)))
+
+    def saturation(self):
+        """The limit in use (cbet_context_saturation), 0.0 if none."""
+        v = C.c_double()
+        _check(lib().cbet_context_saturation(self._h, C.byref(v)))
+        return v.value
+
     def close(self):
         if self._h:
             lib().cbet_context_destroy(self._h)
@@ -851,6 +866,13 @@ def cbet_slab_workspace_bytes_parts(params, own_beams, own_planes, staging_doubl
 def gain_field_slab(fields, ne3d, gain, scratch, change, hx_lo, hx_hi, params, gain_params, ctx, stream=None):
     _check(lib().cbet_gain_field_slab(_addr(fields), _addr(ne3d), _addr(gain), _addr(scratch), _addr(change), hx_lo, hx_hi,
                                       C.byref(params), C.byref(gain_params), ctx.handle, _addr(stream)))
+
+
+def pair_amplitude(fields, ne3d, amp, hx_lo, hx_hi, params, gain_params, ctx, stream=None):
+    """cbet_pair_amplitude: into `amp` (whole-grid [hsize] doubles), for the planes [hx_lo, hx_hi), the largest ion-acoustic
+    amplitude any beam pair's unclamped gain corresponds to, from the NORMALISED `fields` a gain update leaves."""
+    _check(lib().cbet_pair_amplitude(_addr(fields), _addr(ne3d), _addr(amp), hx_lo, hx_hi, C.byref(params), C.byref(gain_params),
+                                     ctx.handle if ctx is not None else None, _addr(stream)))
 
 
 def cbet_workspace_bytes(params):

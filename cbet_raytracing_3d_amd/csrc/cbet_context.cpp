@@ -2,6 +2,7 @@
 // a launch makes against it and the default-context map.
 // Citations are into /root/reference/.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -277,6 +278,23 @@ int cbet_context_state(cbet_context *ctx, void **out)
 {
     if (!ctx || !out) return fail(CBET_EINVAL, "NULL context/out");
     *out = const_cast<double *>(ctx->state);
+    return CBET_OK;
+}
+
+int cbet_context_set_saturation(cbet_context *ctx, double dn_max)
+{
+    if (std::isnan(dn_max)) return fail(CBET_EINVAL, "cbet_context_set_saturation: dn_max is NaN (a finite limit > 0, or 0 = none)");
+    if (std::isinf(dn_max)) return fail(CBET_EINVAL, "cbet_context_set_saturation: dn_max is infinite (a finite limit > 0, or 0 = none)");
+    if (dn_max < 0.0) return fail(CBET_EINVAL, "cbet_context_set_saturation: dn_max = %g is negative (a finite limit > 0, or 0 = none)", dn_max);
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    ctx->dn_max = dn_max;
+    return CBET_OK;
+}
+
+int cbet_context_saturation(cbet_context *ctx, double *out)
+{
+    if (!ctx || !out) return fail(CBET_EINVAL, "NULL context/out");
+    *out = ctx->dn_max;
     return CBET_OK;
 }
 

@@ -127,6 +127,7 @@ struct GainArgs {
     long store0, bstride;                   // whole-grid arrays: 0, hsize; slab-packed arrays: hx_lo * (ny+2)(nz+2), slab entries
     const double *flow;                     // [3][nx*ny*nz] node flow table (ux, uy, uz; cbet_tabulate_flow), or NULL: the closed-form ramp about the origin
     const double *state;                    // [2][nx*ny*nz] node state table (cs, gain_const; cbet_tabulate_mesh_state), or NULL: the scalars cs / gain_const above
+    double sat;                             // limit dn_max of the ion-acoustic amplitude a pair's gain corresponds to (cbet_context_set_saturation), 0 = none
 };
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);
@@ -145,6 +146,8 @@ hipError_t launch_trace_exit(const TraceArgs &a, bool force_idx64, hipStream_t s
 hipError_t launch_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, hipStream_t stream);
 hipError_t launch_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, hipStream_t stream);
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream);
+// k_pair_amplitude: the unclamped amplitude map of normalised fields over the planes [a.hx_lo, a.hx_hi) into amp[hsize]; a.sat is not read
+hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream);
 hipError_t launch_pack_segments(const double *src, long beam_stride, int hy, int hz, const int *seg, long nseg, double *out,
                                 hipStream_t stream);
 hipError_t launch_unpack_segments(double *dst, long beam_stride, int hy, int hz, const int *seg, long nseg, const double *in,

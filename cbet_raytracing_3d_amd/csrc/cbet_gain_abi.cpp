@@ -1,6 +1,6 @@
 // cbet_gain_abi.cpp -- the CBET stage of the C ABI (include/cbet_mi355x.h; SURVEY 8(f) f1, parity unpinned -- see the
 // header): the gain update, the trace with the CBET hooks, the sparse exchange's pack / unpack and the native one-device
-// fixed-point loop.
+// fixed-point loop, the amplitude map of the saturation clamp.
 #include <cmath>
 
 #include "cbet_host_internal.h"
@@ -9,11 +9,12 @@ using namespace cbet;
 
 int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo,
                           int hx_hi, bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx,
-                          void *stream, bool consume)
+                          void *stream, bool consume, double *amplitude)
 {
+    // amplitude: not a gain update but cbet_pair_amplitude's launch on the same argument block (gain is NULL then)
     if (int rc = entry_checks(ctx, p)) return rc;
     if (int rc = validate_gain(p, g)) return rc;
-    if (!fields || !gain) return fail(CBET_EINVAL, "NULL device pointer");
+    if (!fields || !(amplitude ? amplitude : gain)) return fail(CBET_EINVAL, "NULL device pointer");
     if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo) return fail(CBET_EINVAL, "slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
@@ -32,11 +33,13 @@ int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, doub
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
     a.flow = ctx->flow;
     a.state = ctx->state;
+    a.sat = amplitude ? 0.0 : ctx->dn_max;   // the map is the unclamped amplitude
     a.store0 = packed ? (long)hx_lo * plane : 0;
     a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
     if (hx_hi == hx_lo) return CBET_OK;   // an empty slab (more ranks than planes)
     CBET_ENTER_DEVICE(ctx);
-    CBET_HIP(launch_gain_field(a, (hipStream_t)stream));
+    if (amplitude) CBET_HIP(launch_pair_amplitude(a, amplitude, (hipStream_t)stream));
+    else CBET_HIP(launch_gain_field(a, (hipStream_t)stream));
     return CBET_OK;
 }
 
@@ -76,6 +79,19 @@ int cbet_gain_field_packed(double *fields, const double *ne3d, double *gain, dou
                            cbet_context *ctx, void *stream)
 {
     return gain_field_impl(fields, ne3d, gain, scratch, change, hx_lo, hx_hi, true, p, g, ctx, stream);
+}
+
+int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, int hx_lo, int hx_hi, const cbet_params *p,
+                        const cbet_gain_params *g, cbet_context *ctx, void *stream)
+{
+    // the arguments first, the context last: what is wrong with a call does not depend on there being a device
+    if (int rc = validate(p)) return rc;
+    if (int rc = validate_gain(p, g)) return rc;
+    if (!fields) return fail(CBET_EINVAL, "cbet_pair_amplitude: fields is NULL");
+    if (!amp) return fail(CBET_EINVAL, "cbet_pair_amplitude: amp is NULL");
+    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
+        return fail(CBET_EINVAL, "cbet_pair_amplitude: slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
+    return gain_field_impl(const_cast<double *>(fields), ne3d, nullptr, nullptr, nullptr, hx_lo, hx_hi, false, p, g, ctx, stream, false, amp);
 }
 
 // ---- sparse exchange of the slab-owned CBET loop (cbet_grid_kernels.hip) -----------------------------------------

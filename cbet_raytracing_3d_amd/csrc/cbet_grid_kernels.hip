@@ -1,6 +1,8 @@
 // cbet_grid_kernels.hip -- the cell-parallel kernels beside the ray integrator (cbet_kernels.hip):
 //   * k_gain_field (ordered), k_gain_field_sym (pairs once, LDS-staged) : per-beam fields -> CBET gain coefficient (no
 //     reference counterpart, parity unpinned -- model and layout in DESIGN.md section 9)
+//   * k_pair_amplitude               : normalised fields -> the largest ion-acoustic amplitude a cell's pair gains correspond to
+//     (the map the saturation limit of both gain kernels is chosen by)
 //   * k_edep_average                 : the 27-point node average of main.cu:334-349
 // Built with -ffp-contract=off like the rest of the library: every statement of the ordered kernel and of the
 // normalisation is one IEEE operation in the order written, which is the order the CPU checker of the CBET stage
@@ -64,6 +66,13 @@ __device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
 // The prefactor of a cell's pair gains, gain_const (ne / ncrit) / (iaw sqrt(eps)); zero at and above critical density.
 __device__ __forceinline__ double cell_pref(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? c.gc * c.frac * (1.0 / a.iaw) / c.rt : 0.0; }
 
+// Saturation of the ion-acoustic wave.  Scattering off a grating of relative amplitude dn/n exchanges
+// intensity at the rate kap (dn/n) sqrt(Ii Ij), kap = (k0 / 2) (ne / ncrit) / sqrt(eps); the amplitude this model's pair gain
+// corresponds to is therefore |G_ij| sqrt(Ii Ij) / kap.  cell_sat_limit: the value w = |G_ij| sqrt(Ii Ij) may reach under
+// the limit dn_max; zero at and above critical density, where the gain is zero too.
+__device__ __forceinline__ double cell_kap(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? ((0.5 * a.k0) * c.frac) / c.rt : 0.0; }
+__device__ __forceinline__ double cell_sat_limit(const GainArgs &a, const CellState &c) { return a.sat * cell_kap(a, c); }
+
 // The epilogue of both gain kernels: the wave's sums of |new - old| and |new| into GainArgs.change, two atomics per wave.
 __device__ __forceinline__ void report_change(const GainArgs &a, int lane, double sum_change, double sum_abs)
 {
@@ -114,7 +123,9 @@ __device__ __forceinline__ void normalise_entry(const GainArgs &a, const CellSta
 //            beam is not present (E <= 0); with GainArgs.frozen only the energy entry (normalise_entry).
 //   phase 2: K_i = sum_{j != i} G_ij I_j, beams in increasing order; gain <- gain + relax (K - gain),
 //            stored only where it changes.
-template <bool FLOW, bool STATE>
+// SAT (GainArgs.sat > 0): every pair gain is scaled by min(1, lim / w), w = |G_ij| sqrt(Ii Ij) -- one factor for (i, j) and
+// (j, i), so the cell's exchange still cancels; a pair below the limit keeps its bits ((pref * P) * Ij either way).
+template <bool FLOW, bool STATE, bool SAT>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
     const int HY = a.ny + 2, HZ = a.nz + 2;
@@ -149,6 +160,7 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
             if (E != 0.0) normalise_entry(a, c, kmag, ds_node, E, fI, fx, fy, fz, o);
         }
         const double pref = cell_pref(a, c);
+        const double lim = SAT ? cell_sat_limit(a, c) : 0.0;
         for (int bi = 0; bi < a.nbeams; ++bi) {
             const long oi = (long)bi * hsize;
             double raw = 0.0;
@@ -168,7 +180,14 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
                         const double eta = (0.0 - (qx * c.ux + qy * c.uy + qz * c.uz)) / (kiaw * c.cs + 1e-10);
                         const double e2 = eta * eta;
                         const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
-                        acc += pref * P * Ij;
+                        if (SAT) {
+                            double g = pref * P;
+                            const double w = fabs(g) * sqrt(Ii * Ij);
+                            if (w > lim) g = g * (lim / w);
+                            acc += g * Ij;
+                        } else {
+                            acc += pref * P * Ij;
+                        }
                     }
                 }
                 raw = acc;
@@ -184,6 +203,69 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
         }
     }
     report_change(a, lane, sum_change, sum_abs);
+}
+
+// The amplitude map: for NORMALISED fields (I, kx, ky, kz) the largest, over the cell's beam pairs i < j,
+// of the ion-acoustic amplitude the pair's unclamped gain corresponds to, A_ij = |G_ij| sqrt(Ii Ij) / kap -- the ordered
+// kernel's statements, its bricks and its presence mask; one store per valid cell, 0 where no pair exchanges anything or the
+// plasma is not sub-critical.  w / kap grows with w, so the largest w is divided once.  Reads a.fields only; a.sat is not read.
+template <bool FLOW, bool STATE>
+__global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double *__restrict__ amp)
+{
+    const int HY = a.ny + 2, HZ = a.nz + 2;
+    const long hsize = a.bstride;
+    const long total = hsize * a.nbeams;
+    const int bx0 = a.hx_lo >> 1, bx = ((a.hx_hi + 1) >> 1) - bx0;
+    const int by = (HY + 3) / 4, bz = (HZ + 7) / 8;
+    const long bricks = (long)bx * by * bz;
+    const int lane = threadIdx.x & (kWave - 1);
+    const long wave0 = (long)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
+    const long nwaves = (long)gridDim.x * (blockDim.x / kWave);
+    const double iaw2 = a.iaw * a.iaw;
+    for (long brick = wave0; brick < bricks; brick += nwaves) {
+        const int ibz = (int)(brick % bz);
+        const long t = brick / bz;
+        const int iby = (int)(t % by), ibx = bx0 + (int)(t / by);
+        const int hi = 2 * ibx + (lane >> 5), hj = 4 * iby + ((lane >> 3) & 3), hk = 8 * ibz + (lane & 7);
+        const bool valid = hi >= a.hx_lo && hi < a.hx_hi && hj < HY && hk < HZ;
+        const long h = valid ? ((long)hi * HY + hj) * HZ + hk : 0;
+        const double *fI = a.fields + h, *fx = fI + total, *fy = fx + total, *fz = fy + total;
+        const CellState c = cell_state<FLOW, STATE>(a, h);
+        unsigned long long mask = 0ull;             // beams present in some cell of this brick
+        for (int b = 0; b < a.nbeams; ++b) {
+            const double I = valid ? fI[(long)b * hsize] : 0.0;
+            if (__builtin_amdgcn_ballot_w64(I > 0.0) != 0ull) mask |= 1ull << b;
+        }
+        const double pref = cell_pref(a, c);
+        const double kap = cell_kap(a, c);
+        double top = 0.0;
+        unsigned long long mi = mask;
+        while (mi != 0ull) {
+            const int bi = __ffsll((long long)mi) - 1;
+            mi &= mi - 1;
+            const long oi = (long)bi * hsize;
+            const double Ii = fI[oi];
+            const double kxi = fx[oi], kyi = fy[oi], kzi = fz[oi];
+            unsigned long long m = mi;              // the beams after bi
+            while (m != 0ull) {
+                const int bj = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const long oj = (long)bj * hsize;
+                const double Ij = fI[oj];
+                const double qx = fx[oj] - kxi, qy = fy[oj] - kyi, qz = fz[oj] - kzi;
+                const double kiaw = sqrt(qx * qx + qy * qy + qz * qz);
+                if (valid && Ii > 0.0 && Ij > 0.0 && kiaw > 0.0) {
+                    const double eta = (0.0 - (qx * c.ux + qy * c.uy + qz * c.uz)) / (kiaw * c.cs + 1e-10);
+                    const double e2 = eta * eta;
+                    const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
+                    const double g = pref * P;
+                    const double w = fabs(g) * sqrt(Ii * Ij);
+                    if (w > top) top = w;
+                }
+            }
+        }
+        if (valid) amp[h] = kap > 0.0 ? top / kap : 0.0;
+    }
 }
 
 struct BeamAtCell {
@@ -255,6 +337,24 @@ __device__ __forceinline__ double pair_gain_fast(const BeamAtCell &bi, const Bea
     return __builtin_fma(__builtin_fma(-den, qt, num), y, qt);
 }
 
+// The clamp of the pair-once kernel on the value pair_gain_fast returned: with w^2 = (gn Ii) (gn Ij)
+// beyond lim^2 the gain is scaled by lim / w = lim rsqrt(w^2) -- the estimate and two Goldschmidt steps, a few ulp like the
+// pair function itself; squares are compared, and gn comes back untouched where the limit is not reached.
+__device__ __forceinline__ double saturate_fast(double gn, double Ii, double Ij, double lim)
+{
+    const double w2 = (gn * Ii) * (gn * Ij);
+    if (w2 > lim * lim) {
+        const double r0 = __builtin_amdgcn_rsq(w2);
+        double gq = w2 * r0, hq = 0.5 * r0;      // gq -> w, hq -> 1 / (2 w)
+        double e = __builtin_fma(-hq, gq, 0.5);
+        gq = __builtin_fma(gq, e, gq); hq = __builtin_fma(hq, e, hq);
+        e = __builtin_fma(-hq, gq, 0.5);
+        hq = __builtin_fma(hq, e, hq);
+        gn = gn * ((lim + lim) * hq);
+    }
+    return gn;
+}
+
 // LDS traffic between lanes of ONE wavefront: the hardware keeps a wavefront's LDS instructions in order, the compiler
 // has to be told that they may not be reordered across this point
 __device__ __forceinline__ void lds_order()
@@ -269,10 +369,14 @@ __device__ __forceinline__ void lds_order()
 // sixteen per-lane beam offsets of the mask loads are formed per run instead of once per kernel (hs0, the trick of hs1 and
 // hs3), and the first call's arm (not FROZEN: once per solve) keeps three rounds of phase 1 and four of phase 3 in flight
 // instead of four and eight.  None of this reorders a sum: no scratch in any STATE instantiation.
-template <bool FROZEN, bool FLOW, bool STATE>
+// SAT (GainArgs.sat > 0): the cell's limit is one more per-lane value of the state block and of the pair
+// loop, and every pair's gain goes through saturate_fast once, before both of its addends.  The SAT arm takes the same
+// registers back as the STATE arm does; the instantiations without SAT keep their statements.
+template <bool FROZEN, bool FLOW, bool STATE, bool SAT>
 __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 {
-    constexpr int PCH = (STATE && !FROZEN) ? 3 : LCH, QCH = (STATE && !FROZEN) ? 4 : LCH3;
+    constexpr bool LEAN = STATE || SAT;
+    constexpr int PCH = (LEAN && !FROZEN) ? 3 : LCH, QCH = (LEAN && !FROZEN) ? 4 : LCH3;
     static_assert(5 * LCAP * LC >= 64 * (LC + 1), "the slot arrays double as the staging area of the presence masks");
     __shared__ double lds[5 * LCAP * LC];
     double *const sI = lds, *const sX = sI + LCAP * LC, *const sY = sX + LCAP * LC, *const sZ = sY + LCAP * LC,
@@ -285,7 +389,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
     const double iaw2 = a.iaw * a.iaw;
     const int rounds = (a.nbeams + LG - 1) / LG;
     double sum_change = 0.0, sum_abs = 0.0;
-    double st_rt = 0.0, st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_pref = 0.0, st_cs = 0.0;
+    double st_rt = 0.0, st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_pref = 0.0, st_cs = 0.0, st_lim = 0.0;
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {
         const int hi = a.hx_lo + (int)(row / HY), hj = (int)(row % HY);
         // runs start on 128-byte lines of the arrays, not at z = 16 k of the row: the row's first entry sits `sft` doubles into
@@ -307,7 +411,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             {
                 double E[LROUNDS];
                 long hs0 = hsize;
-                if (STATE) asm volatile("" : "+s"(hs0));   // opaque: the sixteen offsets below are formed here, not kept across the kernel
+                if (LEAN) asm volatile("" : "+s"(hs0));   // opaque: the sixteen offsets below are formed here, not kept across the kernel
 #pragma unroll
                 for (int r = 0; r < LROUNDS; ++r) {
                     const int b = LG * r + g;
@@ -332,12 +436,14 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                 st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
                 st_pref = cell_pref(a, c64);
                 if (STATE) st_cs = c64.cs;
+                if (SAT) st_lim = cell_sat_limit(a, c64);
             }
             const int from = LC * (ibz & 3) + c;
             const double rt = __shfl(st_rt, from, kWave), ux = __shfl(st_ux, from, kWave), uy = __shfl(st_uy, from, kWave),
                          uz = __shfl(st_uz, from, kWave);
             const double pref = valid ? __shfl(st_pref, from, kWave) : 0.0;
             const double cs = STATE ? __shfl(st_cs, from, kWave) : a.cs;   // the cell's own, or the uniform one (scalar registers)
+            const double lim = SAT ? __shfl(st_lim, from, kWave) : 0.0;
             const bool subcritical = rt > 0.0;   // eps > 0
             const double kmag = a.k0 * rt;
             const double ds_node = (kC * rt) * a.dt;
@@ -426,8 +532,12 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             S.I = sI[self]; S.kx = sX[self]; S.ky = sY[self]; S.kz = sZ[self];
                             P1.I = sI[p1]; P1.kx = sX[p1]; P1.ky = sY[p1]; P1.kz = sZ[p1];
                             P2.I = sI[p2]; P2.kx = sX[p2]; P2.ky = sY[p2]; P2.kz = sZ[p2];
-                            const double g1 = pair_gain_fast(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2);
-                            const double g2 = g < 2 ? pair_gain_fast(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2) : 0.0;
+                            double g1 = pair_gain_fast(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2);
+                            double g2 = g < 2 ? pair_gain_fast(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2) : 0.0;
+                            if (SAT) {
+                                g1 = saturate_fast(g1, S.I, P1.I, lim);
+                                g2 = saturate_fast(g2, S.I, P2.I, lim);
+                            }
                             sR[self] += g1 * P1.I + g2 * P2.I;
                             lds_order();             // the next statement's entries are other lanes' `self`
                             sR[p1] -= g1 * S.I;
@@ -451,7 +561,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             double KB = 0.0;
 #pragma unroll
                             for (int s_ = 0; s_ < LG; ++s_) {
-                                const double gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
+                                double gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
+                                if (SAT) gn = saturate_fast(gn, A[s_].I, B.I, lim);
                                 KA[s_] += gn * B.I;
                                 KB -= gn * A[s_].I;
                             }
@@ -604,38 +715,51 @@ hipError_t launch_edep_average(const double *edep, double *out, int nx, int ny, 
     return hipGetLastError();
 }
 
+// one dispatch of the run-time switches onto the template arguments: frozen, flow, state, sat
+template <bool... Bs>
+struct Sym {
+    static void launch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream) { hipLaunchKernelGGL((k_gain_field_sym<Bs...>), grid, block, 0, stream, a); }
+};
+template <bool... Bs>
+struct Ordered {
+    static void launch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream) { hipLaunchKernelGGL((k_gain_field<Bs...>), grid, block, 0, stream, a); }
+};
+template <template <bool...> class K, bool... Bs>
+void dispatch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream) { K<Bs...>::launch(a, grid, block, stream); }
+template <template <bool...> class K, bool... Bs, class... Rest>
+void dispatch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, bool first, Rest... rest)
+{
+    if (first) dispatch<K, Bs..., true>(a, grid, block, stream, rest...);
+    else dispatch<K, Bs..., false>(a, grid, block, stream, rest...);
+}
+
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
 {
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
-        const dim3 grid((unsigned)rows), block(64);
-        if (a.state) {
-            if (a.flow) {
-                if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, true, true>), grid, block, 0, stream, a);
-                else hipLaunchKernelGGL((k_gain_field_sym<false, true, true>), grid, block, 0, stream, a);
-            } else {
-                if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, false, true>), grid, block, 0, stream, a);
-                else hipLaunchKernelGGL((k_gain_field_sym<false, false, true>), grid, block, 0, stream, a);
-            }
-        } else if (a.flow) {
-            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, true, false>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((k_gain_field_sym<false, true, false>), grid, block, 0, stream, a);
-        } else {
-            if (a.frozen) hipLaunchKernelGGL((k_gain_field_sym<true, false, false>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((k_gain_field_sym<false, false, false>), grid, block, 0, stream, a);
-        }
+        dispatch<Sym>(a, dim3((unsigned)rows), dim3(64), stream, a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0);
         return hipGetLastError();
     }
     const long bricks = (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8);  // 2 x 4 x 8 cells of the haloed grid each
     long blocks = (bricks + 3) / 4;                                                    // four wavefronts per workgroup
     if (blocks > 256 * 64) blocks = 256 * 64;
+    dispatch<Ordered>(a, dim3((unsigned)blocks), dim3(256), stream, a.flow != nullptr, a.state != nullptr, a.sat > 0.0);
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream)
+{
+    if (a.hx_hi <= a.hx_lo) return hipSuccess;
+    const long bricks = (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8);
+    long blocks = (bricks + 3) / 4;
+    if (blocks > 256 * 64) blocks = 256 * 64;
     const dim3 grid((unsigned)blocks), block(256);
     if (a.state) {
-        if (a.flow) hipLaunchKernelGGL((k_gain_field<true, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k_gain_field<false, true>), grid, block, 0, stream, a);
-    } else if (a.flow) hipLaunchKernelGGL((k_gain_field<true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((k_gain_field<false, false>), grid, block, 0, stream, a);
+        if (a.flow) hipLaunchKernelGGL((k_pair_amplitude<true, true>), grid, block, 0, stream, a, amp);
+        else hipLaunchKernelGGL((k_pair_amplitude<false, true>), grid, block, 0, stream, a, amp);
+    } else if (a.flow) hipLaunchKernelGGL((k_pair_amplitude<true, false>), grid, block, 0, stream, a, amp);
+    else hipLaunchKernelGGL((k_pair_amplitude<false, false>), grid, block, 0, stream, a, amp);
     return hipGetLastError();
 }
 

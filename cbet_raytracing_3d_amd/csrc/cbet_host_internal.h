@@ -33,6 +33,8 @@ struct cbet_context {
     // state table of the gain kernels (cbet_tabulate_mesh_state / cbet_context_set_state): NULL = the scalars cs, gain_const
     double *state_own = nullptr;        // the context's own [2][nx*ny*nz] table, allocated by the first cbet_tabulate_mesh_state
     const double *state = nullptr;      // the table in use: state_own, a caller's, or NULL
+    // limit of the ion-acoustic amplitude in the gain kernels (cbet_context_set_saturation): 0 = none
+    double dn_max = 0.0;
 };
 
 namespace cbet {
@@ -156,7 +158,7 @@ int trace_impl(int b, unsigned nindices, const double *ne3d, const double *kappa
                double zconst, const cbet_params *p, cbet_context *ctx, void *stream, const CbetHooks &hooks);
 int gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo, int hx_hi,
                     bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx, void *stream,
-                    bool consume = false);
+                    bool consume = false, double *amplitude = nullptr);
 
 #pragma GCC visibility pop
 }  // namespace cbet

@@ -72,6 +72,7 @@ class RayTracer:
         self._flow_gp = None            # the gain parameters a "target" flow is tabulated from
         self.gain_state = None          # set_gain_state(): None, "mesh" or the caller's [2, nx, ny, nz] table
         self._state_gp = None           # the gain parameters a "mesh" state takes ti_ev, z_ion and mi_over_me from
+        self.saturation = 0.0           # set_saturation(): the limit of the ion-acoustic amplitude, 0.0 = none
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     # ---- the one spelling of what every launch repeats -------------------------------------------------------------
@@ -104,6 +105,7 @@ class RayTracer:
             api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
         self._tabulate_flow(ctx, params)
         self._tabulate_state(ctx, params)
+        ctx.set_saturation(self.saturation)         # a context prepared for this tracer carries its limit, as it carries its tables
 
     def _tabulate_other(self, ctx, params):
         """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False
@@ -259,6 +261,37 @@ class RayTracer:
         if self._state_is_mesh():
             api.tabulate_mesh_state(self.ctx if ctx is None else ctx, self.params if params is None else params,
                                     self._state_gp, self.mesh, self._stream())
+
+    # ---- saturation of the ion-acoustic wave (include/cbet_mi355x.h cbet_context_set_saturation) --
+    def set_saturation(self, dn_max=0.0):
+        """The limit of the ion-acoustic amplitude in the gain kernels.
+        0.0 (the default): none -- every pair gain is the linear one.
+        dn_max > 0: the gain of every beam pair is scaled down where the amplitude it corresponds to, |G_ij| sqrt(Ii Ij) / kap
+        with kap = (k0 / 2) (ne / ncrit) / sqrt(1 - ne / ncrit), exceeds dn_max; the same factor for both beams of the pair, so
+        a cell's exchange still cancels.  pair_amplitude() maps that amplitude, to choose a value by.
+        The limit is the context's: gain_field, both loops of cbet_solve and api.cbet_solve(ctx=tracer.ctx) honour it from
+        the next gain update on, and so does every context prepared for this tracer later (the pipeline's).  A negative, NaN
+        or infinite value raises and changes nothing."""
+        self.ctx.set_saturation(dn_max)
+        self.saturation = float(dn_max)
+
+    def pair_amplitude(self, fields, gain_params, x_lo=0, x_hi=None, ne3d=None, out=None):
+        """The largest ion-acoustic amplitude any beam pair's UNCLAMPED gain corresponds to, per cell of the planes
+        [x_lo, x_hi): a grid-shaped tensor (`out`, or a zeroed new one; cells of other planes are left as they are).
+        `fields` are normalised fields [4, nbeams, ...] as gain_field leaves them; they are not changed.  The flow and the
+        gain state are read as gain_field reads them; the limit of set_saturation is not."""
+        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+        if self._state_is_mesh() and self.ctx.state() is None:
+            raise ValueError("pair_amplitude: set_gain_state(\"mesh\") needs tabulate() first")
+        if isinstance(self.flow, str) and self.ctx.flow() is None:
+            raise ValueError("pair_amplitude: set_flow(\"%s\") needs tabulate() first" % self.flow)
+        if out is None:
+            out = torch.zeros(self.grid_shape, dtype=torch.float64, device=self.device)
+        else:
+            _require(out, self.grid_shape, "out")
+        api.pair_amplitude(fields, ne3d, out, x_lo, self.grid_shape[0] if x_hi is None else x_hi, self.params, gain_params,
+                           self.ctx, self._stream())
+        return out
 
     def _no_target(self, what):
         if self.flow is not None:

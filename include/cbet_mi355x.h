@@ -706,6 +706,48 @@ int cbet_cbet_solve(double *te_data_g, double *r_data_g, double *ne_data_g, doub
  */
 const double *cbet_cbet_workspace_gain(const cbet_params *p, const void *workspace);
 
+/* ---- saturation of the ion-acoustic wave --------------------------------------------------- */
+/*
+ * The pair gain G_ij = pref P(eta_ij) of the gain kernels is linear: nothing in it limits the ion-acoustic grating a beam
+ * pair drives.  (cbet_gain_params.max_exponent is a numerical clamp of the TRACE kernels on |K ds| per ray step; it does not
+ * act on the pair gains and is not symmetric between the two beams of a pair.)  A context can hold a limit dn_max > 0 on
+ * the grating's relative amplitude.  Scattering off a grating of amplitude dn/n exchanges intensity at the rate
+ * kap (dn/n) sqrt(Ii Ij), kap = (k0 / 2) frac / sqrt(eps) with k0 = omega / c, frac = ne / ncrit, eps = 1 - frac; so
+ *     A_ij = |G_ij| sqrt(Ii Ij) / kap                       (dimensionless: G I and kap are both 1/cm)
+ * is the amplitude this model's gain corresponds to -- no more than that: the model's parity is unpinned (DESIGN.md section
+ * 9).  With a limit every pair gain becomes G_ij min(1, dn_max / A_ij).  The factor is the same for (i, j) and (j, i): G
+ * stays antisymmetric and a cell's exchange sum_i I_i K_i still cancels.
+ *
+ * The ordered kernel, every written operator ONE IEEE fp64 operation in the written order, no fused multiply-add:
+ *     per cell:  kap = ((0.5 * k0) * frac) / rt             (rt = sqrt(eps), eps > 0;  kap = 0 otherwise)
+ *                lim = dn_max * kap
+ *     per pair:  g = pref * P
+ *                w = fabs(g) * sqrt(Ii * Ij)
+ *                if (w > lim) g = g * (lim / w)
+ *                acc += g * Ij
+ * A pair that does not reach the limit keeps its bits (the update without a limit adds (pref * P) * Ij).  With a state table
+ * pref holds the node's gain_const, as without a limit.  The pair-once kernel applies ONE factor per unordered pair to its
+ * pair function's value before both addends, comparing squares and scaling by lim rsqrt(w^2) from the hardware estimate
+ * (a few ulp, like its pair function); where the limit is not reached the value is untouched.
+ *
+ * cbet_context_set_saturation: dn_max > 0 sets the limit, 0 = none (a new context's default); negative, NaN or infinite:
+ * CBET_EINVAL naming the offence.  Host-side state only, like cbet_context_set_state: it applies to launches made after it.
+ * Every entry that updates the gain with that context honours it -- cbet_gain_field, cbet_gain_field_slab,
+ * cbet_gain_field_packed, and cbet_cbet_solve with a caller's context (the limit is uniform: the solve does not refuse it;
+ * with ctx == NULL it runs without one).
+ * cbet_context_saturation: *out = the limit in use, 0 if none.
+ * cbet_pair_amplitude: the map of the UNCLAMPED amplitude.  `fields` are NORMALISED whole-grid device fields
+ * [4][nbeams][hsize] (I, kx, ky, kz), as a gain update without `consume` leaves them; `amp` is [hsize] device doubles,
+ * whole-grid storage.  For every cell of the planes [hx_lo, hx_hi) it writes max over i < j of A_ij by the statements above
+ * (the largest w, divided by kap), 0 where fewer than two beams are present, where no present pair has k_i != k_j, or where
+ * kap = 0; other planes are not written.  It reads the context's flow and state tables like the gain kernels (ne3d NULL:
+ * the context's), ignores the context's dn_max and changes neither `fields` nor any gain.  Stream-ordered.
+ */
+int cbet_context_set_saturation(cbet_context *ctx, double dn_max);
+int cbet_context_saturation(cbet_context *ctx, double *out);
+int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, int hx_lo, int hx_hi, const cbet_params *p,
+                        const cbet_gain_params *g, cbet_context *ctx, void *stream);
+
 /* ---- exit pass --------------------------------------------------------------- */
 /*
  * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
