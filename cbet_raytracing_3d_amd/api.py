@@ -364,6 +364,7 @@ EXPORTS = [
     "cbet_tabulate_mesh_state", "cbet_context_set_state", "cbet_context_state", "cbet_mesh_state_table",
     "cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit",
     "cbet_context_set_saturation", "cbet_context_saturation", "cbet_pair_amplitude",
+    "cbet_exchange_matrix_work_bytes", "cbet_exchange_matrix", "cbet_exchange_matrix_host",
 ]
 
 _lib = None
@@ -473,6 +474,11 @@ def lib():
     L.cbet_context_set_saturation.argtypes = [vp, C.c_double]
     L.cbet_context_saturation.argtypes = [vp, dp]
     L.cbet_pair_amplitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
+    L.cbet_exchange_matrix_work_bytes.argtypes = [C.POINTER(Params)]
+    L.cbet_exchange_matrix_work_bytes.restype = C.c_size_t
+    L.cbet_exchange_matrix.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
+    L.cbet_exchange_matrix_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp,
+                                            C.c_double]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
@@ -873,6 +879,37 @@ def pair_amplitude(fields, ne3d, amp, hx_lo, hx_hi, params, gain_params, ctx, st
     amplitude any beam pair's unclamped gain corresponds to, from the NORMALISED `fields` a gain update leaves."""
     _check(lib().cbet_pair_amplitude(_addr(fields), _addr(ne3d), _addr(amp), hx_lo, hx_hi, C.byref(params), C.byref(gain_params),
                                      ctx.handle if ctx is not None else None, _addr(stream)))
+
+
+def exchange_matrix_work_bytes(params):
+    """cbet_exchange_matrix_work_bytes: device bytes of the `work` array of exchange_matrix, for any slab of the grid."""
+    return int(lib().cbet_exchange_matrix_work_bytes(C.byref(params)))
+
+
+def exchange_matrix(fields, ne3d, out, gross, work, hx_lo, hx_hi, params, gain_params, ctx, stream=None):
+    """cbet_exchange_matrix: the pairwise exchange of the NORMALISED device `fields` over the planes [hx_lo, hx_hi), ADDED into
+    the upper triangle of `out` (device [nbeams, nbeams]: out[i, j] = the energy beam i gains from beam j per field pass; lower
+    triangle negated, diagonal zero) and of `gross` (the sum of magnitudes, symmetric; may be None).  The context's flow and
+    state tables and its saturation limit are honoured."""
+    _check(lib().cbet_exchange_matrix(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), _addr(work), hx_lo, hx_hi,
+                                      C.byref(params), C.byref(gain_params), ctx.handle if ctx is not None else None, _addr(stream)))
+
+
+def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=None, dn_max=0.0, hx_lo=0, hx_hi=None, out=None,
+                         gross=None):
+    """cbet_exchange_matrix_host, the host twin: numpy (T, Gross), each (nbeams, nbeams), of normalised HOST fields
+    [4, nbeams, nx + 2, ny + 2, nz + 2] over the planes [hx_lo, hx_hi).  ne3d (nx, ny, nz); flow (3, nx, ny, nz) or None = the
+    closed-form ramp; state (2, nx, ny, nz) or None = the scalars; dn_max 0 = no limit.  out / gross: arrays to ADD into
+    (default: new zeroed ones)."""
+    nb = params.nbeams
+    host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
+    fields, ne3d, flow, state = host(fields), host(ne3d), host(flow), host(state)
+    out = np.zeros((nb, nb)) if out is None else out
+    gross = np.zeros((nb, nb)) if gross is None else gross
+    _check(lib().cbet_exchange_matrix_host(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
+                                           params.nx + 2 if hx_hi is None else hx_hi, C.byref(params), C.byref(gain_params),
+                                           _addr(flow), _addr(state), dn_max))
+    return out, gross
 
 
 def cbet_workspace_bytes(params):

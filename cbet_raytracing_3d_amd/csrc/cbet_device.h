@@ -148,6 +148,11 @@ hipError_t launch_farfield(const cbet_ray_exit *exits, long n, int ntheta, int n
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream);
 // k_pair_amplitude: the unclamped amplitude map of normalised fields over the planes [a.hx_lo, a.hx_hi) into amp[hsize]; a.sat is not read
 hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream);
+// k_exchange_matrix + k_exchange_reduce: the pairwise exchange of normalised fields over the planes
+// [a.hx_lo, a.hx_hi), added into out / gross ([nbeams][nbeams], gross may be NULL); a.sat is honoured.  work holds
+// exchange_groups(rows) x 2 x nbeams (nbeams - 1) / 2 doubles, rows = planes x (ny + 2).
+inline long exchange_groups(long rows) { return rows < CBET_EXCHANGE_MAX_GROUPS ? rows : CBET_EXCHANGE_MAX_GROUPS; }
+hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, double *gross, hipStream_t stream);
 hipError_t launch_pack_segments(const double *src, long beam_stride, int hy, int hz, const int *seg, long nseg, double *out,
                                 hipStream_t stream);
 hipError_t launch_unpack_segments(double *dst, long beam_stride, int hy, int hz, const int *seg, long nseg, const double *in,

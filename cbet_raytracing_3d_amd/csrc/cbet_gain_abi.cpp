@@ -1,6 +1,6 @@
 // cbet_gain_abi.cpp -- the CBET stage of the C ABI (include/cbet_mi355x.h; SURVEY 8(f) f1, parity unpinned -- see the
 // header): the gain update, the trace with the CBET hooks, the sparse exchange's pack / unpack and the native one-device
-// fixed-point loop, the amplitude map of the saturation clamp.
+// fixed-point loop, the amplitude map of the saturation clamp, the pairwise exchange matrix.
 #include <cmath>
 
 #include "cbet_host_internal.h"
@@ -92,6 +92,50 @@ int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, i
     if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
         return fail(CBET_EINVAL, "cbet_pair_amplitude: slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
     return gain_field_impl(const_cast<double *>(fields), ne3d, nullptr, nullptr, nullptr, hx_lo, hx_hi, false, p, g, ctx, stream, false, amp);
+}
+
+// ---- pairwise exchange matrix (cbet_grid_kernels.hip k_exchange_matrix, k_exchange_reduce) --------
+size_t cbet_exchange_matrix_work_bytes(const cbet_params *p)
+{
+    if (!p || validate(p) != CBET_OK || p->nbeams > CBET_MAX_CBET_BEAMS) return 0;
+    const size_t npairs = (size_t)p->nbeams * (p->nbeams - 1) / 2;
+    return (size_t)exchange_groups((long)(p->nx + 2) * (p->ny + 2)) * 2 * npairs * sizeof(double);
+}
+
+int cbet_exchange_matrix(const double *fields, const double *ne3d, double *out, double *gross, void *work, int hx_lo, int hx_hi,
+                         const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx, void *stream)
+{
+    // the arguments first, the context last, as cbet_pair_amplitude
+    if (int rc = validate(p)) return rc;
+    if (p->nbeams > CBET_MAX_CBET_BEAMS)
+        return fail(CBET_EINVAL, "cbet_exchange_matrix: nbeams = %d exceeds CBET_MAX_CBET_BEAMS = %d", p->nbeams, CBET_MAX_CBET_BEAMS);
+    if (int rc = validate_gain(p, g)) return rc;
+    if (!fields) return fail(CBET_EINVAL, "cbet_exchange_matrix: fields is NULL");
+    if (!out) return fail(CBET_EINVAL, "cbet_exchange_matrix: out is NULL");
+    if (!work) return fail(CBET_EINVAL, "cbet_exchange_matrix: work is NULL");
+    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
+        return fail(CBET_EINVAL, "cbet_exchange_matrix: slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
+    if (int rc = entry_checks(ctx, p)) return rc;
+    double cs = 0, gc = 0;
+    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
+    if (p->nbeams < 2 || hx_hi == hx_lo) return CBET_OK;   // one beam exchanges with nobody; an empty slab adds nothing
+    const cbet_derived &d = ctx->d;
+    GainArgs a{};
+    grid_args(a, p, d);
+    a.nbeams = p->nbeams; a.dt = d.dt;
+    a.ncrit = d.ncrit; a.k0 = d.omega / kC;
+    a.cs = cs; a.gain_const = gc; a.iaw = g->iaw;
+    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
+    a.relax = g->relax;
+    a.fields = const_cast<double *>(fields); a.ne3d = ne3d ? ne3d : ctx->ne3d;
+    a.hx_lo = hx_lo; a.hx_hi = hx_hi;
+    a.flow = ctx->flow;
+    a.state = ctx->state;
+    a.sat = ctx->dn_max;                     // the matrix decomposes the K the solve uses: the limit is honoured
+    a.store0 = 0; a.bstride = d.edep_size;
+    CBET_ENTER_DEVICE(ctx);
+    CBET_HIP(launch_exchange_matrix(a, (double *)work, out, gross, (hipStream_t)stream));
+    return CBET_OK;
 }
 
 // ---- sparse exchange of the slab-owned CBET loop (cbet_grid_kernels.hip) -----------------------------------------

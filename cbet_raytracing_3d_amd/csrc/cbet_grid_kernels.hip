@@ -3,6 +3,8 @@
 //     reference counterpart, parity unpinned -- model and layout in DESIGN.md section 9)
 //   * k_pair_amplitude               : normalised fields -> the largest ion-acoustic amplitude a cell's pair gains correspond to
 //     (the map the saturation limit of both gain kernels is chosen by)
+//   * k_exchange_matrix, k_exchange_reduce : normalised fields -> the N x N table of energy beam j hands to beam i per pass, and
+//     its gross counterpart (lanes are beam pairs, per-workgroup tables in LDS, no atomics)
 //   * k_edep_average                 : the 27-point node average of main.cu:334-349
 // Built with -ffp-contract=off like the rest of the library: every statement of the ordered kernel and of the
 // normalisation is one IEEE operation in the order written, which is the order the CPU checker of the CBET stage
@@ -615,6 +617,200 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------
+// The pairwise exchange matrix: for NORMALISED fields, T[i][j] = sum over cells of
+// ((ds_node g_ij) I_i) I_j and Gross[i][j] = the sum of its magnitudes, every unordered pair once per cell with
+// pair_gain_fast (+ saturate_fast under SAT), the arithmetic of k_gain_field_sym.  Reads a.fields only; a.sat is honoured.
+// One workgroup of four wavefronts per z-row (grid-stride), the row cut into runs of XC = 16 cells by element index with
+// k_gain_field_sym's `sft`, so a view of the fields that starts off a 128-byte line is grouped as the aligned one.  Per run:
+//   masks : thread (cell c, group g) loads the intensity of beam 16 r + g in round r; one ballot per round gives the
+//           wavefront's share of the presence mask (I > 0 somewhere in the run), four shares are OR-ed through LDS.
+//   stage : the same thread stages its entry (I, kx, ky, kz) at [cell][slot] -- slot = the beam's rank in the mask -- with
+//           zeros where the beam is absent from the cell, so the pair adds an exact zero there; the direction entries are
+//           loaded only where I > 0.  Up to 32 present beams: 16 cells x 33; more: two halves of 8 cells x 65.
+//   pairs : LANES ARE PAIRS of the compacted slots, not cells: thread t takes pairs t, t + 256, ... of the n (n - 1) / 2,
+//           walks the cells (both beams from LDS, slot-fastest: neighbouring lanes read neighbouring words; the cell's
+//           state from the registers of the lane that holds it, by readlane) and sums x and |x| in registers, then adds once
+//           into the workgroup's table at the pair's triangular index.  Inside a round every lane owns a different pair and
+//           rounds, halves and runs are separated by barriers: no LDS atomics, and every entry's adds come in run order.
+// The table (T then Gross, 2 x npairs doubles, zeroed first) leaves by plain vector stores to work[group][2][npairs];
+// k_exchange_reduce sums the groups in order.  LDS 2 x 2016 + 4 x 528 + 7 x 64 doubles + masks = 53 KB: three workgroups,
+// twelve wavefronts per CU.  The plasma state is computed for 64 cells at a time, as in k_gain_field_sym.
+// ---------------------------------------------------------------------------------------------
+constexpr int XT = 256, XC = 16, XG = XT / XC, XROUNDS = CBET_MAX_CBET_BEAMS / XG;
+constexpr int XSTAGE = 528;                                                        // 16 x 33 >= 8 x 65
+constexpr int XPAIRS = CBET_MAX_CBET_BEAMS * (CBET_MAX_CBET_BEAMS - 1) / 2;        // 2016
+static_assert(XG * XROUNDS == 64 && XT / kWave == 4, "the mask shares below are written for four wavefronts of 4 x 16 lanes");
+
+// a double of lane `l` of the wavefront (l wave-uniform), whatever lanes are active
+__device__ __forceinline__ double readlane_f64(double v, int l)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
+// first pair index of row i of the upper triangle of an n x n matrix, rows in order: (i, i + 1), (i, i + 2), ...
+__device__ __forceinline__ int tri_start(int i, int n) { return i * (2 * n - i - 1) / 2; }
+
+template <bool FLOW, bool STATE, bool SAT>
+__global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, double *__restrict__ work)
+{
+    __shared__ double tab[2 * XPAIRS];
+    __shared__ double sI[XSTAGE], sX[XSTAGE], sY[XSTAGE], sZ[XSTAGE];
+    __shared__ double sSt[7][64];
+    __shared__ unsigned long long sMask[XT / kWave];
+    __shared__ int sBeam[CBET_MAX_CBET_BEAMS];
+    const int nb = a.nbeams, npairs = nb * (nb - 1) / 2;
+    const int tid = threadIdx.x, c = tid & (XC - 1), g = tid >> 4, lane = tid & (kWave - 1), wv = tid >> 6;
+    const int HY = a.ny + 2, HZ = a.nz + 2;
+    const long hsize = a.bstride;
+    const long total = hsize * nb;
+    const long rows = (long)(a.hx_hi - a.hx_lo) * HY;
+    const double iaw2 = a.iaw * a.iaw;
+    for (int t = tid; t < 2 * npairs; t += XT) tab[t] = 0.0;   // pairs this workgroup never meets leave as zeros
+    __syncthreads();
+    double st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_cs = 0.0, st_pi = 0.0, st_lim = 0.0, st_ds = 0.0;
+    for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int hi = a.hx_lo + (int)(row / HY), hj = (int)(row % HY);
+        const long base = ((long)hi * HY + hj) * HZ;
+        const int sft = (int)((base - a.store0) & (XC - 1));   // k_gain_field_sym's: runs are cut by element index
+        const int zb_row = (HZ + sft + XC - 1) / XC;
+        for (int ibz = 0; ibz < zb_row; ++ibz) {
+            const int hk = XC * ibz + c - sft;
+            const bool valid = hk >= 0 && hk < HZ;
+            const long hs = base + (valid ? hk : 0) - a.store0;
+            const double *fI = a.fields + hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
+            double E[XROUNDS];
+#pragma unroll
+            for (int r = 0; r < XROUNDS; ++r) {
+                const int b = XG * r + g;
+                E[r] = (b < nb && valid) ? fI[(long)b * hsize] : 0.0;
+            }
+            // this wavefront's lanes are groups 4 wv .. 4 wv + 3, sixteen cells each: bits [16 q, 16 q + 16) of a ballot
+            unsigned long long share = 0ull;
+#pragma unroll
+            for (int r = 0; r < XROUNDS; ++r) {
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(E[r] > 0.0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if ((bal >> (16 * q)) & 0xffffull) share |= 1ull << (XG * r + 4 * wv + q);
+            }
+            if (lane == 0) sMask[wv] = share;
+            // the plasma state of 64 cells at a time (thread = cell), for the four runs they make up
+            if ((ibz & 3) == 0 && tid < 64) {
+                const int hk64 = XC * ibz + tid - sft;
+                const CellState c64 = cell_state<FLOW, STATE>(a, base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                sSt[0][tid] = c64.ux; sSt[1][tid] = c64.uy; sSt[2][tid] = c64.uz; sSt[3][tid] = c64.cs;
+                sSt[4][tid] = cell_pref(a, c64) * iaw2;
+                sSt[5][tid] = SAT ? cell_sat_limit(a, c64) : 0.0;
+                sSt[6][tid] = (kC * c64.rt) * a.dt;
+            }
+            __syncthreads();                     // masks and state are in LDS; the previous run's pair loops are done
+            const unsigned long long mask = sMask[0] | sMask[1] | sMask[2] | sMask[3];
+            const int n = __popcll(mask);
+            if (n < 2) {                         // nothing to exchange (uniform over the workgroup)
+                __syncthreads();                 // sMask is read before it is written again
+                continue;
+            }
+            {
+                const int from = XC * (ibz & 3) + c;   // lane l of every wavefront holds the state of cell l & 15 of the run
+                st_ux = sSt[0][from]; st_uy = sSt[1][from]; st_uz = sSt[2][from]; st_cs = sSt[3][from];
+                st_pi = sSt[4][from]; st_lim = sSt[5][from]; st_ds = sSt[6][from];
+            }
+            // up to 32 present beams: all sixteen cells at once; more: two halves of eight cells (fewer cells, more slots)
+            const int sh = n <= 32 ? 4 : 3, lc = 1 << sh, cl = c & (lc - 1), sp = n <= 32 ? 33 : 65;
+            const int np = n * (n - 1) / 2;
+            for (int part = 0; part < (XC >> sh); ++part) {
+                if (part) __syncthreads();       // the previous half's pair loops are done
+                if ((c >> sh) == part) {
+                    int at[XROUNDS];
+                    double X[XROUNDS], Y[XROUNDS], Z[XROUNDS];
+#pragma unroll
+                    for (int r = 0; r < XROUNDS; ++r) {   // every direction load in flight before the first LDS store
+                        const int b = XG * r + g;
+                        const bool staged = b < nb && ((mask >> b) & 1ull);
+                        at[r] = staged ? cl * sp + __popcll(mask & ((1ull << b) - 1ull)) : -1;
+                        const bool here = staged && E[r] > 0.0;   // a beam absent from THIS cell gives and takes nothing
+                        const long o = (long)b * hsize;
+                        X[r] = here ? fx[o] : 0.0;
+                        Y[r] = here ? fy[o] : 0.0;
+                        Z[r] = here ? fz[o] : 0.0;
+                    }
+#pragma unroll
+                    for (int r = 0; r < XROUNDS; ++r) {
+                        if (at[r] < 0) continue;
+                        sI[at[r]] = E[r] > 0.0 ? E[r] : 0.0;
+                        sX[at[r]] = X[r]; sY[at[r]] = Y[r]; sZ[at[r]] = Z[r];
+                        if (cl == 0) sBeam[at[r]] = XG * r + g;   // (cl == 0: at[r] is the slot)
+                    }
+                }
+                __syncthreads();
+                for (int q = tid; q < np; q += XT) {
+                    // pair q of the slots' upper triangle -> (sa, sb), sa < sb
+                    const float fn = (float)(2 * n - 1);
+                    int sa = (int)((fn - sqrtf(fn * fn - 8.0f * (float)q)) * 0.5f);
+                    sa = sa < 0 ? 0 : (sa > n - 2 ? n - 2 : sa);
+                    while (tri_start(sa, n) > q) --sa;
+                    while (tri_start(sa + 1, n) <= q) ++sa;
+                    const int sb = sa + 1 + q - tri_start(sa, n);
+                    double sum_t = 0.0, sum_g = 0.0;
+                    for (int k = 0; k < lc; ++k) {
+                        const int cell = (part << sh) + k;
+                        const double ux = readlane_f64(st_ux, cell), uy = readlane_f64(st_uy, cell), uz = readlane_f64(st_uz, cell);
+                        const double cs = STATE ? readlane_f64(st_cs, cell) : a.cs;
+                        const double pref_iaw2 = readlane_f64(st_pi, cell), ds_node = readlane_f64(st_ds, cell);
+                        BeamAtCell A, B;
+                        A.I = sI[k * sp + sa]; A.kx = sX[k * sp + sa]; A.ky = sY[k * sp + sa]; A.kz = sZ[k * sp + sa];
+                        B.I = sI[k * sp + sb]; B.kx = sX[k * sp + sb]; B.ky = sY[k * sp + sb]; B.kz = sZ[k * sp + sb];
+                        double gn = pair_gain_fast(A, B, ux, uy, uz, cs, iaw2, pref_iaw2);
+                        if (SAT) gn = saturate_fast(gn, A.I, B.I, readlane_f64(st_lim, cell));
+                        const double x = ((ds_node * gn) * A.I) * B.I;
+                        sum_t += x;
+                        sum_g += fabs(x);
+                    }
+                    const int bi = sBeam[sa], bj = sBeam[sb];
+                    const int at = tri_start(bi, nb) + (bj - bi - 1);
+                    tab[at] += sum_t;
+                    tab[npairs + at] += sum_g;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    double *mine = work + (long)blockIdx.x * (2 * npairs);
+    for (int t = tid; t < 2 * npairs; t += XT) mine[t] = tab[t];
+}
+
+// One lane per unordered pair: the groups' partial sums in group order, added into the upper triangle of out (and gross);
+// the lower triangle is rewritten from the upper one, the diagonal as zero.
+__global__ void __launch_bounds__(256) k_exchange_reduce(const double *__restrict__ work, int groups, int nb,
+                                                         double *__restrict__ out, double *__restrict__ gross)
+{
+    const int npairs = nb * (nb - 1) / 2;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < nb) {
+        out[p * nb + p] = 0.0;
+        if (gross) gross[p * nb + p] = 0.0;
+    }
+    if (p >= npairs) return;
+    int i = 0;
+    while (tri_start(i + 1, nb) <= p) ++i;
+    const int j = i + 1 + p - tri_start(i, nb);
+    double t = 0.0, s = 0.0;
+    for (int grp = 0; grp < groups; ++grp) {
+        t += work[(long)grp * (2 * npairs) + p];
+        s += work[(long)grp * (2 * npairs) + npairs + p];
+    }
+    const double nt = out[i * nb + j] + t;
+    out[i * nb + j] = nt;
+    out[j * nb + i] = -nt;
+    if (gross) {
+        const double ng = gross[i * nb + j] + s;
+        gross[i * nb + j] = ng;
+        gross[j * nb + i] = ng;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // main.cu:334-349 (commented out there): edepavg[i][j][k] = (27 haloed cells around node (i,j,k)) / 27,
 // terms added in the order the reference writes them (i offset fastest, then j, then k).  A 4 x 4 x 64
 // output tile per workgroup, its 6 x 6 x 66 input block staged through LDS: HBM sees every input once.
@@ -760,6 +956,31 @@ hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t str
         else hipLaunchKernelGGL((k_pair_amplitude<false, true>), grid, block, 0, stream, a, amp);
     } else if (a.flow) hipLaunchKernelGGL((k_pair_amplitude<true, false>), grid, block, 0, stream, a, amp);
     else hipLaunchKernelGGL((k_pair_amplitude<false, false>), grid, block, 0, stream, a, amp);
+    return hipGetLastError();
+}
+
+template <bool... Bs>
+struct Exchange {
+    static void launch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, double *work) { hipLaunchKernelGGL((k_exchange_matrix<Bs...>), grid, block, 0, stream, a, work); }
+};
+template <bool... Bs>
+void dispatch_exchange(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, double *work) { Exchange<Bs...>::launch(a, grid, block, stream, work); }
+template <bool... Bs, class... Rest>
+void dispatch_exchange(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, double *work, bool first, Rest... rest)
+{
+    if (first) dispatch_exchange<Bs..., true>(a, grid, block, stream, work, rest...);
+    else dispatch_exchange<Bs..., false>(a, grid, block, stream, work, rest...);
+}
+
+hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, double *gross, hipStream_t stream)
+{
+    if (a.hx_hi <= a.hx_lo || a.nbeams < 2) return hipSuccess;
+    // the number of workgroups follows from the slab alone, never from the device: the same partial sums everywhere
+    const long groups = exchange_groups((long)(a.hx_hi - a.hx_lo) * (a.ny + 2));
+    dispatch_exchange<>(a, dim3((unsigned)groups), dim3(XT), stream, work, a.flow != nullptr, a.state != nullptr, a.sat > 0.0);
+    if (hipError_t e = hipGetLastError()) return e;
+    const int npairs = a.nbeams * (a.nbeams - 1) / 2, lanes = npairs > a.nbeams ? npairs : a.nbeams;
+    hipLaunchKernelGGL(k_exchange_reduce, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, work, (int)groups, a.nbeams, out, gross);
     return hipGetLastError();
 }
 

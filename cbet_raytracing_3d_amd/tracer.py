@@ -73,6 +73,7 @@ class RayTracer:
         self.gain_state = None          # set_gain_state(): None, "mesh" or the caller's [2, nx, ny, nz] table
         self._state_gp = None           # the gain parameters a "mesh" state takes ti_ev, z_ion and mi_over_me from
         self.saturation = 0.0           # set_saturation(): the limit of the ion-acoustic amplitude, 0.0 = none
+        self._exchange_work = None      # exchange_matrix(): the per-workgroup partial tables, allocated by the first call
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     # ---- the one spelling of what every launch repeats -------------------------------------------------------------
@@ -292,6 +293,36 @@ class RayTracer:
         api.pair_amplitude(fields, ne3d, out, x_lo, self.grid_shape[0] if x_hi is None else x_hi, self.params, gain_params,
                            self.ctx, self._stream())
         return out
+
+    def exchange_matrix(self, fields, gain_params, x_lo=0, x_hi=None, ne3d=None, out=None, gross=False):
+        """Which beam feeds which: the [nbeams, nbeams] tensor T with T[i, j] = the energy beam i gains from beam j per field
+        pass over the planes [x_lo, x_hi) (beam_gain's units; T[j, i] = -T[i, j]), ADDED into `out` if given (its upper
+        triangle; slabs and ranks sum) or into a zeroed new one.  gross=True: (T, Gross) with Gross[i, j] the sum of the
+        magnitudes of the cells' exchanges, symmetric; gross may also be a tensor to add into.
+        `fields` are normalised fields [4, nbeams, ...] as gain_field leaves them; they are not changed.  The flow and the
+        gain state are read as gain_field reads them, and the limit of set_saturation is honoured."""
+        nb = self.params.nbeams
+        _require(fields, (4, nb) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+        if self._state_is_mesh() and self.ctx.state() is None:
+            raise ValueError("exchange_matrix: set_gain_state(\"mesh\") needs tabulate() first")
+        if isinstance(self.flow, str) and self.ctx.flow() is None:
+            raise ValueError("exchange_matrix: set_flow(\"%s\") needs tabulate() first" % self.flow)
+        if out is None:
+            out = torch.zeros((nb, nb), dtype=torch.float64, device=self.device)
+        else:
+            _require(out, (nb, nb), "out")
+        if gross is True:
+            gross = torch.zeros((nb, nb), dtype=torch.float64, device=self.device)
+        elif gross is False or gross is None:
+            gross = None
+        else:
+            _require(gross, (nb, nb), "gross")
+        if self._exchange_work is None:      # one double at the least: a single beam needs none, the entry wants a pointer
+            self._exchange_work = torch.empty(max(api.exchange_matrix_work_bytes(self.params) // 8, 1), dtype=torch.float64,
+                                              device=self.device)
+        api.exchange_matrix(fields, ne3d, out, gross, self._exchange_work, x_lo, self.grid_shape[0] if x_hi is None else x_hi,
+                            self.params, gain_params, self.ctx, self._stream())
+        return out if gross is None else (out, gross)
 
     def _no_target(self, what):
         if self.flow is not None:

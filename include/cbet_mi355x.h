@@ -748,6 +748,48 @@ int cbet_context_saturation(cbet_context *ctx, double *out);
 int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, int hx_lo, int hx_hi, const cbet_params *p,
                         const cbet_gain_params *g, cbet_context *ctx, void *stream);
 
+/* ---- pairwise exchange matrix ------------------------------------------------------------- */
+/*
+ * Which beam feeds which, and how much.  For a cell of the haloed deposit grid and beams i != j both present there
+ * (I_i > 0, I_j > 0, k_i != k_j, eps > 0), with the NORMALISED fields (I, kx, ky, kz) a gain update leaves:
+ *     x_ij(cell) = ((ds_node * g_ij) * I_i) * I_j           ds_node = (c * rt) * dt, the divisor of the normalisation
+ * g_ij is the cell's pair gain exactly as the gain kernels form it, pref * P(eta_ij) with q = k_j - k_i: it reads the
+ * context's flow table and state table if selected, and it is scaled by min(1, lim / w) when the context holds a saturation
+ * limit -- unlike cbet_pair_amplitude the matrix HONOURS dn_max, because it decomposes the K that the solve uses.
+ *     T[i][j]     = sum over cells of x_ij     the energy beam i gains from beam j per field pass, in beam_gain's units;
+ *                                              T[j][i] = -T[i][j] and T[i][i] = 0
+ *     Gross[i][j] = sum over cells of |x_ij|   symmetric; the scale a tolerance on T[i][j] is taken against
+ * Identity: sum_j T[i][j] = sum over cells of ds_node * I_i * K_i, K the unrelaxed sum of the gain kernels.
+ *
+ * cbet_exchange_matrix: `fields` are NORMALISED whole-grid device fields [4][nbeams][hsize] under cbet_pair_amplitude's
+ * contract, never written; the planes [hx_lo, hx_hi) are covered.  `out` is device [nbeams][nbeams]: its upper triangle is
+ * ADDED into (slabs and ranks sum; the caller zeroes it before the first call), its lower triangle is rewritten as the
+ * negated upper one and its diagonal as 0.  `gross` is the same shape (upper triangle added into, lower mirrored, diagonal
+ * 0), or NULL.  ne3d NULL = the context's table.  Stream-ordered, no synchronisation, no allocation.
+ * Every unordered pair is evaluated once per cell with the pair-once gain kernel's pair function (and its clamp): the
+ * arithmetic of the kernel cbet_cbet_solve runs, a few ulp per pair from the ordered statements.  Per-workgroup partial
+ * tables are written to `work` and summed in workgroup order by a second kernel: no floating-point atomics, so two calls on
+ * the same inputs give the same bits, on any device -- the number of workgroups is min(rows, CBET_EXCHANGE_MAX_GROUPS) with
+ * rows = (hx_hi - hx_lo) (ny + 2), never the device's size.  `work` holds [groups][2][nbeams (nbeams - 1) / 2] doubles;
+ * cbet_exchange_matrix_work_bytes(p) is the size for the whole grid, enough for any slab: at most 768 x 2 x 2016 doubles =
+ * 24.8 MB (0 for one beam or bad parameters).
+ * CBET_EINVAL naming the offence: nbeams > CBET_MAX_CBET_BEAMS, a slab outside [0, nx + 2] or reversed, NULL fields, out
+ * or work.  With nbeams == 1 nothing is launched and `out` keeps the caller's zeros; an empty slab changes nothing.
+ *
+ * cbet_exchange_matrix_host: the host twin and the reference of the device path at any size.  HOST pointers; no context:
+ * ne3d [nx][ny][nz] (required), flow [3][nx][ny][nz] or NULL = the closed-form ramp about the origin, state [2][nx][ny][nz]
+ * or NULL = cbet_gain_constants' scalars, dn_max (0 = none) explicit.  It runs the ORDERED kernel's statements, one IEEE
+ * operation per written operator (the statements of DESIGN.md sections 9 and 17), cells in index order, every pair's two
+ * sums compensated (Neumaier), and makes no HIP call.  out / gross as above.
+ */
+#define CBET_EXCHANGE_MAX_GROUPS 768
+size_t cbet_exchange_matrix_work_bytes(const cbet_params *p);
+int cbet_exchange_matrix(const double *fields, const double *ne3d, double *out, double *gross, void *work, int hx_lo, int hx_hi,
+                         const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx, void *stream);
+int cbet_exchange_matrix_host(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo, int hx_hi,
+                              const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
+                              double dn_max);
+
 /* ---- exit pass --------------------------------------------------------------- */
 /*
  * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
