@@ -7,39 +7,49 @@
 
 using namespace cbet;
 
-int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo,
-                          int hx_hi, bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx,
-                          void *stream, bool consume, double *amplitude)
+GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
+                         const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
+                         int hx_lo, int hx_hi, bool packed)
 {
-    // amplitude: not a gain update but cbet_pair_amplitude's launch on the same argument block (gain is NULL then)
-    if (int rc = entry_checks(ctx, p)) return rc;
-    if (int rc = validate_gain(p, g)) return rc;
-    if (!fields || !(amplitude ? amplitude : gain)) return fail(CBET_EINVAL, "NULL device pointer");
-    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo) return fail(CBET_EINVAL, "slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
-    double cs = 0, gc = 0;
-    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
-    const cbet_derived &d = ctx->d;
     GainArgs a{};
     grid_args(a, p, d);
     a.nbeams = p->nbeams; a.dt = d.dt;
     a.ncrit = d.ncrit; a.k0 = d.omega / kC;
-    a.cs = cs; a.gain_const = gc; a.iaw = g->iaw;
-    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
-    a.relax = g->relax;
-    a.fields = fields; a.ne3d = ne3d ? ne3d : ctx->ne3d; a.gain = gain; a.scratch = scratch; a.change = change;
+    ramp_args(a, g, cs);
+    a.gain_const = gc; a.iaw = g->iaw; a.relax = g->relax;
+    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat;
     a.hx_lo = hx_lo; a.hx_hi = hx_hi;
-    a.consume = (consume && scratch) ? 1 : 0;
-    a.frozen = g->directions_frozen ? 1 : 0;
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
-    a.flow = ctx->flow;
-    a.state = ctx->state;
-    a.sat = amplitude ? 0.0 : ctx->dn_max;   // the map is the unclamped amplitude
     a.store0 = packed ? (long)hx_lo * plane : 0;
     a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
+    return a;
+}
+
+int cbet::slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p)
+{
+    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
+        return fail(CBET_EINVAL, "%sslab [%d,%d) outside the haloed grid [0,%d)", who, hx_lo, hx_hi, p->nx + 2);
+    return CBET_OK;
+}
+
+int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo,
+                          int hx_hi, bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx,
+                          void *stream, bool consume)
+{
+    if (int rc = entry_checks(ctx, p)) return rc;
+    if (int rc = validate_gain(p, g)) return rc;
+    if (!fields || !gain) return fail(CBET_EINVAL, "NULL device pointer");
+    if (int rc = slab_check("", hx_lo, hx_hi, p)) return rc;
+    double cs = 0, gc = 0;
+    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (hx_hi == hx_lo) return CBET_OK;   // an empty slab (more ranks than planes)
+    GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, hx_lo,
+                           hx_hi, packed);
+    a.gain = gain; a.scratch = scratch; a.change = change;
+    a.consume = (consume && scratch) ? 1 : 0;
+    a.frozen = g->directions_frozen ? 1 : 0;
     CBET_ENTER_DEVICE(ctx);
-    if (amplitude) CBET_HIP(launch_pair_amplitude(a, amplitude, (hipStream_t)stream));
-    else CBET_HIP(launch_gain_field(a, (hipStream_t)stream));
+    CBET_HIP(launch_gain_field(a, (hipStream_t)stream));
     return CBET_OK;
 }
 
@@ -89,9 +99,16 @@ int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, i
     if (int rc = validate_gain(p, g)) return rc;
     if (!fields) return fail(CBET_EINVAL, "cbet_pair_amplitude: fields is NULL");
     if (!amp) return fail(CBET_EINVAL, "cbet_pair_amplitude: amp is NULL");
-    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
-        return fail(CBET_EINVAL, "cbet_pair_amplitude: slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
-    return gain_field_impl(const_cast<double *>(fields), ne3d, nullptr, nullptr, nullptr, hx_lo, hx_hi, false, p, g, ctx, stream, false, amp);
+    if (int rc = slab_check("cbet_pair_amplitude: ", hx_lo, hx_hi, p)) return rc;
+    if (int rc = entry_checks(ctx, p)) return rc;
+    double cs = 0, gc = 0;
+    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
+    if (hx_hi == hx_lo) return CBET_OK;
+    // sat = 0: the map is the unclamped amplitude
+    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, 0.0, hx_lo, hx_hi, false);
+    CBET_ENTER_DEVICE(ctx);
+    CBET_HIP(launch_pair_amplitude(a, amp, (hipStream_t)stream));
+    return CBET_OK;
 }
 
 // ---- pairwise exchange matrix (cbet_grid_kernels.hip k_exchange_matrix, k_exchange_reduce) --------
@@ -113,26 +130,13 @@ int cbet_exchange_matrix(const double *fields, const double *ne3d, double *out, 
     if (!fields) return fail(CBET_EINVAL, "cbet_exchange_matrix: fields is NULL");
     if (!out) return fail(CBET_EINVAL, "cbet_exchange_matrix: out is NULL");
     if (!work) return fail(CBET_EINVAL, "cbet_exchange_matrix: work is NULL");
-    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
-        return fail(CBET_EINVAL, "cbet_exchange_matrix: slab [%d,%d) outside the haloed grid [0,%d)", hx_lo, hx_hi, p->nx + 2);
+    if (int rc = slab_check("cbet_exchange_matrix: ", hx_lo, hx_hi, p)) return rc;
     if (int rc = entry_checks(ctx, p)) return rc;
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (p->nbeams < 2 || hx_hi == hx_lo) return CBET_OK;   // one beam exchanges with nobody; an empty slab adds nothing
-    const cbet_derived &d = ctx->d;
-    GainArgs a{};
-    grid_args(a, p, d);
-    a.nbeams = p->nbeams; a.dt = d.dt;
-    a.ncrit = d.ncrit; a.k0 = d.omega / kC;
-    a.cs = cs; a.gain_const = gc; a.iaw = g->iaw;
-    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
-    a.relax = g->relax;
-    a.fields = const_cast<double *>(fields); a.ne3d = ne3d ? ne3d : ctx->ne3d;
-    a.hx_lo = hx_lo; a.hx_hi = hx_hi;
-    a.flow = ctx->flow;
-    a.state = ctx->state;
-    a.sat = ctx->dn_max;                     // the matrix decomposes the K the solve uses: the limit is honoured
-    a.store0 = 0; a.bstride = d.edep_size;
+    // sat = the context's: the matrix decomposes the K the solve uses, the limit is honoured
+    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, hx_lo, hx_hi, false);
     CBET_ENTER_DEVICE(ctx);
     CBET_HIP(launch_exchange_matrix(a, (double *)work, out, gross, (hipStream_t)stream));
     return CBET_OK;

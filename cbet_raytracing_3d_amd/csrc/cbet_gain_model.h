@@ -1,0 +1,116 @@
+// cbet_gain_model.h -- the statements of the CBET gain stage (DESIGN.md sections 9, 16, 17), each written once for the gfx950
+// kernels (cbet_grid_kernels.hip) and the host twin of the exchange matrix (cbet_exchange_host.cpp): a deposit-grid cell's
+// plasma state, the prefactor and the saturation limit that follow from it, and the gain of an ORDERED beam pair with its
+// clamp.  The pair-once kernels' fast pair function (pair_gain_fast, saturate_fast) is device-only and stays with them.
+// Built with -ffp-contract=off on both sides: every operator below is one IEEE fp64 operation, in the order written, so a
+// kernel and the twin agree bit for bit.  The includer provides sqrt and fabs of a double: <hip/hip_runtime.h> or <cmath>.
+#ifndef CBET_GAIN_MODEL_H_
+#define CBET_GAIN_MODEL_H_
+
+#include "cbet_device.h"
+#include "cbet_hd.h"
+#include "cbet_node_model.h"
+
+namespace cbet {
+
+struct CellState {
+    double frac, eps, rt, ux, uy, uz;   // ne/ncrit, 1 - ne/ncrit, sqrt(eps), flow velocity
+    double cs, gc;                      // sound speed and gain_const: the node's (state table) or the uniform ones
+};
+
+// Deposit-grid cell h = ((hi * (ny+2)) + hj) * (nz+2) + hk takes its plasma state from node (hi-1, hj-1, hk-1), clamped.
+CBET_HD void cell_node(const GainArgs &a, long h, int &i, int &j, int &k)
+{
+    const int sYh = a.nz + 2;
+    const long sXh = (long)(a.ny + 2) * sYh;
+    const int hi = (int)(h / sXh);
+    const int rem = (int)(h - hi * sXh);
+    const int hj = rem / sYh, hk = rem - hj * sYh;
+    i = hi < 1 ? 0 : (hi > a.nx ? a.nx - 1 : hi - 1);
+    j = hj < 1 ? 0 : (hj > a.ny ? a.ny - 1 : hj - 1);
+    k = hk < 1 ? 0 : (hk > a.nz ? a.nz - 1 : hk - 1);
+}
+
+// FLOW: the flow velocity is read from GainArgs.flow (a node table, cbet_target.hip k_tabulate_flow) instead of the closed-form
+// radial ramp about the origin.  STATE: the sound speed and gain_const are read from GainArgs.state (a node table,
+// cbet_mesh.hip k_mesh_state) instead of the uniform GainArgs.cs / gain_const.  Template arguments, the kernels' own: as plain
+// bool parameters the same statements compile to other code in the pair-once kernels, whose register budget is spent.
+template <bool FLOW, bool STATE>
+CBET_HD CellState cell_state(const GainArgs &a, long h)
+{
+    int i, j, k;
+    cell_node(a, h, i, j, k);
+    CellState c;
+    c.frac = a.ne3d[((long)i * a.ny + j) * a.nz + k] / a.ncrit;
+    c.eps = 1.0 - c.frac;
+    c.rt = c.eps > 0.0 ? sqrt(c.eps) : 0.0;
+    if (STATE) {
+        const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
+        c.cs = a.state[node];
+        c.gc = a.state[node + nodes];
+    } else {
+        c.cs = a.cs;
+        c.gc = a.gain_const;
+    }
+    if (FLOW) {
+        const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
+        c.ux = a.flow[node];
+        c.uy = a.flow[node + nodes];
+        c.uz = a.flow[node + 2 * nodes];
+        return c;
+    }
+    double xc, yc, zc, rr;                                            // the sphere about the origin: no offset, rho' == rho
+    node_centre(a, i, j, k, 0.0, 0.0, 0.0, xc, yc, zc, rr);
+    radial_flow(a, rr, rr, xc, yc, zc, c.ux, c.uy, c.uz);
+    return c;
+}
+// ... chosen at run time by the tables the block carries (the host twin).
+CBET_HD CellState cell_state(const GainArgs &a, long h)
+{
+    if (a.flow) return a.state ? cell_state<true, true>(a, h) : cell_state<true, false>(a, h);
+    return a.state ? cell_state<false, true>(a, h) : cell_state<false, false>(a, h);
+}
+
+// The prefactor of a cell's pair gains, gain_const (ne / ncrit) / (iaw sqrt(eps)); zero at and above critical density.
+CBET_HD double cell_pref(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? c.gc * c.frac * (1.0 / a.iaw) / c.rt : 0.0; }
+
+// Saturation of the ion-acoustic wave.  Scattering off a grating of relative amplitude dn/n exchanges
+// intensity at the rate kap (dn/n) sqrt(Ii Ij), kap = (k0 / 2) (ne / ncrit) / sqrt(eps); the amplitude this model's pair gain
+// corresponds to is therefore |G_ij| sqrt(Ii Ij) / kap.  cell_sat_limit: the value w = |G_ij| sqrt(Ii Ij) may reach under
+// the limit dn_max; zero at and above critical density, where the gain is zero too.
+CBET_HD double cell_kap(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? ((0.5 * a.k0) * c.frac) / c.rt : 0.0; }
+CBET_HD double cell_sat_limit(const GainArgs &a, const CellState &c) { return a.sat * cell_kap(a, c); }
+
+// One beam's normalised entry of a cell, and the ion-acoustic wave of the ordered pair (i, j): q = k_j - k_i and |q|.
+struct BeamAtCell { double I, kx, ky, kz; };
+struct PairWave { double qx, qy, qz, kiaw; };
+CBET_HD BeamAtCell beam_at(const double *fI, const double *fx, const double *fy, const double *fz, long o) { return {fI[o], fx[o], fy[o], fz[o]}; }
+CBET_HD PairWave pair_wave(const BeamAtCell &bi, const BeamAtCell &bj)
+{
+    PairWave w;
+    w.qx = bj.kx - bi.kx; w.qy = bj.ky - bi.ky; w.qz = bj.kz - bi.kz;
+    w.kiaw = sqrt(w.qx * w.qx + w.qy * w.qy + w.qz * w.qz);
+    return w;
+}
+// Both beams are present in the cell and not parallel: the pair exchanges something.
+CBET_HD bool pair_present(const BeamAtCell &bi, const BeamAtCell &bj, const PairWave &w) { return bi.I > 0.0 && bj.I > 0.0 && w.kiaw > 0.0; }
+// G_ij = pref P(eta_ij) of a present pair, iaw2 = iaw^2; G_ji = -G_ij exactly (q and with it eta change sign, P is odd).
+CBET_HD double pair_gain(const CellState &c, double pref, double iaw2, const PairWave &w)
+{
+    const double eta = (0.0 - (w.qx * c.ux + w.qy * c.uy + w.qz * c.uz)) / (w.kiaw * c.cs + 1e-10);
+    const double e2 = eta * eta;
+    const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
+    return pref * P;
+}
+// The clamp: g scaled by min(1, lim / w), w = |g| sqrt(Ii Ij) (pair_swing) -- one factor for (i, j) and (j, i); a
+// pair below the limit keeps its bits.
+CBET_HD double pair_swing(double g, double Ii, double Ij) { return fabs(g) * sqrt(Ii * Ij); }
+CBET_HD double pair_clamp(double g, double Ii, double Ij, double lim)
+{
+    const double w = pair_swing(g, Ii, Ij);
+    if (w > lim) g = g * (lim / w);
+    return g;
+}
+
+}  // namespace cbet
+#endif

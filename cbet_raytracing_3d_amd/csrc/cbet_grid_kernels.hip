@@ -6,74 +6,21 @@
 //   * k_exchange_matrix, k_exchange_reduce : normalised fields -> the N x N table of energy beam j hands to beam i per pass, and
 //     its gross counterpart (lanes are beam pairs, per-workgroup tables in LDS, no atomics)
 //   * k_edep_average                 : the 27-point node average of main.cu:334-349
+// The gain model -- a cell's plasma state (cell_state), its prefactor and saturation limit, the ordered pair gain and its clamp
+// -- is cbet_gain_model.h's, written once for these kernels and the exchange matrix's host twin (cbet_exchange_host.cpp).  Shared
+// inside this file: brick_cell (k_gain_field, k_pair_amplitude), row_runs (k_gain_field_sym, k_exchange_matrix), pair_gain_fast
+// and saturate_fast (the two pair-once kernels), one dispatch of run-time switches onto template arguments (all four).
 // Built with -ffp-contract=off like the rest of the library: every statement of the ordered kernel and of the
 // normalisation is one IEEE operation in the order written, which is the order the CPU checker of the CBET stage
 // uses; the pair-once kernel's pair function (pair_gain_fast) is the exception and says so.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "cbet_device.h"
-#include "cbet_node_model.h"
+#include "cbet_gain_model.h"
 
 namespace cbet {
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// CBET extension (no reference counterpart; model and layout in DESIGN.md section 9).
-// Deposit-grid cell (hi,hj,hk) takes its plasma state from node (hi-1,hj-1,hk-1), clamped.
-// ---------------------------------------------------------------------------------------------
-struct CellState {
-    double frac, eps, rt, ux, uy, uz;   // ne/ncrit, 1 - ne/ncrit, sqrt(eps), flow velocity
-    double cs, gc;                      // sound speed and gain_const: the node's (STATE) or the uniform ones
-};
-
-// FLOW: the flow velocity is read from GainArgs.flow (a node table, cbet_target.hip k_tabulate_flow) instead of the closed-form radial
-// ramp about the origin.  STATE: the sound speed and gain_const are read from GainArgs.state (a node table, cbet_mesh.hip k_mesh_state)
-// instead of the uniform GainArgs.cs / gain_const.
-template <bool FLOW, bool STATE>
-__device__ __forceinline__ CellState cell_state(const GainArgs &a, long h)
-{
-    const int sYh = a.nz + 2;
-    const long sXh = (long)(a.ny + 2) * sYh;
-    const int hi = (int)(h / sXh);
-    const int rem = (int)(h - hi * sXh);
-    const int hj = rem / sYh, hk = rem - hj * sYh;
-    const int i = hi < 1 ? 0 : (hi > a.nx ? a.nx - 1 : hi - 1);
-    const int j = hj < 1 ? 0 : (hj > a.ny ? a.ny - 1 : hj - 1);
-    const int k = hk < 1 ? 0 : (hk > a.nz ? a.nz - 1 : hk - 1);
-    CellState c;
-    c.frac = a.ne3d[((long)i * a.ny + j) * a.nz + k] / a.ncrit;
-    c.eps = 1.0 - c.frac;
-    c.rt = c.eps > 0.0 ? sqrt(c.eps) : 0.0;
-    if (STATE) {
-        const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
-        c.cs = a.state[node];
-        c.gc = a.state[node + nodes];
-    } else {
-        c.cs = a.cs;
-        c.gc = a.gain_const;
-    }
-    if (FLOW) {
-        const long nodes = (long)a.nx * a.ny * a.nz, node = ((long)i * a.ny + j) * a.nz + k;
-        c.ux = a.flow[node];
-        c.uy = a.flow[node + nodes];
-        c.uz = a.flow[node + 2 * nodes];
-        return c;
-    }
-    double xc, yc, zc, rr;                                            // the sphere about the origin: no offset, rho' == rho
-    node_centre(a, i, j, k, 0.0, 0.0, 0.0, xc, yc, zc, rr);
-    radial_flow(a, rr, rr, xc, yc, zc, c.ux, c.uy, c.uz);
-    return c;
-}
-
-// The prefactor of a cell's pair gains, gain_const (ne / ncrit) / (iaw sqrt(eps)); zero at and above critical density.
-__device__ __forceinline__ double cell_pref(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? c.gc * c.frac * (1.0 / a.iaw) / c.rt : 0.0; }
-
-// Saturation of the ion-acoustic wave.  Scattering off a grating of relative amplitude dn/n exchanges
-// intensity at the rate kap (dn/n) sqrt(Ii Ij), kap = (k0 / 2) (ne / ncrit) / sqrt(eps); the amplitude this model's pair gain
-// corresponds to is therefore |G_ij| sqrt(Ii Ij) / kap.  cell_sat_limit: the value w = |G_ij| sqrt(Ii Ij) may reach under
-// the limit dn_max; zero at and above critical density, where the gain is zero too.
-__device__ __forceinline__ double cell_kap(const GainArgs &a, const CellState &c) { return c.eps > 0.0 ? ((0.5 * a.k0) * c.frac) / c.rt : 0.0; }
-__device__ __forceinline__ double cell_sat_limit(const GainArgs &a, const CellState &c) { return a.sat * cell_kap(a, c); }
 
 // The epilogue of both gain kernels: the wave's sums of |new - old| and |new| into GainArgs.change, two atomics per wave.
 __device__ __forceinline__ void report_change(const GainArgs &a, int lane, double sum_change, double sum_abs)
@@ -117,40 +64,48 @@ __device__ __forceinline__ void normalise_entry(const GainArgs &a, const CellSta
     fI[o] = I; fx[o] = kx; fy[o] = ky; fz[o] = kz;
 }
 
-// fields (E, Dx, Dy, Dz) -> gain coefficient, one wavefront per 2 x 4 x 8 brick of deposit-grid cells
-// (z fastest: every load is eight 64-B runs).  A compact brick keeps the set of beams present
-// ANYWHERE in the wave small -- the beam loops below run over that set (a ballot-built bit mask),
+// The walk of k_gain_field and k_pair_amplitude: one wavefront per 2 x 4 x 8 brick of deposit-grid cells (z fastest: every
+// load is eight 64-B runs), the bricks that touch the slab [hx_lo, hx_hi) in z, y, x order.  A compact brick keeps the set of
+// beams present ANYWHERE in the wave small -- the beam loops of both kernels run over that set (a ballot-built bit mask),
 // and a 64-cell z-row crosses several times more beams than a brick does.
+// h, hs: the lane's cell of the haloed grid and its index into the (possibly slab-packed) arrays; cell store0 where not valid
+struct BrickCell { bool valid; long h, hs; };
+__host__ __device__ inline long brick_count(const GainArgs &a) { return (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8); }
+__device__ __forceinline__ BrickCell brick_cell(const GainArgs &a, long brick, int lane)
+{
+    const int HY = a.ny + 2, HZ = a.nz + 2;
+    const int bx0 = a.hx_lo >> 1, by = (HY + 3) / 4, bz = (HZ + 7) / 8;
+    const int ibz = (int)(brick % bz);
+    const long t = brick / bz;
+    const int iby = (int)(t % by), ibx = bx0 + (int)(t / by);
+    const int hi = 2 * ibx + (lane >> 5), hj = 4 * iby + ((lane >> 3) & 3), hk = 8 * ibz + (lane & 7);
+    const bool valid = hi >= a.hx_lo && hi < a.hx_hi && hj < HY && hk < HZ;
+    const long h = valid ? ((long)hi * HY + hj) * HZ + hk : a.store0;
+    return {valid, h, h - a.store0};
+}
+
+// fields (E, Dx, Dy, Dz) -> gain coefficient, brick by brick (brick_cell).
 //   phase 1: every entry a beam's rays touched (E != 0) is normalised in place to (I, kx, ky, kz), I = 0 where the
 //            beam is not present (E <= 0); with GainArgs.frozen only the energy entry (normalise_entry).
-//   phase 2: K_i = sum_{j != i} G_ij I_j, beams in increasing order; gain <- gain + relax (K - gain),
-//            stored only where it changes.
-// SAT (GainArgs.sat > 0): every pair gain is scaled by min(1, lim / w), w = |G_ij| sqrt(Ii Ij) -- one factor for (i, j) and
-// (j, i), so the cell's exchange still cancels; a pair below the limit keeps its bits ((pref * P) * Ij either way).
+//   phase 2: K_i = sum_{j != i} G_ij I_j, beams in increasing order; gain <- gain + relax (K - gain), stored only where it changes.
+// SAT (GainArgs.sat > 0): every pair gain goes through pair_clamp -- one factor for (i, j) and (j, i), so the cell's
+// exchange still cancels; a pair below the limit keeps its bits ((pref * P) * Ij either way).
 template <bool FLOW, bool STATE, bool SAT>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
-    const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride;                 // entries stored per beam (the whole haloed grid, or one x-slab of it)
     const long total = hsize * a.nbeams;
-    const int bx0 = a.hx_lo >> 1, bx = ((a.hx_hi + 1) >> 1) - bx0;   // brick columns touching the slab [hx_lo, hx_hi)
-    const int by = (HY + 3) / 4, bz = (HZ + 7) / 8;
-    const long bricks = (long)bx * by * bz;
+    const long bricks = brick_count(a);
     const int lane = threadIdx.x & (kWave - 1);
     const long wave0 = (long)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
     const long nwaves = (long)gridDim.x * (blockDim.x / kWave);
     const double iaw2 = a.iaw * a.iaw;
     double sum_change = 0.0, sum_abs = 0.0;
     for (long brick = wave0; brick < bricks; brick += nwaves) {
-        const int ibz = (int)(brick % bz);
-        const long t = brick / bz;
-        const int iby = (int)(t % by), ibx = bx0 + (int)(t / by);
-        const int hi = 2 * ibx + (lane >> 5), hj = 4 * iby + ((lane >> 3) & 3), hk = 8 * ibz + (lane & 7);
-        const bool valid = hi >= a.hx_lo && hi < a.hx_hi && hj < HY && hk < HZ;
-        const long h = valid ? ((long)hi * HY + hj) * HZ + hk : a.store0;
-        const long hs = h - a.store0;               // index into the (possibly slab-packed) arrays
-        double *fI = a.fields + hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
-        const CellState c = cell_state<FLOW, STATE>(a, h);
+        const BrickCell cell = brick_cell(a, brick, lane);
+        const bool valid = cell.valid;
+        double *fI = a.fields + cell.hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
+        const CellState c = cell_state<FLOW, STATE>(a, cell.h);
         const double kmag = a.k0 * c.rt;
         const double ds_node = (kC * c.rt) * a.dt;  // group speed x dt: energy x length -> intensity
         unsigned long long mask = 0ull;             // beams present in some cell of this brick
@@ -167,35 +122,24 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
             const long oi = (long)bi * hsize;
             double raw = 0.0;
             if ((mask >> bi) & 1ull) {
-                const double Ii = fI[oi];
-                const double kxi = fx[oi], kyi = fy[oi], kzi = fz[oi];
+                const BeamAtCell Bi = beam_at(fI, fx, fy, fz, oi);
                 double acc = 0.0;
                 unsigned long long m = mask & ~(1ull << bi);
                 while (m != 0ull) {
                     const int bj = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    const long oj = (long)bj * hsize;
-                    const double Ij = fI[oj];
-                    const double qx = fx[oj] - kxi, qy = fy[oj] - kyi, qz = fz[oj] - kzi;
-                    const double kiaw = sqrt(qx * qx + qy * qy + qz * qz);
-                    if (valid && Ii > 0.0 && Ij > 0.0 && kiaw > 0.0) {
-                        const double eta = (0.0 - (qx * c.ux + qy * c.uy + qz * c.uz)) / (kiaw * c.cs + 1e-10);
-                        const double e2 = eta * eta;
-                        const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
-                        if (SAT) {
-                            double g = pref * P;
-                            const double w = fabs(g) * sqrt(Ii * Ij);
-                            if (w > lim) g = g * (lim / w);
-                            acc += g * Ij;
-                        } else {
-                            acc += pref * P * Ij;
-                        }
+                    const BeamAtCell Bj = beam_at(fI, fx, fy, fz, (long)bj * hsize);
+                    const PairWave w = pair_wave(Bi, Bj);
+                    if (valid && pair_present(Bi, Bj, w)) {
+                        double g = pair_gain(c, pref, iaw2, w);
+                        if (SAT) g = pair_clamp(g, Bi.I, Bj.I, lim);
+                        acc += g * Bj.I;
                     }
                 }
                 raw = acc;
             }
             if (valid) {
-                double *gp = a.gain + oi + hs;
+                double *gp = a.gain + oi + cell.hs;
                 const double old = *gp;
                 const double nw = old + a.relax * (raw - old);
                 if (nw != old) *gp = nw;
@@ -214,25 +158,18 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 template <bool FLOW, bool STATE>
 __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double *__restrict__ amp)
 {
-    const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride;
     const long total = hsize * a.nbeams;
-    const int bx0 = a.hx_lo >> 1, bx = ((a.hx_hi + 1) >> 1) - bx0;
-    const int by = (HY + 3) / 4, bz = (HZ + 7) / 8;
-    const long bricks = (long)bx * by * bz;
+    const long bricks = brick_count(a);
     const int lane = threadIdx.x & (kWave - 1);
     const long wave0 = (long)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
     const long nwaves = (long)gridDim.x * (blockDim.x / kWave);
     const double iaw2 = a.iaw * a.iaw;
     for (long brick = wave0; brick < bricks; brick += nwaves) {
-        const int ibz = (int)(brick % bz);
-        const long t = brick / bz;
-        const int iby = (int)(t % by), ibx = bx0 + (int)(t / by);
-        const int hi = 2 * ibx + (lane >> 5), hj = 4 * iby + ((lane >> 3) & 3), hk = 8 * ibz + (lane & 7);
-        const bool valid = hi >= a.hx_lo && hi < a.hx_hi && hj < HY && hk < HZ;
-        const long h = valid ? ((long)hi * HY + hj) * HZ + hk : 0;
-        const double *fI = a.fields + h, *fx = fI + total, *fy = fx + total, *fz = fy + total;
-        const CellState c = cell_state<FLOW, STATE>(a, h);
+        const BrickCell cell = brick_cell(a, brick, lane);
+        const bool valid = cell.valid;
+        const double *fI = a.fields + cell.hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
+        const CellState c = cell_state<FLOW, STATE>(a, cell.h);
         unsigned long long mask = 0ull;             // beams present in some cell of this brick
         for (int b = 0; b < a.nbeams; ++b) {
             const double I = valid ? fI[(long)b * hsize] : 0.0;
@@ -245,34 +182,22 @@ __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double
         while (mi != 0ull) {
             const int bi = __ffsll((long long)mi) - 1;
             mi &= mi - 1;
-            const long oi = (long)bi * hsize;
-            const double Ii = fI[oi];
-            const double kxi = fx[oi], kyi = fy[oi], kzi = fz[oi];
+            const BeamAtCell Bi = beam_at(fI, fx, fy, fz, (long)bi * hsize);
             unsigned long long m = mi;              // the beams after bi
             while (m != 0ull) {
                 const int bj = __ffsll((long long)m) - 1;
                 m &= m - 1;
-                const long oj = (long)bj * hsize;
-                const double Ij = fI[oj];
-                const double qx = fx[oj] - kxi, qy = fy[oj] - kyi, qz = fz[oj] - kzi;
-                const double kiaw = sqrt(qx * qx + qy * qy + qz * qz);
-                if (valid && Ii > 0.0 && Ij > 0.0 && kiaw > 0.0) {
-                    const double eta = (0.0 - (qx * c.ux + qy * c.uy + qz * c.uz)) / (kiaw * c.cs + 1e-10);
-                    const double e2 = eta * eta;
-                    const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
-                    const double g = pref * P;
-                    const double w = fabs(g) * sqrt(Ii * Ij);
-                    if (w > top) top = w;
+                const BeamAtCell Bj = beam_at(fI, fx, fy, fz, (long)bj * hsize);
+                const PairWave w = pair_wave(Bi, Bj);
+                if (valid && pair_present(Bi, Bj, w)) {
+                    const double sw = pair_swing(pair_gain(c, pref, iaw2, w), Bi.I, Bj.I);
+                    if (sw > top) top = sw;
                 }
             }
         }
-        if (valid) amp[h] = kap > 0.0 ? top / kap : 0.0;
+        if (valid) amp[cell.h] = kap > 0.0 ? top / kap : 0.0;
     }
 }
-
-struct BeamAtCell {
-    double I, kx, ky, kz;
-};
 
 // ---------------------------------------------------------------------------------------------
 // The same update with every unordered beam pair evaluated ONCE (G_ji = -G_ij exactly: eta changes sign, P is odd) and
@@ -310,6 +235,24 @@ struct BeamAtCell {
 // ---------------------------------------------------------------------------------------------
 constexpr int LC = 16, LG = 4, LCAP = 20, LROUNDS = 64 / LG;
 constexpr int LCH = 4, LCH3 = 8;   // rounds whose loads are in flight together in phase 1 / phase 3
+
+// The cut of z-row (hi, hj) of the haloed grid into runs of LC cells, k_gain_field_sym's and k_exchange_matrix's.  Runs start
+// on 128-byte lines of the arrays, not at z = 16 k of the row: the row's first entry sits `sft` doubles into a line (rows are
+// nz + 2 doubles long), so the first run holds the 16 - sft cells up to the next line and every later one is exactly one line
+// per beam and array (beams whose stride from beam 0 is an odd multiple of 8 doubles -- every second one at 256^3 -- stay
+// half a line off: the arrays' beam stride is the caller's).  Plain members and a function of scalars on purpose: the validity
+// test and the clamp of the 64-cell state index stay written out in both kernels, since either of them behind a call -- or
+// any member function here -- changes the code the compiler emits for kernels whose register budget is spent.
+struct RowRuns { long base; int sft, count; };   // the row's first cell, the shift, the number of runs
+__device__ __forceinline__ RowRuns row_runs(const GainArgs &a, int hi, int hj)
+{
+    const int hz = a.nz + 2;
+    const long base = ((long)hi * (a.ny + 2) + hj) * hz;
+    const int sft = (int)((base - a.store0) & (LC - 1));
+    return {base, sft, (hz + sft + LC - 1) / LC};
+}
+// z of lane c's cell of run `run`: outside [0, nz + 2) for the lanes in front of the first run's cells and behind the last's
+__device__ __forceinline__ int run_hk(int run, int c, int sft) { return LC * run + c - sft; }
 
 // pref * P(eta_ij) as ONE quotient: with N = -(q . u) and D = |q| cs + 1e-10 (eta = N / D),
 //   P = iaw^2 eta / ((eta^2 - 1)^2 + iaw^2 eta^2) = iaw^2 N D^3 / ((N^2 - D^2)^2 + iaw^2 N^2 D^2),
@@ -393,17 +336,11 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
     double sum_change = 0.0, sum_abs = 0.0;
     double st_rt = 0.0, st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_pref = 0.0, st_cs = 0.0, st_lim = 0.0;
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int hi = a.hx_lo + (int)(row / HY), hj = (int)(row % HY);
-        // runs start on 128-byte lines of the arrays, not at z = 16 k of the row: the row's first entry sits `sft` doubles into
-        // a line (rows are nz + 2 doubles long), so the first run holds the 16 - sft cells up to the next line and every later
-        // one is exactly one line per beam and array (beams whose stride from beam 0 is an odd multiple of 8 doubles -- every
-        // second one at 256^3 -- stay half a line off: the arrays' beam stride is the caller's)
-        const int sft = (int)((((long)hi * HY + hj) * HZ - a.store0) & (LC - 1));
-        const int zb_row = (HZ + sft + LC - 1) / LC;
-        for (int ibz = 0; ibz < zb_row; ++ibz) {
-            const int hk = LC * ibz + c - sft;
+        const RowRuns runs = row_runs(a, a.hx_lo + (int)(row / HY), (int)(row % HY));
+        for (int ibz = 0; ibz < runs.count; ++ibz) {
+            const int hk = run_hk(ibz, c, runs.sft);
             const bool valid = hk >= 0 && hk < HZ;
-            const long h = ((long)hi * HY + hj) * HZ + (valid ? hk : 0);
+            const long h = runs.base + (valid ? hk : 0);
             const long hs = h - a.store0;
             double *fI = a.fields + hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
             // ---- which beams touched the run (E != 0 somewhere), which are present (E > 0 somewhere): every round's
@@ -433,8 +370,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             const int n = __popcll(mask), tiles = (n + LG - 1) / LG;
             // the plasma state of 64 cells at a time (lane = cell), handed to the four runs they make up
             if ((ibz & 3) == 0) {
-                const int hk64 = LC * ibz + lane - sft;
-                const CellState c64 = cell_state<FLOW, STATE>(a, ((long)hi * HY + hj) * HZ + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                const int hk64 = run_hk(ibz, lane, runs.sft);
+                const CellState c64 = cell_state<FLOW, STATE>(a, runs.base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
                 st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
                 st_pref = cell_pref(a, c64);
                 if (STATE) st_cs = c64.cs;
@@ -640,6 +577,7 @@ constexpr int XT = 256, XC = 16, XG = XT / XC, XROUNDS = CBET_MAX_CBET_BEAMS / X
 constexpr int XSTAGE = 528;                                                        // 16 x 33 >= 8 x 65
 constexpr int XPAIRS = CBET_MAX_CBET_BEAMS * (CBET_MAX_CBET_BEAMS - 1) / 2;        // 2016
 static_assert(XG * XROUNDS == 64 && XT / kWave == 4, "the mask shares below are written for four wavefronts of 4 x 16 lanes");
+static_assert(XC == LC, "RowRuns cuts both kernels' rows");
 
 // a double of lane `l` of the wavefront (l wave-uniform), whatever lanes are active
 __device__ __forceinline__ double readlane_f64(double v, int l)
@@ -670,14 +608,11 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
     __syncthreads();
     double st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_cs = 0.0, st_pi = 0.0, st_lim = 0.0, st_ds = 0.0;
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int hi = a.hx_lo + (int)(row / HY), hj = (int)(row % HY);
-        const long base = ((long)hi * HY + hj) * HZ;
-        const int sft = (int)((base - a.store0) & (XC - 1));   // k_gain_field_sym's: runs are cut by element index
-        const int zb_row = (HZ + sft + XC - 1) / XC;
-        for (int ibz = 0; ibz < zb_row; ++ibz) {
-            const int hk = XC * ibz + c - sft;
+        const RowRuns runs = row_runs(a, a.hx_lo + (int)(row / HY), (int)(row % HY));   // k_gain_field_sym's: cut by element index
+        for (int ibz = 0; ibz < runs.count; ++ibz) {
+            const int hk = run_hk(ibz, c, runs.sft);
             const bool valid = hk >= 0 && hk < HZ;
-            const long hs = base + (valid ? hk : 0) - a.store0;
+            const long hs = runs.base + (valid ? hk : 0) - a.store0;
             const double *fI = a.fields + hs, *fx = fI + total, *fy = fx + total, *fz = fy + total;
             double E[XROUNDS];
 #pragma unroll
@@ -697,8 +632,8 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
             if (lane == 0) sMask[wv] = share;
             // the plasma state of 64 cells at a time (thread = cell), for the four runs they make up
             if ((ibz & 3) == 0 && tid < 64) {
-                const int hk64 = XC * ibz + tid - sft;
-                const CellState c64 = cell_state<FLOW, STATE>(a, base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                const int hk64 = run_hk(ibz, tid, runs.sft);
+                const CellState c64 = cell_state<FLOW, STATE>(a, runs.base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
                 sSt[0][tid] = c64.ux; sSt[1][tid] = c64.uy; sSt[2][tid] = c64.uz; sSt[3][tid] = c64.cs;
                 sSt[4][tid] = cell_pref(a, c64) * iaw2;
                 sSt[5][tid] = SAT ? cell_sat_limit(a, c64) : 0.0;
@@ -911,22 +846,22 @@ hipError_t launch_edep_average(const double *edep, double *out, int nx, int ny, 
     return hipGetLastError();
 }
 
-// one dispatch of the run-time switches onto the template arguments: frozen, flow, state, sat
-template <bool... Bs>
-struct Sym {
-    static void launch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream) { hipLaunchKernelGGL((k_gain_field_sym<Bs...>), grid, block, 0, stream, a); }
-};
-template <bool... Bs>
-struct Ordered {
-    static void launch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream) { hipLaunchKernelGGL((k_gain_field<Bs...>), grid, block, 0, stream, a); }
-};
-template <template <bool...> class K, bool... Bs>
-void dispatch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream) { K<Bs...>::launch(a, grid, block, stream); }
-template <template <bool...> class K, bool... Bs, class... Rest>
-void dispatch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, bool first, Rest... rest)
+// One dispatch of run-time switches onto template arguments, for the four templated kernels: dispatch({s0, s1, ...}, launch)
+// calls launch(c0, c1, ...) with ck a std::true_type or std::false_type -- the launch names <decltype(ck)::value...>.
+template <int N, class Launch, class... Cs>
+void dispatch(const bool (&on)[N], Launch launch, Cs... cs)
 {
-    if (first) dispatch<K, Bs..., true>(a, grid, block, stream, rest...);
-    else dispatch<K, Bs..., false>(a, grid, block, stream, rest...);
+    if constexpr (sizeof...(Cs) == N) launch(cs...);
+    else if (on[sizeof...(Cs)]) dispatch(on, launch, cs..., std::true_type{});
+    else dispatch(on, launch, cs..., std::false_type{});
+}
+
+// k_gain_field's and k_pair_amplitude's grid: four wavefronts per workgroup, one brick per wavefront up to the cap
+static dim3 brick_grid(const GainArgs &a)
+{
+    long blocks = (brick_count(a) + 3) / 4;
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    return dim3((unsigned)blocks);
 }
 
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
@@ -934,42 +869,24 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
-        dispatch<Sym>(a, dim3((unsigned)rows), dim3(64), stream, a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0);
-        return hipGetLastError();
+        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0}, [&](auto... s) {
+            hipLaunchKernelGGL((k_gain_field_sym<decltype(s)::value...>), dim3((unsigned)rows), dim3(64), 0, stream, a);
+        });
+    } else {
+        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0}, [&](auto... s) {
+            hipLaunchKernelGGL((k_gain_field<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a);
+        });
     }
-    const long bricks = (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8);  // 2 x 4 x 8 cells of the haloed grid each
-    long blocks = (bricks + 3) / 4;                                                    // four wavefronts per workgroup
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    dispatch<Ordered>(a, dim3((unsigned)blocks), dim3(256), stream, a.flow != nullptr, a.state != nullptr, a.sat > 0.0);
     return hipGetLastError();
 }
 
 hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream)
 {
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
-    const long bricks = (long)(((a.hx_hi + 1) >> 1) - (a.hx_lo >> 1)) * ((a.ny + 5) / 4) * ((a.nz + 9) / 8);
-    long blocks = (bricks + 3) / 4;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    const dim3 grid((unsigned)blocks), block(256);
-    if (a.state) {
-        if (a.flow) hipLaunchKernelGGL((k_pair_amplitude<true, true>), grid, block, 0, stream, a, amp);
-        else hipLaunchKernelGGL((k_pair_amplitude<false, true>), grid, block, 0, stream, a, amp);
-    } else if (a.flow) hipLaunchKernelGGL((k_pair_amplitude<true, false>), grid, block, 0, stream, a, amp);
-    else hipLaunchKernelGGL((k_pair_amplitude<false, false>), grid, block, 0, stream, a, amp);
+    dispatch({a.flow != nullptr, a.state != nullptr}, [&](auto... s) {
+        hipLaunchKernelGGL((k_pair_amplitude<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a, amp);
+    });
     return hipGetLastError();
-}
-
-template <bool... Bs>
-struct Exchange {
-    static void launch(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, double *work) { hipLaunchKernelGGL((k_exchange_matrix<Bs...>), grid, block, 0, stream, a, work); }
-};
-template <bool... Bs>
-void dispatch_exchange(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, double *work) { Exchange<Bs...>::launch(a, grid, block, stream, work); }
-template <bool... Bs, class... Rest>
-void dispatch_exchange(const GainArgs &a, dim3 grid, dim3 block, hipStream_t stream, double *work, bool first, Rest... rest)
-{
-    if (first) dispatch_exchange<Bs..., true>(a, grid, block, stream, work, rest...);
-    else dispatch_exchange<Bs..., false>(a, grid, block, stream, work, rest...);
 }
 
 hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, double *gross, hipStream_t stream)
@@ -977,7 +894,9 @@ hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, 
     if (a.hx_hi <= a.hx_lo || a.nbeams < 2) return hipSuccess;
     // the number of workgroups follows from the slab alone, never from the device: the same partial sums everywhere
     const long groups = exchange_groups((long)(a.hx_hi - a.hx_lo) * (a.ny + 2));
-    dispatch_exchange<>(a, dim3((unsigned)groups), dim3(XT), stream, work, a.flow != nullptr, a.state != nullptr, a.sat > 0.0);
+    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0}, [&](auto... s) {
+        hipLaunchKernelGGL((k_exchange_matrix<decltype(s)::value...>), dim3((unsigned)groups), dim3(XT), 0, stream, a, work);
+    });
     if (hipError_t e = hipGetLastError()) return e;
     const int npairs = a.nbeams * (a.nbeams - 1) / 2, lanes = npairs > a.nbeams ? npairs : a.nbeams;
     hipLaunchKernelGGL(k_exchange_reduce, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, work, (int)groups, a.nbeams, out, gross);

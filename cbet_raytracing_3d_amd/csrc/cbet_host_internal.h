@@ -107,6 +107,13 @@ void grid_args(Args &a, const cbet_params *p, const cbet_derived &d)
     a.xmin = p->xmin; a.ymin = p->ymin; a.zmin = p->zmin;
     a.dx = d.dx; a.dy = d.dy; a.dz = d.dz;
 }
+// The Mach ramp of radial_flow (cbet_node_model.h) and the sound speed it scales: GainArgs' and FlowArgs'.
+template <class Args>
+void ramp_args(Args &a, const cbet_gain_params *g, double cs)
+{
+    a.cs = cs;
+    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
+}
 // The six exit planes {xlo, xhi, ylo, yhi, zlo, zhi} of launch_ray_XZ.cu:352-354, xmin - (dx / 2.0), xmax + (dx / 2.0), ...:
 // ONE statement for the array context_create uploads (cbet_context::bounds) and for TraceArgs::exit_planes.
 inline void host_exit_planes(const cbet_params *p, const cbet_derived &d, double out[6])
@@ -137,6 +144,13 @@ MeshArgs mesh_state_args(const cbet_params *p, const cbet_derived &d, const cbet
                          const cbet_mesh *mesh, const cbet_mesh_ions *ions, double *state);
 // The mesh's sizes and NULL pointers (all a device entry can check); whole: the values too (HOST arrays).
 int mesh_check(const cbet_mesh *mesh, bool whole);
+// The gain kernels', k_pair_amplitude's, k_exchange_matrix's and its host twin's (cbet_gain_abi.cpp).  cs, gc: cbet_gain_constants';
+// packed: the arrays hold the slab's planes only.  gain, scratch, change, consume and frozen stay zero: the gain update sets them.
+GainArgs gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
+                   const double *fields, const double *ne3d, const double *flow, const double *state, double sat, int hx_lo,
+                   int hx_hi, bool packed);
+// The slab [hx_lo, hx_hi) lies in the haloed grid; who: the entry point's name and ": " in front of the message, or "".
+int slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
 // The context's own table of `components` doubles per node in *slot, allocated on the first call (not capturable).
@@ -158,7 +172,7 @@ int trace_impl(int b, unsigned nindices, const double *ne3d, const double *kappa
                double zconst, const cbet_params *p, cbet_context *ctx, void *stream, const CbetHooks &hooks);
 int gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo, int hx_hi,
                     bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx, void *stream,
-                    bool consume = false, double *amplitude = nullptr);
+                    bool consume = false);
 
 #pragma GCC visibility pop
 }  // namespace cbet

@@ -2,7 +2,7 @@
 // twins: the clamped bisection bracket and the two-table interpolation of launch_ray_XZ.cu:16-63, the node's centre and
 // radius (:296), the absorbed fraction (:299-305) and the Mach ramp with its radial flow.  The plain
 // tabulation (cbet_kernels.hip), perturbed targets (cbet_target_model.h), the hydro mesh (cbet_mesh_model.h) and the gain
-// kernels' cell state (cbet_grid_kernels.hip) are written over them.
+// stage's cell state (cbet_gain_model.h, for the gain kernels and the exchange matrix's host twin) are written over them.
 // Built with -ffp-contract=off on both sides: every operator below is one IEEE fp64 operation, in the order written, so a
 // kernel and its twin agree bit for bit.  The includer provides sqrt(double): <hip/hip_runtime.h> in device code, <cmath>
 // on the host.

@@ -67,8 +67,7 @@ FlowArgs flow_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_
 {
     FlowArgs a{};
     grid_args(a, p, d);
-    a.cs = cs;
-    a.mach_r0 = g->mach_r0; a.mach_0 = g->mach_0; a.mach_r1 = g->mach_r1; a.mach_1 = g->mach_1;
+    ramp_args(a, g, cs);
     a.flow = out;
     if (target) fill_target(target, &a);
     return a;
