@@ -58,6 +58,17 @@ namespace {
 #define CBET_BALLOT(cond) __builtin_amdgcn_ballot_w64(cond)
 // a per-lane predicate FROM a wave-uniform 64-bit mask (no instruction: the mask is used as the condition register)
 #define CBET_LANES(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
+// Which side of a wave-uniform branch of the step loop the calm step takes: the compiler lays that side out as the
+// fall-through and moves the other out of line (scripts/isa_layout.py counts the calm step's taken branches).
+#define CBET_USUAL(cond) __builtin_expect(!!(cond), 1)
+#define CBET_RARE(cond) __builtin_expect(!!(cond), 0)
+// ... and a side that is seldom taken, but not never: 0.17 rays end per wave-step at 256^3, several of a bundle in the same
+// step, and the probability given (0.9 against) is enough to lay the arm out behind the loop.  (Marked CBET_RARE the
+// arm is classed cold, and with it cold the compiler selects the loop header's phis -- every loop-carried mask, origin and
+// flag -- as vector registers, which the moves tied to scalar registers (commit) then refuse: "illegal VGPR to SGPR copy".
+// Which value starts it was not found; 0.9 is chosen to stay BELOW this compiler's cold classification and must not be raised:
+// it leans on a threshold inside the compiler, and a toolchain that moves the threshold fails at compile time, not at run time.)
+#define CBET_SELDOM(cond) __builtin_expect_with_probability(!!(cond), 0, 0.9)
 
 // A wave-private tile of fp64 accumulators covering WX x WY x WZ nodes (powers of two), addressed toroidally.
 template <int WX_, int WY_, int WZ_, bool PAD, bool XORSW = false>
@@ -190,7 +201,7 @@ __device__ __forceinline__ void write_back_far(const TraceArgs &a, double *tile,
 template <class F>
 __device__ __forceinline__ void miss_add8(unsigned long long hbm_m, WaveCounters &wc, F add8)
 {
-    if (hbm_m != 0ull) {
+    if (CBET_RARE(hbm_m != 0ull)) {
         wc.pend += 8;
         if (CBET_LANES(hbm_m)) add8();
     }
@@ -354,7 +365,7 @@ __device__ __forceinline__ int follow_plane_axis(int r, unsigned long long mm, i
     // a decision tree -- four ballots on the usual path (a member on one edge, nobody near the other) instead of the
     // eight thresholds.
     const unsigned long long edge = __builtin_amdgcn_ballot_w64((unsigned)(r - 1) >= (unsigned)(S - 1)) & mm;   // r <= 0 or r >= S
-    if (edge == 0ull) return 0;
+    if (CBET_USUAL(edge == 0ull)) return 0;
     const unsigned long long hi = __builtin_amdgcn_ballot_w64(r >= S) & edge;     // at_hi (a member above the box included)
     const bool at_hi = hi != 0ull, at_lo = hi != edge;                            // (the edge lanes that are not high are low)
     if (at_hi == at_lo) return 0;                                                 // members on both edges: stay
@@ -748,7 +759,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             // offset, and box A's swizzle is an exclusive-or of an x and a y term into the z field -- a node's offset is the
             // exclusive-or of a per-x, a per-y and a per-z term: one v_bitop3_b32 (truth table 0x96) per node.
             int ax0, ax1, by0, by1, cz0, cz1;
-            if (b_active == 0) {   // scalar branch: everything goes to box A, compile-time masks and strides
+            if (CBET_USUAL(b_active == 0)) {   // scalar branch: everything goes to box A, compile-time masks and strides
                 ax0 = T::xterm(X0 & T::XM); ax1 = T::xterm(X1 & T::XM);
                 by0 = T::yterm(Y0 & T::YM); by1 = T::yterm(Y1 & T::YM);
                 cz0 = (Z0 & T::ZM) << 3; cz1 = (Z1 & T::ZM) << 3;
@@ -907,7 +918,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // loads the compiler waits for with vmcnt(0), i.e. together with every write-back atomic in flight).
     unsigned long long died = CBET_BALLOT(s.uray <= s.ustop);
     const int faces = slow | near;   // (a far jump keeps the cell: all six planes)
-    if (faces != 0) {   // scalar branch
+    if (CBET_RARE(faces != 0)) {   // scalar branch
         dbl2 bx, by, bz;   // {xlo, xhi}, {ylo, yhi}, {zlo, zhi}
         exit_planes_load(bx, by, bz);
         if (faces & 1) died |= CBET_BALLOT(s.px < bx.x) | CBET_BALLOT(s.px > bx.y);
@@ -915,7 +926,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         if (faces & 4) died |= CBET_BALLOT(s.pz < bz.x) | CBET_BALLOT(s.pz > bz.y);
     }
     died &= live;
-    if (died != 0ull) {   // scalar branch: some ray ended in this step, its tt + 1-th
+    if (CBET_SELDOM(died != 0ull)) {   // scalar branch: some ray ended in this step, its tt + 1-th
         asm volatile("");
         commit(tot_steps, tot_steps + __popcll(died) * (tt + 1));
         // its deposit goes where the window pass of this step put it, now (the boxes stand for exactly these nodes)
@@ -969,7 +980,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // exact there -- along the others.  (Two arms, each updating from the old cell, and the in-place form pinned to its
         // two carry instructions per axis (cell_step): with one shared update that the rare arm takes back, or with the arms'
         // common tails merged by the compiler, the old cell or the increment costs the common path a copy per axis.)
-        if (slow == 0) {
+        if (CBET_USUAL(slow == 0)) {
             cell_step3(s.ci, s.cj, s.ck, upx, dnx, upy, dny, upz, dnz);
         } else {
             if (slow & 1) s.ci = relocate_closed(s.ci, fx, nx);
@@ -1017,8 +1028,8 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // low corner is a function of the cell while the offsets are negative), every lane around the rare branch
         if constexpr (ACC) {
             const unsigned long long fl_m = (all_negative && !p_odd) ? (live & moved_m) : live;
-            if (fl_m != 0ull) {   // scalar branch (taken in 99 % of the wave-steps: some lane always moves on)
-                if (miss_m == 0ull) flush_sums(fl_m, 0ull);      // (the usual case without the mask arithmetic)
+            if (CBET_USUAL(fl_m != 0ull)) {   // scalar branch (taken in 99 % of the wave-steps: some lane always moves on)
+                if (CBET_USUAL(miss_m == 0ull)) flush_sums(fl_m, 0ull);      // (the usual case without the mask arithmetic)
                 else flush_sums(fl_m & ~miss_m, fl_m & miss_m);
             }
             restart_m = fl_m;
@@ -1030,7 +1041,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // the lane's low corner (haloed) relative to box A's origin: what the common case tests; the corner itself is
         // rebuilt from it where a box has to move (as a value of its own it costs three copies per step)
         int rx, ry, rz;
-        if (all_negative) {   // scalar branch
+        if (CBET_USUAL(all_negative)) {   // scalar branch
             rx = s.ci - oA.x;
             ry = s.cj - oA.y;
             rz = s.ck - oA.z;
@@ -1085,7 +1096,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         const unsigned long long memA = live & ~hbm;
         unsigned long long out_core = memA & ~(CBET_BALLOT((unsigned)rx <= (unsigned)T::SX) & CBET_BALLOT((unsigned)ry <= (unsigned)T::SY) &
                                                CBET_BALLOT((unsigned)rz <= (unsigned)T::SZ));
-        if (b_active != 0) {   // scalar branch
+        if (CBET_RARE(b_active != 0)) {   // scalar branch
             asm volatile("");   // (a real branch: if-converted, its assignments cost the common path two selects)
             if constexpr (STATS) wc.slabs_bsteps += 1u;
             const int abx = oA.x - oB.x, aby = oA.y - oB.y, abz = oA.z - oB.z;
@@ -1097,7 +1108,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         // (lanes the last window pass left outside both boxes send the wave through the general arm again, which clears or
         // renews their mark: 1 % of the wave-steps)
         out_core |= miss_m;
-        if (out_core != 0ull) {
+        if (CBET_RARE(out_core != 0ull)) {
             wc.dg.arm_begin();
             // The wave-uniform state this arm changes -- box origins, masks, flags -- is worked on in COPIES and written back
             // at the end through commit(): an assembly move TIED to the variable's register, so that the value the arm leaves
@@ -1114,7 +1125,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             const unsigned long long lost_mask =
                 memA & ~(CBET_BALLOT((unsigned)(lx - nA.x) <= (unsigned)T::SX) & CBET_BALLOT((unsigned)(ly - nA.y) <= (unsigned)T::SY) &
                          CBET_BALLOT((unsigned)(lz - nA.z) <= (unsigned)T::SZ));
-            if (lost_mask == 0ull && n_bact == 0) {
+            if (CBET_USUAL(lost_mask == 0ull && n_bact == 0)) {
                 // the usual outcome: A moved and holds every live lane again (tile_off = 0 stands, nobody outside)
                 n_near = box_near_axes<T>(nA, nx, ny, nz);
             } else {
@@ -1164,7 +1175,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
             // (the write-back paths keep the count in a vector register; the common path's stays scalar this way)
             wc.pend = __builtin_amdgcn_readfirstlane(wc.pend);
             wc.dg.arm_end();
-        } else if (near != 0) {
+        } else if (CBET_RARE(near != 0)) {
             commit(near, box_near_axes<T>(oA, nx, ny, nz) | (b_active == 0 ? 0 : box_near_axes<TB>(oB, nx, ny, nz)));
         }
         step_tail(tt);
