@@ -365,13 +365,16 @@ EXPORTS = [
     "cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit",
     "cbet_context_set_saturation", "cbet_context_saturation", "cbet_pair_amplitude",
     "cbet_exchange_matrix_work_bytes", "cbet_exchange_matrix", "cbet_exchange_matrix_host",
+    "cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted",
 ]
 
 _lib = None
 
 
-def lib():
-    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built."""
+def lib(tolerate=()):
+    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning entries that an
+    OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack; such a build must then
+    not be asked for shifts."""
     global _lib
     if _lib is not None:
         return _lib
@@ -479,8 +482,15 @@ def lib():
     L.cbet_exchange_matrix.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
     L.cbet_exchange_matrix_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp,
                                             C.c_double]
+    detuning = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
+                "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp]}
+    absent = [name for name in detuning if name in tolerate and not hasattr(L, name)]
+    for name, types in detuning.items():
+        if name not in absent:
+            getattr(L, name).argtypes = types
     for name in EXPORTS:
-        getattr(L, name)  # AttributeError here = the library is older than the header
+        if name not in absent:
+            getattr(L, name)  # AttributeError here = the library is older than the header
     _lib = L
     return L
 
@@ -616,6 +626,7 @@ class Context:
         self.gpu = gpu
         self._flow_ref = None           # set_flow(): the caller's table, kept alive
         self._state_ref = None          # set_state(): likewise
+        self.detuning_source = None     # set_detuning(): the array last given (its own copy), None for none
         _check(lib().cbet_context_create(C.byref(self._h), C.byref(params), gpu))
 
     @property
@@ -685,6 +696,25 @@ class Context:
         v = C.c_double()
         _check(lib().cbet_context_saturation(self._h, C.byref(v)))
         return v.value
+
+    def set_detuning(self, domega, stream=None):
+        """cbet_context_set_detuning: the gain updates of this context give beam b the angular-frequency shift domega[b]
+        (rad/s, one per beam of the context's parameters); None, or shifts that are all equal, = none, the default.  A set-up
+        call: it synchronises `stream` and copies synchronously.  A NaN or infinite shift or a wrong count raises.
+        A RayTracer's own context is where the tracer's shifts live: RayTracer.set_detuning calls this, RayTracer.detuning reads
+        the context back, and the contexts the tracer prepares later are given what this context was last given."""
+        if domega is None:
+            _check(lib().cbet_context_set_detuning(self._h, None, 0, _addr(stream)))
+        else:
+            arr = np.array(domega, dtype=np.float64).reshape(-1)
+            _check(lib().cbet_context_set_detuning(self._h, arr.ctypes.data, arr.size, _addr(stream)))
+        self.detuning_source = None if domega is None else arr
+
+    def detuning(self):
+        """The shifts in use (cbet_context_detuning): a numpy array of one double per beam, or None if none."""
+        out, n = np.zeros(MAX_CBET_BEAMS), C.c_int()
+        _check(lib().cbet_context_detuning(self._h, _dptr(out), C.byref(n)))
+        return out[:n.value].copy() if n.value else None
 
     def close(self):
         if self._h:
@@ -895,20 +925,31 @@ def exchange_matrix(fields, ne3d, out, gross, work, hx_lo, hx_hi, params, gain_p
                                       C.byref(params), C.byref(gain_params), ctx.handle if ctx is not None else None, _addr(stream)))
 
 
+def wavelength_shift_to_domega(params, dlambda_angstrom):
+    """Wavelength shifts (Angstrom, scalar or array; > 0 = red) of the nominal wavelength l0 = 2 pi c / omega of `params` as
+    angular-frequency shifts in rad/s: omega l0 / (l0 + dl) - omega, not its first-order form."""
+    omega = derive(params).omega
+    lam0 = 2.0 * np.pi * 29979245800.0 / omega          # cm; the library's c (cbet_device.h kC)
+    dl = np.asarray(dlambda_angstrom, dtype=np.float64) * 1e-8
+    return omega * lam0 / (lam0 + dl) - omega
+
+
 def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=None, dn_max=0.0, hx_lo=0, hx_hi=None, out=None,
-                         gross=None):
+                         gross=None, shift=None):
     """cbet_exchange_matrix_host, the host twin: numpy (T, Gross), each (nbeams, nbeams), of normalised HOST fields
     [4, nbeams, nx + 2, ny + 2, nz + 2] over the planes [hx_lo, hx_hi).  ne3d (nx, ny, nz); flow (3, nx, ny, nz) or None = the
-    closed-form ramp; state (2, nx, ny, nz) or None = the scalars; dn_max 0 = no limit.  out / gross: arrays to ADD into
-    (default: new zeroed ones)."""
+    closed-form ramp; state (2, nx, ny, nz) or None = the scalars; dn_max 0 = no limit; shift (nbeams,) per-beam frequency
+    shifts in rad/s or None (cbet_exchange_matrix_host_shifted).  out / gross: arrays to ADD into (default: new zeroed ones)."""
     nb = params.nbeams
     host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
-    fields, ne3d, flow, state = host(fields), host(ne3d), host(flow), host(state)
+    fields, ne3d, flow, state, shift = host(fields), host(ne3d), host(flow), host(state), host(shift)
+    if shift is not None and shift.shape != (nb,):
+        raise ValueError("shift holds one value per beam: shape (%d,), got %r" % (nb, shift.shape))
     out = np.zeros((nb, nb)) if out is None else out
     gross = np.zeros((nb, nb)) if gross is None else gross
-    _check(lib().cbet_exchange_matrix_host(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
-                                           params.nx + 2 if hx_hi is None else hx_hi, C.byref(params), C.byref(gain_params),
-                                           _addr(flow), _addr(state), dn_max))
+    _check(lib().cbet_exchange_matrix_host_shifted(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
+                                                   params.nx + 2 if hx_hi is None else hx_hi, C.byref(params), C.byref(gain_params),
+                                                   _addr(flow), _addr(state), dn_max, _addr(shift)))
     return out, gross
 
 

@@ -113,6 +113,7 @@ int cbet_context_destroy(cbet_context *ctx)
     (void)hipFree(ctx->counters);
     (void)hipFree(ctx->flow_own);
     (void)hipFree(ctx->state_own);
+    (void)hipFree(ctx->shift_own);
     delete ctx;
     return CBET_OK;
 }
@@ -295,6 +296,53 @@ int cbet_context_saturation(cbet_context *ctx, double *out)
 {
     if (!ctx || !out) return fail(CBET_EINVAL, "NULL context/out");
     *out = ctx->dn_max;
+    return CBET_OK;
+}
+
+// The values are judged before the context, as cbet_context_set_saturation judges its own: a refusal needs no device.
+int cbet_context_set_detuning(cbet_context *ctx, const double *domega, int nbeams, void *stream)
+{
+    if (domega) {
+        if (nbeams > CBET_MAX_CBET_BEAMS)
+            return fail(CBET_EINVAL, "cbet_context_set_detuning: nbeams = %d exceeds CBET_MAX_CBET_BEAMS = %d", nbeams, CBET_MAX_CBET_BEAMS);
+        if (nbeams < 1) return fail(CBET_EINVAL, "cbet_context_set_detuning: nbeams = %d (one shift per beam)", nbeams);
+        for (int b = 0; b < nbeams; ++b) {
+            if (std::isnan(domega[b])) return fail(CBET_EINVAL, "cbet_context_set_detuning: domega[%d] is NaN (finite shifts in rad/s, or NULL = none)", b);
+            if (std::isinf(domega[b])) return fail(CBET_EINVAL, "cbet_context_set_detuning: domega[%d] is infinite (finite shifts in rad/s, or NULL = none)", b);
+        }
+    }
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (domega && nbeams != ctx->p.nbeams)
+        return fail(CBET_EINVAL, "cbet_context_set_detuning: nbeams = %d, the context was created for %d beams", nbeams, ctx->p.nbeams);
+    bool one_colour = true;
+    for (int b = 1; domega && b < nbeams; ++b) one_colour = one_colour && domega[b] == domega[0];
+    if (one_colour) {                       // only differences enter the model: nothing to carry
+        ctx->shift = nullptr;
+        return CBET_OK;
+    }
+    CBET_ENTER_DEVICE(ctx);
+    if (!ctx->shift_own) {
+        hipError_t e = hipMalloc((void **)&ctx->shift_own, sizeof ctx->shift_host);
+        if (e != hipSuccess) {
+            ctx->shift_own = nullptr;
+            return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(detuning table): %s", hipGetErrorString(e));
+        }
+    }
+    double fresh[CBET_MAX_CBET_BEAMS] = {};   // an entry per possible beam: zero past nbeams
+    for (int b = 0; b < nbeams; ++b) fresh[b] = domega[b];
+    CBET_HIP(hipStreamSynchronize((hipStream_t)stream));   // a launch in flight may still read the old values
+    CBET_HIP(hipMemcpy(ctx->shift_own, fresh, sizeof fresh, hipMemcpyHostToDevice));
+    std::memcpy(ctx->shift_host, fresh, sizeof fresh);
+    ctx->shift = ctx->shift_own;
+    return CBET_OK;
+}
+
+int cbet_context_detuning(cbet_context *ctx, double *out, int *nbeams)
+{
+    if (!ctx || !nbeams) return fail(CBET_EINVAL, "NULL context/nbeams");
+    *nbeams = ctx->shift ? ctx->p.nbeams : 0;
+    if (out)
+        for (int b = 0; b < *nbeams; ++b) out[b] = ctx->shift_host[b];
     return CBET_OK;
 }
 

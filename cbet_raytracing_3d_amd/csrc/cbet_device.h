@@ -128,6 +128,7 @@ struct GainArgs {
     const double *flow;                     // [3][nx*ny*nz] node flow table (ux, uy, uz; cbet_tabulate_flow), or NULL: the closed-form ramp about the origin
     const double *state;                    // [2][nx*ny*nz] node state table (cs, gain_const; cbet_tabulate_mesh_state), or NULL: the scalars cs / gain_const above
     double sat;                             // limit dn_max of the ion-acoustic amplitude a pair's gain corresponds to (cbet_context_set_saturation), 0 = none
+    const double *shift;                    // [CBET_MAX_CBET_BEAMS] per-beam angular-frequency shifts, rad/s (cbet_context_set_detuning; entries past nbeams are 0), or NULL: one colour
 };
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);

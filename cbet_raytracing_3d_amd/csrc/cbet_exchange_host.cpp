@@ -3,7 +3,8 @@
 // are cbet_gain_model.h's for k_gain_field and for this file alike (cell_state, cell_pref, cell_sat_limit, pair_gain,
 // pair_clamp), on an argument block filled by the kernels' own builder (gain_args) -- one IEEE operation per written
 // operator, the library is built with -ffp-contract=off -- with every pair's two sums compensated (Neumaier).
-// No HIP call: it is the reference of the device path at any size.
+// No HIP call: it is the reference of the device path at any size.  cbet_exchange_matrix_host_shifted is the twin with per-beam
+// frequency shifts; the argument builder the kernels and the twin share (gain_args) lives here too.
 #include <cmath>
 #include <vector>
 
@@ -25,9 +26,45 @@ inline void add_compensated(double &sum, double &comp, double x)
 }  // namespace
 }  // namespace cbet
 
+// The argument block of the gain kernels, of k_pair_amplitude, of k_exchange_matrix and of the twin below (cbet_host_internal.h):
+// here, beside the twin, so that the twin links without the HIP runtime.
+cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
+                               const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
+                               const double *shift, int hx_lo, int hx_hi, bool packed)
+{
+    GainArgs a{};
+    grid_args(a, p, d);
+    a.nbeams = p->nbeams; a.dt = d.dt;
+    a.ncrit = d.ncrit; a.k0 = d.omega / kC;
+    ramp_args(a, g, cs);
+    a.gain_const = gc; a.iaw = g->iaw; a.relax = g->relax;
+    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat; a.shift = shift;
+    a.hx_lo = hx_lo; a.hx_hi = hx_hi;
+    const long plane = (long)(p->ny + 2) * (p->nz + 2);
+    a.store0 = packed ? (long)hx_lo * plane : 0;
+    a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
+    return a;
+}
+
+int cbet::slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p)
+{
+    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
+        return fail(CBET_EINVAL, "%sslab [%d,%d) outside the haloed grid [0,%d)", who, hx_lo, hx_hi, p->nx + 2);
+    return CBET_OK;
+}
+
 extern "C" int cbet_exchange_matrix_host(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo,
                                          int hx_hi, const cbet_params *p, const cbet_gain_params *g, const double *flow,
                                          const double *state, double dn_max)
+{
+    return cbet_exchange_matrix_host_shifted(fields, ne3d, out, gross, hx_lo, hx_hi, p, g, flow, state, dn_max, nullptr);
+}
+
+// ... with per-beam frequency shifts: shift[nbeams] rad/s, or NULL.  The ordered statement with the
+// beat frequency (pair_gain's second form) wherever shift is given -- equal shifts add an exact zero to every pair.
+extern "C" int cbet_exchange_matrix_host_shifted(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo,
+                                                 int hx_hi, const cbet_params *p, const cbet_gain_params *g, const double *flow,
+                                                 const double *state, double dn_max, const double *shift)
 {
     using namespace cbet;
     cbet_derived d;
@@ -43,8 +80,13 @@ extern "C" int cbet_exchange_matrix_host(const double *fields, const double *ne3
     if (!(dn_max >= 0.0) || std::isinf(dn_max))
         return fail(CBET_EINVAL, "cbet_exchange_matrix_host: dn_max must be finite and >= 0 (0 = no limit)");
     const int nb = p->nbeams;
+    double table[CBET_MAX_CBET_BEAMS] = {};   // the kernels' table: an entry per possible beam, zero past nbeams
+    for (int b = 0; shift && b < nb; ++b) {
+        if (!std::isfinite(shift[b])) return fail(CBET_EINVAL, "cbet_exchange_matrix_host_shifted: shift[%d] is not finite", b);
+        table[b] = shift[b];
+    }
     if (nb < 2 || hx_hi == hx_lo) return CBET_OK;
-    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, hx_lo, hx_hi, false);
+    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, shift ? table : nullptr, hx_lo, hx_hi, false);
     const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride, total = hsize * nb;
     const double iaw2 = a.iaw * a.iaw;
@@ -71,7 +113,7 @@ extern "C" int cbet_exchange_matrix_host(const double *fields, const double *ne3
                 const BeamAtCell Bj = beam_at(fI, fx, fy, fz, (long)bj * hsize);
                 const PairWave w = pair_wave(Bi, Bj);
                 if (!pair_present(Bi, Bj, w)) continue;
-                double gn = pair_gain(c, pref, iaw2, w);
+                double gn = a.shift ? pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]) : pair_gain(c, pref, iaw2, w);
                 if (sat) gn = pair_clamp(gn, Bi.I, Bj.I, lim);
                 const double x = ((ds_node * gn) * Bi.I) * Bj.I;
                 const size_t at = (size_t)bi * nb + bj;

@@ -7,31 +7,6 @@
 
 using namespace cbet;
 
-GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
-                         const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                         int hx_lo, int hx_hi, bool packed)
-{
-    GainArgs a{};
-    grid_args(a, p, d);
-    a.nbeams = p->nbeams; a.dt = d.dt;
-    a.ncrit = d.ncrit; a.k0 = d.omega / kC;
-    ramp_args(a, g, cs);
-    a.gain_const = gc; a.iaw = g->iaw; a.relax = g->relax;
-    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat;
-    a.hx_lo = hx_lo; a.hx_hi = hx_hi;
-    const long plane = (long)(p->ny + 2) * (p->nz + 2);
-    a.store0 = packed ? (long)hx_lo * plane : 0;
-    a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
-    return a;
-}
-
-int cbet::slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p)
-{
-    if (hx_lo < 0 || hx_hi > p->nx + 2 || hx_hi < hx_lo)
-        return fail(CBET_EINVAL, "%sslab [%d,%d) outside the haloed grid [0,%d)", who, hx_lo, hx_hi, p->nx + 2);
-    return CBET_OK;
-}
-
 int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo,
                           int hx_hi, bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx,
                           void *stream, bool consume)
@@ -43,8 +18,8 @@ int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, doub
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (hx_hi == hx_lo) return CBET_OK;   // an empty slab (more ranks than planes)
-    GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, hx_lo,
-                           hx_hi, packed);
+    GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, ctx->shift,
+                           hx_lo, hx_hi, packed);
     a.gain = gain; a.scratch = scratch; a.change = change;
     a.consume = (consume && scratch) ? 1 : 0;
     a.frozen = g->directions_frozen ? 1 : 0;
@@ -104,8 +79,8 @@ int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, i
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (hx_hi == hx_lo) return CBET_OK;
-    // sat = 0: the map is the unclamped amplitude
-    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, 0.0, hx_lo, hx_hi, false);
+    // sat = 0: the map is the unclamped amplitude (of the detuned gain, if the context has shifts)
+    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, 0.0, ctx->shift, hx_lo, hx_hi, false);
     CBET_ENTER_DEVICE(ctx);
     CBET_HIP(launch_pair_amplitude(a, amp, (hipStream_t)stream));
     return CBET_OK;
@@ -135,8 +110,8 @@ int cbet_exchange_matrix(const double *fields, const double *ne3d, double *out, 
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (p->nbeams < 2 || hx_hi == hx_lo) return CBET_OK;   // one beam exchanges with nobody; an empty slab adds nothing
-    // sat = the context's: the matrix decomposes the K the solve uses, the limit is honoured
-    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, hx_lo, hx_hi, false);
+    // sat and shift = the context's: the matrix decomposes the K the solve uses, the limit and the detuning are honoured
+    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, ctx->shift, hx_lo, hx_hi, false);
     CBET_ENTER_DEVICE(ctx);
     CBET_HIP(launch_exchange_matrix(a, (double *)work, out, gross, (hipStream_t)stream));
     return CBET_OK;

@@ -102,6 +102,25 @@ CBET_HD double pair_gain(const CellState &c, double pref, double iaw2, const Pai
     const double P = iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
     return pref * P;
 }
+// Wavelength detuning.  Beam b's angular frequency is omega + w_b (rad/s), omega the nominal one of
+// cbet_derive; the ion-acoustic wave of the ordered pair (i, j) is driven at the beat frequency, so the Doppler term of the
+// resonance gains dw = w_j - w_i:  eta_ij = ((0.0 - q . u) + (w_j - w_i)) / (|q| cs + 1e-10).  Beam i gains where its
+// frequency in the plasma frame is the lower one: in still plasma the red-shifted beam gains.  (w_i - w_j) = -(w_j - w_i)
+// exactly, so G_ji = -G_ij stays exact and a cell's exchange sum_i I_i K_i still cancels; dw = 0 adds an exact zero.  Only
+// the beat frequency enters: each beam's own k0, ncrit and refraction keep the nominal wavelength (relative change ~1e-3),
+// and the Manley-Rowe photon-number correction of the same order is left out.  pair_present is unchanged: two exactly
+// parallel beams exchange nothing, detuned or not.
+// pair_resonance: P(eta), the statements pair_gain above runs after its eta, for the detuned form.
+CBET_HD double pair_resonance(double eta, double iaw2)
+{
+    const double e2 = eta * eta;
+    return iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + iaw2 * e2);
+}
+CBET_HD double pair_gain(const CellState &c, double pref, double iaw2, const PairWave &w, double dw)
+{
+    const double eta = ((0.0 - (w.qx * c.ux + w.qy * c.uy + w.qz * c.uz)) + dw) / (w.kiaw * c.cs + 1e-10);
+    return pref * pair_resonance(eta, iaw2);
+}
 // The clamp: g scaled by min(1, lim / w), w = |g| sqrt(Ii Ij) (pair_swing) -- one factor for (i, j) and (j, i); a
 // pair below the limit keeps its bits.
 CBET_HD double pair_swing(double g, double Ii, double Ij) { return fabs(g) * sqrt(Ii * Ij); }

@@ -10,6 +10,7 @@
 // -- is cbet_gain_model.h's, written once for these kernels and the exchange matrix's host twin (cbet_exchange_host.cpp).  Shared
 // inside this file: brick_cell (k_gain_field, k_pair_amplitude), row_runs (k_gain_field_sym, k_exchange_matrix), pair_gain_fast
 // and saturate_fast (the two pair-once kernels), one dispatch of run-time switches onto template arguments (all four).
+// DETUNE, the last switch of all four (GainArgs.shift != NULL): per-beam frequency shifts, DESIGN.md section 19.
 // Built with -ffp-contract=off like the rest of the library: every statement of the ordered kernel and of the
 // normalisation is one IEEE operation in the order written, which is the order the CPU checker of the CBET stage
 // uses; the pair-once kernel's pair function (pair_gain_fast) is the exception and says so.
@@ -90,7 +91,9 @@ __device__ __forceinline__ BrickCell brick_cell(const GainArgs &a, long brick, i
 //   phase 2: K_i = sum_{j != i} G_ij I_j, beams in increasing order; gain <- gain + relax (K - gain), stored only where it changes.
 // SAT (GainArgs.sat > 0): every pair gain goes through pair_clamp -- one factor for (i, j) and (j, i), so the cell's
 // exchange still cancels; a pair below the limit keeps its bits ((pref * P) * Ij either way).
-template <bool FLOW, bool STATE, bool SAT>
+// DETUNE (GainArgs.shift != NULL): the pair's resonance gains the beat frequency shift[bj] - shift[bi]
+// (pair_gain's second form) -- both beams are wave-uniform, the two entries come by scalar loads.
+template <bool FLOW, bool STATE, bool SAT, bool DETUNE>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
     const long hsize = a.bstride;                 // entries stored per beam (the whole haloed grid, or one x-slab of it)
@@ -131,7 +134,9 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
                     const BeamAtCell Bj = beam_at(fI, fx, fy, fz, (long)bj * hsize);
                     const PairWave w = pair_wave(Bi, Bj);
                     if (valid && pair_present(Bi, Bj, w)) {
-                        double g = pair_gain(c, pref, iaw2, w);
+                        double g;
+                        if constexpr (DETUNE) g = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
+                        else g = pair_gain(c, pref, iaw2, w);
                         if (SAT) g = pair_clamp(g, Bi.I, Bj.I, lim);
                         acc += g * Bj.I;
                     }
@@ -155,7 +160,8 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 // of the ion-acoustic amplitude the pair's unclamped gain corresponds to, A_ij = |G_ij| sqrt(Ii Ij) / kap -- the ordered
 // kernel's statements, its bricks and its presence mask; one store per valid cell, 0 where no pair exchanges anything or the
 // plasma is not sub-critical.  w / kap grows with w, so the largest w is divided once.  Reads a.fields only; a.sat is not read.
-template <bool FLOW, bool STATE>
+// DETUNE: the amplitude is that of the detuned |G_ij|.
+template <bool FLOW, bool STATE, bool DETUNE>
 __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double *__restrict__ amp)
 {
     const long hsize = a.bstride;
@@ -190,7 +196,10 @@ __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double
                 const BeamAtCell Bj = beam_at(fI, fx, fy, fz, (long)bj * hsize);
                 const PairWave w = pair_wave(Bi, Bj);
                 if (valid && pair_present(Bi, Bj, w)) {
-                    const double sw = pair_swing(pair_gain(c, pref, iaw2, w), Bi.I, Bj.I);
+                    double gn;
+                    if constexpr (DETUNE) gn = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
+                    else gn = pair_gain(c, pref, iaw2, w);
+                    const double sw = pair_swing(gn, Bi.I, Bj.I);
                     if (sw > top) top = sw;
                 }
             }
@@ -259,18 +268,26 @@ __device__ __forceinline__ int run_hk(int run, int c, int sft) { return LC * run
 // square root and reciprocal by the hardware estimates and Newton steps (a few ulp; the sums of the symmetric kernels are
 // grouped differently from the ordered kernel's anyway).  q = 0 (a beam against itself, or two parallel beams) gives
 // N = 0 over D^4 = 1e-40: zero, as in the ordered kernel.
+// DETUNE: N = -(q . u) + dw with dw = w_j - w_i, the pair's beat frequency.  Two parallel beams of
+// different colour would give N = dw over D = 1e-10; the ordered kernel does not evaluate them (pair_present), so here dw
+// counts only where q != 0: one compare and one select, and q = 0 keeps N = 0 and the exact zero.
+template <bool DETUNE = false>
 __device__ __forceinline__ double pair_gain_fast(const BeamAtCell &bi, const BeamAtCell &bj, double ux, double uy, double uz,
-                                                 double cs, double iaw2, double pref_iaw2)
+                                                 double cs, double iaw2, double pref_iaw2, double dw = 0.0)
 {
     const double qx = bj.kx - bi.kx, qy = bj.ky - bi.ky, qz = bj.kz - bi.kz;
-    const double q2 = fmax(__builtin_fma(qz, qz, __builtin_fma(qy, qy, qx * qx)), 1e-280);
+    const double q2raw = __builtin_fma(qz, qz, __builtin_fma(qy, qy, qx * qx));
+    const double q2 = fmax(q2raw, 1e-280);
+    double N;
+    // DETUNE forms the numerator first: dw is dead before the square-root chain starts (k_gain_field_sym's registers are spent)
+    if constexpr (DETUNE) N = (q2raw > 0.0 ? dw : 0.0) - __builtin_fma(qz, uz, __builtin_fma(qy, uy, qx * ux));
     // |q| = sqrt(q2): one Goldschmidt step from the reciprocal-square-root estimate, one correction
     const double r0 = __builtin_amdgcn_rsq(q2);
     double gq = q2 * r0, hq = 0.5 * r0;
     const double e = __builtin_fma(-hq, gq, 0.5);
     gq = __builtin_fma(gq, e, gq); hq = __builtin_fma(hq, e, hq);
     gq = __builtin_fma(__builtin_fma(-gq, gq, q2), hq, gq);
-    const double N = -__builtin_fma(qz, uz, __builtin_fma(qy, uy, qx * ux));
+    if constexpr (!DETUNE) N = -__builtin_fma(qz, uz, __builtin_fma(qy, uy, qx * ux));
     const double D = __builtin_fma(gq, cs, 1e-10);
     const double N2 = N * N, D2 = D * D, t = N2 - D2;
     const double den = __builtin_fma(t, t, (iaw2 * N2) * D2);
@@ -308,6 +325,13 @@ __device__ __forceinline__ void lds_order()
     __builtin_amdgcn_wave_barrier();
 }
 
+// a double that is the same in every active lane, moved to scalar registers
+__device__ __forceinline__ double uniform_f64(double v)
+{
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
 // STATE (the cell's own sound speed, cell_state): cs is one more per-lane value of the 64-cell state block and of the pair
 // loop, where the uniform one sits in scalar registers.  The 168 registers have no room for it -- the instantiations without
 // STATE already keep some loop invariants in scratch -- so the STATE arm gives registers back where they are cheapest: the
@@ -317,15 +341,26 @@ __device__ __forceinline__ void lds_order()
 // SAT (GainArgs.sat > 0): the cell's limit is one more per-lane value of the state block and of the pair
 // loop, and every pair's gain goes through saturate_fast once, before both of its addends.  The SAT arm takes the same
 // registers back as the STATE arm does; the instantiations without SAT keep their statements.
-template <bool FROZEN, bool FLOW, bool STATE, bool SAT>
+// DETUNE (GainArgs.shift != NULL): the pair loop knows a beam by its compacted SLOT, not its number, and
+// the slot -> beam map is the run's (the rank of the beam's bit in the presence mask), uniform over its cells: the shifts are
+// staged once per run as 64 doubles of LDS indexed by slot (sW; 13.3 KB in all, still twelve workgroups per CU), zero in the
+// padding slots of the last tile.  In phase 2 the A tile's four shifts are the same in every lane and are moved to scalar
+// registers; the B beam's slot differs between the four lane groups, so its shift is one more LDS read beside its entry.
+// The pair function takes dw = w_B - w_A once per pair, before both of its addends: the exchange still cancels.
+template <bool FROZEN, bool FLOW, bool STATE, bool SAT, bool DETUNE>
 __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 {
-    constexpr bool LEAN = STATE || SAT;
+    constexpr bool LEAN = STATE || SAT || DETUNE;
     constexpr int PCH = (LEAN && !FROZEN) ? 3 : LCH, QCH = (LEAN && !FROZEN) ? 4 : LCH3;
     static_assert(5 * LCAP * LC >= 64 * (LC + 1), "the slot arrays double as the staging area of the presence masks");
     __shared__ double lds[5 * LCAP * LC];
     double *const sI = lds, *const sX = sI + LCAP * LC, *const sY = sX + LCAP * LC, *const sZ = sY + LCAP * LC,
                  *const sR = sZ + LCAP * LC;
+    double *sW = nullptr;                        // [slot] the run's shifts (DETUNE only: no LDS in the other instantiations)
+    if constexpr (DETUNE) {
+        __shared__ double shifts_by_slot[64];
+        sW = shifts_by_slot;
+    }
     const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride;
     const long total = hsize * a.nbeams;
@@ -368,14 +403,39 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                 }
             }
             const int n = __popcll(mask), tiles = (n + LG - 1) / LG;
+            if constexpr (DETUNE) {
+                // the run's shifts by slot: lane b holds beam b's (the table has an entry per lane: CBET_MAX_CBET_BEAMS = 64);
+                // zeros first, for the padding slots.  The barriers in front of phase 2 order these stores before its reads,
+                // the one behind it orders the reads before the next run's stores.
+                static_assert(CBET_MAX_CBET_BEAMS == 64, "one lane per entry of GainArgs.shift");
+                int ln = lane;
+                asm volatile("" : "+v"(ln));     // opaque: the entry's address and the lane's bit mask are formed here, not kept across the kernel
+                sW[ln] = 0.0;
+                lds_order();
+                if ((mask >> ln) & 1ull) sW[__popcll(mask & ((1ull << ln) - 1ull))] = a.shift[ln];
+            }
             // the plasma state of 64 cells at a time (lane = cell), handed to the four runs they make up
             if ((ibz & 3) == 0) {
                 const int hk64 = run_hk(ibz, lane, runs.sft);
-                const CellState c64 = cell_state<FLOW, STATE>(a, runs.base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
-                st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
-                st_pref = cell_pref(a, c64);
-                if (STATE) st_cs = c64.cs;
-                if (SAT) st_lim = cell_sat_limit(a, c64);
+                if constexpr (DETUNE) {
+                    // The DETUNE arm gives back the registers its pair loop takes: the kernel-wide invariants of cell_state,
+                    // cell_pref and cell_kap -- (mach_r1 - mach_r0), (mach_1 - mach_0), 1.0 / iaw, 0.5 * k0, hoisted into vector
+                    // registers or scratch in the other instantiations -- are formed here, once per 64 cells, from operands the
+                    // compiler cannot see through.  The same operations on the same values: no bit changes.
+                    GainArgs b = a;
+                    asm volatile("" : "+s"(b.mach_r0), "+s"(b.mach_0), "+s"(b.iaw), "+s"(b.k0));
+                    const CellState c64 = cell_state<FLOW, STATE>(b, runs.base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                    st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
+                    st_pref = cell_pref(b, c64);
+                    if (STATE) st_cs = c64.cs;
+                    if (SAT) st_lim = cell_sat_limit(b, c64);
+                } else {
+                    const CellState c64 = cell_state<FLOW, STATE>(a, runs.base + (hk64 < 0 ? 0 : (hk64 < HZ ? hk64 : HZ - 1)));
+                    st_rt = c64.rt; st_ux = c64.ux; st_uy = c64.uy; st_uz = c64.uz;
+                    st_pref = cell_pref(a, c64);
+                    if (STATE) st_cs = c64.cs;
+                    if (SAT) st_lim = cell_sat_limit(a, c64);
+                }
             }
             const int from = LC * (ibz & 3) + c;
             const double rt = __shfl(st_rt, from, kWave), ux = __shfl(st_ux, from, kWave), uy = __shfl(st_uy, from, kWave),
@@ -471,8 +531,15 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             S.I = sI[self]; S.kx = sX[self]; S.ky = sY[self]; S.kz = sZ[self];
                             P1.I = sI[p1]; P1.kx = sX[p1]; P1.ky = sY[p1]; P1.kz = sZ[p1];
                             P2.I = sI[p2]; P2.kx = sX[p2]; P2.ky = sY[p2]; P2.kz = sZ[p2];
-                            double g1 = pair_gain_fast(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2);
-                            double g2 = g < 2 ? pair_gain_fast(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2) : 0.0;
+                            double g1, g2;
+                            if constexpr (DETUNE) {
+                                const double wS = sW[LG * ta + g];
+                                g1 = pair_gain_fast<true>(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2, sW[LG * ta + ((g + 1) & 3)] - wS);
+                                g2 = g < 2 ? pair_gain_fast<true>(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2, sW[LG * ta + ((g + 2) & 3)] - wS) : 0.0;
+                            } else {
+                                g1 = pair_gain_fast(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2);
+                                g2 = g < 2 ? pair_gain_fast(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2) : 0.0;
+                            }
                             if (SAT) {
                                 g1 = saturate_fast(g1, S.I, P1.I, lim);
                                 g2 = saturate_fast(g2, S.I, P2.I, lim);
@@ -493,14 +560,23 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             A[s_].I = sI[at]; A[s_].kx = sX[at]; A[s_].ky = sY[at]; A[s_].kz = sZ[at];
                             KA[s_] = 0.0;
                         }
+                        double WA[LG] = {};      // the A tile's shifts: the same in every lane, kept in scalar registers
+                        if constexpr (DETUNE) {
+#pragma unroll
+                            for (int s_ = 0; s_ < LG; ++s_) WA[s_] = uniform_f64(sW[LG * ta + s_]);
+                        }
                         for (int tb = ta + 1; tb < tiles; ++tb) {
                             const int bt = ((LG * tb + g) << sh) + cl;
                             BeamAtCell B;
                             B.I = sI[bt]; B.kx = sX[bt]; B.ky = sY[bt]; B.kz = sZ[bt];
+                            double WB = 0.0;
+                            if constexpr (DETUNE) WB = sW[LG * tb + g];
                             double KB = 0.0;
 #pragma unroll
                             for (int s_ = 0; s_ < LG; ++s_) {
-                                double gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
+                                double gn;
+                                if constexpr (DETUNE) gn = pair_gain_fast<true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, WB - WA[s_]);
+                                else gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
                                 if (SAT) gn = saturate_fast(gn, A[s_].I, B.I, lim);
                                 KA[s_] += gn * B.I;
                                 KB -= gn * A[s_].I;
@@ -589,7 +665,9 @@ __device__ __forceinline__ double readlane_f64(double v, int l)
 // first pair index of row i of the upper triangle of an n x n matrix, rows in order: (i, i + 1), (i, i + 2), ...
 __device__ __forceinline__ int tri_start(int i, int n) { return i * (2 * n - i - 1) / 2; }
 
-template <bool FLOW, bool STATE, bool SAT>
+// DETUNE (GainArgs.shift != NULL): a lane's pair is (sBeam[sa], sBeam[sb]); it forms w_j - w_i once, in
+// front of its walk over the cells.
+template <bool FLOW, bool STATE, bool SAT, bool DETUNE>
 __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, double *__restrict__ work)
 {
     __shared__ double tab[2 * XPAIRS];
@@ -687,6 +765,8 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
                     while (tri_start(sa, n) > q) --sa;
                     while (tri_start(sa + 1, n) <= q) ++sa;
                     const int sb = sa + 1 + q - tri_start(sa, n);
+                    double dw = 0.0;             // DETUNE: the lane's pair's beat frequency, formed once
+                    if constexpr (DETUNE) dw = a.shift[sBeam[sb]] - a.shift[sBeam[sa]];
                     double sum_t = 0.0, sum_g = 0.0;
                     for (int k = 0; k < lc; ++k) {
                         const int cell = (part << sh) + k;
@@ -696,7 +776,9 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
                         BeamAtCell A, B;
                         A.I = sI[k * sp + sa]; A.kx = sX[k * sp + sa]; A.ky = sY[k * sp + sa]; A.kz = sZ[k * sp + sa];
                         B.I = sI[k * sp + sb]; B.kx = sX[k * sp + sb]; B.ky = sY[k * sp + sb]; B.kz = sZ[k * sp + sb];
-                        double gn = pair_gain_fast(A, B, ux, uy, uz, cs, iaw2, pref_iaw2);
+                        double gn;
+                        if constexpr (DETUNE) gn = pair_gain_fast<true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw);
+                        else gn = pair_gain_fast(A, B, ux, uy, uz, cs, iaw2, pref_iaw2);
                         if (SAT) gn = saturate_fast(gn, A.I, B.I, readlane_f64(st_lim, cell));
                         const double x = ((ds_node * gn) * A.I) * B.I;
                         sum_t += x;
@@ -869,11 +951,11 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
-        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0}, [&](auto... s) {
+        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr}, [&](auto... s) {
             hipLaunchKernelGGL((k_gain_field_sym<decltype(s)::value...>), dim3((unsigned)rows), dim3(64), 0, stream, a);
         });
     } else {
-        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0}, [&](auto... s) {
+        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr}, [&](auto... s) {
             hipLaunchKernelGGL((k_gain_field<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a);
         });
     }
@@ -883,7 +965,7 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
 hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream)
 {
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
-    dispatch({a.flow != nullptr, a.state != nullptr}, [&](auto... s) {
+    dispatch({a.flow != nullptr, a.state != nullptr, a.shift != nullptr}, [&](auto... s) {
         hipLaunchKernelGGL((k_pair_amplitude<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a, amp);
     });
     return hipGetLastError();
@@ -894,7 +976,7 @@ hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, 
     if (a.hx_hi <= a.hx_lo || a.nbeams < 2) return hipSuccess;
     // the number of workgroups follows from the slab alone, never from the device: the same partial sums everywhere
     const long groups = exchange_groups((long)(a.hx_hi - a.hx_lo) * (a.ny + 2));
-    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0}, [&](auto... s) {
+    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr}, [&](auto... s) {
         hipLaunchKernelGGL((k_exchange_matrix<decltype(s)::value...>), dim3((unsigned)groups), dim3(XT), 0, stream, a, work);
     });
     if (hipError_t e = hipGetLastError()) return e;

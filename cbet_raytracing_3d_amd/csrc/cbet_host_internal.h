@@ -35,6 +35,10 @@ struct cbet_context {
     const double *state = nullptr;      // the table in use: state_own, a caller's, or NULL
     // limit of the ion-acoustic amplitude in the gain kernels (cbet_context_set_saturation): 0 = none
     double dn_max = 0.0;
+    // per-beam frequency shifts of the gain kernels (cbet_context_set_detuning): NULL = one colour
+    double *shift_own = nullptr;        // the context's own [CBET_MAX_CBET_BEAMS] table, allocated by the first cbet_context_set_detuning that selects shifts
+    const double *shift = nullptr;      // the table in use: shift_own, or NULL
+    double shift_host[CBET_MAX_CBET_BEAMS] = {};   // what shift_own holds (cbet_context_detuning)
 };
 
 namespace cbet {
@@ -144,11 +148,13 @@ MeshArgs mesh_state_args(const cbet_params *p, const cbet_derived &d, const cbet
                          const cbet_mesh *mesh, const cbet_mesh_ions *ions, double *state);
 // The mesh's sizes and NULL pointers (all a device entry can check); whole: the values too (HOST arrays).
 int mesh_check(const cbet_mesh *mesh, bool whole);
-// The gain kernels', k_pair_amplitude's, k_exchange_matrix's and its host twin's (cbet_gain_abi.cpp).  cs, gc: cbet_gain_constants';
+// The gain kernels', k_pair_amplitude's, k_exchange_matrix's and its host twin's (cbet_exchange_host.cpp).  cs, gc: cbet_gain_constants';
 // packed: the arrays hold the slab's planes only.  gain, scratch, change, consume and frozen stay zero: the gain update sets them.
+// shift: the per-beam frequency shifts, a table of CBET_MAX_CBET_BEAMS doubles (device memory for a kernel, host memory for the
+// twin), or NULL.
 GainArgs gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
-                   const double *fields, const double *ne3d, const double *flow, const double *state, double sat, int hx_lo,
-                   int hx_hi, bool packed);
+                   const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
+                   const double *shift, int hx_lo, int hx_hi, bool packed);
 // The slab [hx_lo, hx_hi) lies in the haloed grid; who: the entry point's name and ": " in front of the message, or "".
 int slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p);
 

@@ -107,6 +107,12 @@ class RayTracer:
         self._tabulate_flow(ctx, params)
         self._tabulate_state(ctx, params)
         ctx.set_saturation(self.saturation)         # a context prepared for this tracer carries its limit, as it carries its tables
+        # ... and the frequency shifts the tracer's own context was last given (set_detuning, or a caller's call on it): a
+        # set-up call, made only when they changed
+        own = self.ctx.detuning_source
+        if ctx is not self.ctx and ctx.detuning_source is not own:
+            ctx.set_detuning(own, self._stream())
+            ctx.detuning_source = own
 
     def _tabulate_other(self, ctx, params):
         """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False
@@ -275,6 +281,29 @@ class RayTracer:
         or infinite value raises and changes nothing."""
         self.ctx.set_saturation(dn_max)
         self.saturation = float(dn_max)
+
+    # ---- wavelength detuning (include/cbet_mi355x.h cbet_context_set_detuning; DESIGN.md section 19) --------------------
+    def set_detuning(self, dlambda_angstrom=None, domega=None):
+        """Per-beam colours in the gain kernels: ONE of dlambda_angstrom (wavelength shifts of the nominal wavelength in
+        Angstrom, > 0 = red; api.wavelength_shift_to_domega) or domega (angular-frequency shifts in rad/s), one value per
+        beam.  Neither given: off, the default.  The ion-acoustic resonance of the ordered pair (i, j) gains the beat frequency
+        w_j - w_i: in still plasma the red-shifted beam gains.  Only differences enter, so equal shifts are the same as none.
+        The shifts are the context's: gain_field, pair_amplitude, exchange_matrix, both loops of cbet_solve and
+        api.cbet_solve(ctx=tracer.ctx) honour them from the next launch on, and so does every context prepared for this
+        tracer later (the pipeline's).  A set-up call: it waits for torch's current stream.  A NaN or infinite shift or a
+        wrong count raises and changes nothing."""
+        if dlambda_angstrom is not None and domega is not None:
+            raise ValueError("set_detuning takes dlambda_angstrom or domega, not both")
+        if dlambda_angstrom is not None:
+            dl = np.asarray(dlambda_angstrom, dtype=np.float64)
+            if not np.isfinite(dl).all():
+                raise ValueError("set_detuning: dlambda_angstrom holds a NaN or infinite value")
+            domega = api.wavelength_shift_to_domega(self.params, dl)
+        self.ctx.set_detuning(domega, self._stream())
+
+    def detuning(self):
+        """The frequency shifts in use (rad/s, one per beam; the context's own record), or None if none."""
+        return self.ctx.detuning()
 
     def pair_amplitude(self, fields, gain_params, x_lo=0, x_hi=None, ne3d=None, out=None):
         """The largest ion-acoustic amplitude any beam pair's UNCLAMPED gain corresponds to, per cell of the planes

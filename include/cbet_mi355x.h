@@ -790,6 +790,43 @@ int cbet_exchange_matrix_host(const double *fields, const double *ne3d, double *
                               const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
                               double dn_max);
 
+/* ---- wavelength detuning ------------------------------------------------------------------ */
+/*
+ * Per-beam frequency shifts in the gain stage.  Beam b has the angular frequency omega + w_b, omega the nominal one of
+ * cbet_derive and w_b in rad/s (a wavelength shift dl of the nominal l0 = 2 pi c / omega is w = omega l0 / (l0 + dl) - omega:
+ * a red shift, dl > 0, is a negative w).  The ion-acoustic wave of the ordered pair (i, j), q = k_j - k_i, is driven at the
+ * beat frequency, so the resonance of the pair gain G_ij = pref P(eta_ij) becomes
+ *     eta_ij = ((0.0 - (qx*ux + qy*uy + qz*uz)) + (w_j - w_i)) / (kiaw*cs + 1e-10)
+ * in the ordered kernel -- every written operator ONE IEEE fp64 operation in the written order, no fused multiply-add --
+ * and N = -(q . u) + (w_j - w_i) in the pair function of the pair-once kernels (a few ulp from it, as without shifts).
+ * Identities: beam i gains where its frequency in the plasma frame is the lower one, so in still plasma the red-shifted beam
+ * gains; (w_i - w_j) = -(w_j - w_i) exactly, so G_ji = -G_ij stays exact and a cell's exchange sum_i I_i K_i still cancels,
+ * with or without a saturation limit; equal shifts add an exact zero and give the bits of no shifts; two exactly parallel
+ * beams exchange nothing whatever their colours (the pair-once kernels count the beat frequency only where q != 0).
+ * Out of scope: only the beat frequency enters.  Each beam's own k0, ncrit and refraction keep the nominal wavelength (the
+ * relative change is ~1e-3 at +-3 Angstrom of 351 nm), and the Manley-Rowe photon-number correction of the same order is
+ * left out.  The trace kernels only gather K and do not see the shifts.
+ *
+ * cbet_context_set_detuning: domega[nbeams] HOST doubles.  NULL, or all shifts equal to the first, selects none (a new
+ * context's default); otherwise the values are copied to a device table of CBET_MAX_CBET_BEAMS doubles that the context owns
+ * (the first such call allocates it).  The call synchronises `stream` before it overwrites the table and copies
+ * synchronously: a SET-UP call, not capturable in a graph, and launches on other streams that still read the table are the
+ * caller's to wait for.  It applies to launches made after it.  CBET_EINVAL naming the offence: a NaN or infinite shift,
+ * nbeams above CBET_MAX_CBET_BEAMS or below 1, nbeams different from the context's parameters, a NULL context; a refused call
+ * changes nothing.  Every entry that builds its gain arguments from that context honours the shifts -- cbet_gain_field,
+ * cbet_gain_field_slab, cbet_gain_field_packed, cbet_pair_amplitude (the amplitude is the detuned |G_ij|'s),
+ * cbet_exchange_matrix, and cbet_cbet_solve with a caller's context; with ctx == NULL the solve runs without shifts.
+ * cbet_context_detuning: *nbeams = the number of shifts in use, 0 for none, and out[0 .. *nbeams) = their values (out holds
+ * CBET_MAX_CBET_BEAMS doubles, or is NULL to ask for the count alone).
+ * cbet_exchange_matrix_host_shifted: cbet_exchange_matrix_host with shift[nbeams] HOST doubles or NULL: the ordered
+ * statements with the beat frequency, compensated sums as there.  cbet_exchange_matrix_host calls it with NULL.
+ */
+int cbet_context_set_detuning(cbet_context *ctx, const double *domega, int nbeams, void *stream);
+int cbet_context_detuning(cbet_context *ctx, double *out, int *nbeams);
+int cbet_exchange_matrix_host_shifted(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo, int hx_hi,
+                                      const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
+                                      double dn_max, const double *shift);
+
 /* ---- exit pass --------------------------------------------------------------- */
 /*
  * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
