@@ -1,18 +1,19 @@
 """The cases of tests/test_exchange_host.py and tests/test_gpu_exchange_matrix.py (the pairwise exchange matrix, DESIGN.md
 section 18): two CPU references of T[i][j] = sum over cells of ds g_ij I_i I_j and of Gross[i][j] = the sum of the magnitudes
-that do not share a line with the library, on the worlds of helpers/saturation_cases.py.
+that do not share a line with the library, on the worlds of helpers/gain_worlds.py.
 
-  composed_matrix: T_ij = sum over cells of E_i K_i^(ij), K_i^(ij) the pieces of saturation_cases.Composed -- the unchanged
+  composed_matrix: T_ij = sum over cells of E_i K_i^(ij), K_i^(ij) the pieces of gain_reference.Composed -- the unchanged
       oracle run pair by pair; E_i = ds I_i is the deposited energy, so nothing of the normalisation is restated.
-  pairwise_matrix: the pair loop of saturation_cases.Restatement (its pref, kap, u, cs, ds) over normalised fields, one row of
-      the matrix at a time.
+  pairwise_matrix: the pair loop of gain_reference.Restatement.update over normalised fields with matrix=True, one row of the
+      matrix at a time.
 
 normalised(): the fields a gain update leaves, from Restatement.normalise -- what both the host twin and pairwise_matrix read."""
 import numpy as np
 
 from helpers import saturation_cases as SC
+from helpers.gain_worlds import SLABS as _SLABS
 
-SLABS = [(0, 9), (9, 22)]          # and (22, nx + 2): the three slabs of the tests
+SLABS = [(0, 9), _SLABS["traced"]]          # and (22, nx + 2): the three slabs of the tests
 
 
 def normalised(R, raw):
@@ -28,38 +29,13 @@ def _antisymmetric(T, G):
 
 
 def pairwise_matrix(R, inten, k, dn_max=0.0, planes=None):
-    """(T, Gross) of normalised fields by Restatement R's cell quantities; planes = (lo, hi): those x planes only."""
-    nb, n = inten.shape
-    inside = np.ones(n, dtype=bool)
-    if planes is not None:
-        inside = np.zeros(R.grid, dtype=bool)
-        inside[planes[0]:planes[1]] = True
-        inside = inside.reshape(-1)
-    T, G = np.zeros((nb, nb)), np.zeros((nb, nb))
-    for i in range(nb - 1):
-        at = np.nonzero((inten[i] > 0) & inside)[0]
-        if at.size == 0:
-            continue
-        Ii, Ij = inten[i, at], inten[i + 1:, at]
-        q = k[:, i + 1:, at] - k[:, i:i + 1, at]
-        kiaw = np.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2])
-        ok = (Ij > 0) & (kiaw > 0)
-        eta = (0.0 - (q[0] * R.u[0][at] + q[1] * R.u[1][at] + q[2] * R.u[2][at])) / (np.where(ok, kiaw, 1.0) * R.cs[at] + 1e-10)
-        e2 = eta * eta
-        P = R.iaw2 * eta / ((e2 - 1.0) * (e2 - 1.0) + R.iaw2 * e2)
-        gain = np.where(ok, R.pref[at] * P, 0.0)
-        if dn_max > 0:
-            w = np.abs(gain) * np.sqrt(Ii * Ij)
-            lim = dn_max * R.kap[at]
-            gain = gain * np.where(w > lim, lim / np.where(w > 0, w, 1.0), 1.0)
-        x = R.ds[at] * gain * Ii * Ij
-        T[i, i + 1:] = x.sum(axis=1)
-        G[i, i + 1:] = np.abs(x).sum(axis=1)
-    return _antisymmetric(T, G)
+    """(T, Gross) of normalised fields by Restatement R's pair loop; planes = (lo, hi): those x planes only."""
+    out = R.update(None, limits=[dn_max], matrix=True, normalised=(inten, k), planes=planes)
+    return out["T"][0], out["G"][0]
 
 
 def composed_matrix(comp, dn_max=0.0):
-    """(T, Gross) from saturation_cases.Composed: sum over cells of E_i K_i^(ij), the piece scaled by the clamp's factor."""
+    """(T, Gross) from gain_reference.Composed: sum over cells of E_i K_i^(ij), the piece scaled by the clamp's factor."""
     nb = comp.nb
     T, G = np.zeros((nb, nb)), np.zeros((nb, nb))
     lim = dn_max * comp.kap

@@ -1,6 +1,6 @@
 """Wavelength detuning in the gain stage, the part that needs no device: the new entries of the C ABI
 are exported, declared and refuse bad arguments, the wavelength conversion is the exact one, the CPU reference of
-tests/test_gpu_detuning.py (helpers/detuning_cases.py) meets the conditions asked of it alone, and the shifted host twin of
+tests/test_gpu_detuning.py (helpers/gain_reference.py with the shifts of helpers/detuning_cases.py) meets the conditions asked of it alone, and the shifted host twin of
 the exchange matrix agrees with that reference and keeps its exact identities -- in Python, and as a stand-alone program
 under AddressSanitizer + UndefinedBehaviorSanitizer.
 
@@ -18,9 +18,10 @@ from cbet_raytracing_3d_amd import build
 from conftest import NCPU, ROOT
 from helpers import detuning_cases as DC
 from helpers import exchange_cases as XC
+from helpers import gain_worlds as W
 from helpers import saturation_cases as SC
+from helpers.gain_worlds import LAST_BITS         # here of Gross_ij: tests/test_exchange_host.py's bound
 
-LAST_BITS = 1e-12          # of Gross_ij: tests/test_exchange_host.py's bound
 NAMES = ("cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted")
 CSRC = os.path.join(ROOT, "cbet_raytracing_3d_amd", "csrc")
 
@@ -34,18 +35,18 @@ def api():
 
 def _world(w, which):
     if "xfields" not in w:
-        w["xfields"], w["xI"], w["xk"] = XC.normalised(w[which], w.get("raw", w.get("ofields")))
+        w["xfields"], w["xI"], w["xk"] = XC.normalised(w[which], w["raw"])
     return w
 
 
 @pytest.fixture(scope="module")
 def traced(api, oracle, inputs):
-    return _world(SC.traced_world(api, oracle, inputs, NCPU), "restated")
+    return _world(W.traced_world(api, oracle, inputs, NCPU), "restated")
 
 
 @pytest.fixture(scope="module")
 def crowded(api, oracle, inputs):
-    return _world(SC.crowded_world(api, oracle, inputs, NCPU), "plain")
+    return _world(W.crowded_world(api, oracle, inputs, NCPU), "plain")
 
 
 def _error(api):
@@ -155,9 +156,9 @@ def test_shifts_are_distinct_and_move_the_reference(traced, crowded):
 
 def test_reference_without_shifts_is_the_saturation_tests_reference(crowded):
     R = crowded["plain"]
-    again = DC.update(R, crowded["raw"])
+    again = R.update(crowded["raw"])
     assert np.array_equal(again["K"][0], SC.reference(crowded, "plain")["K0"])
-    equal = DC.update(R, crowded["raw"], np.full(60, 1.7e12))
+    equal = R.update(crowded["raw"], np.full(60, 1.7e12))
     assert np.array_equal(equal["K"][0], again["K"][0])                     # only differences enter
 
 

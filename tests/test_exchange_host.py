@@ -1,7 +1,7 @@
 """The pairwise exchange matrix, the part that needs no device: the new entries of the C ABI are
 exported, declared and refuse bad arguments, and the host twin cbet_exchange_matrix_host -- the reference of the device path
 in tests/test_gpu_exchange_matrix.py -- agrees with two CPU references that share no line with the library
-(helpers/exchange_cases.py) on the two grids of helpers/saturation_cases.py:
+(helpers/exchange_cases.py) on the two grids of helpers/gain_worlds.py:
 
   TRACED  48 x 21 x 134, six beams, the oracle's traced fields: the oracle composed per pair, and the numpy pair loop.
   CROWDED 13 x 11 x 148, sixty beams, 9-54 beams per cell, super-critical nodes, touched-but-absent entries: the numpy pair
@@ -18,9 +18,10 @@ import pytest
 
 from conftest import NCPU, ROOT
 from helpers import exchange_cases as XC
+from helpers import gain_worlds as W
 from helpers import saturation_cases as SC
+from helpers.gain_worlds import LAST_BITS         # here of Gross_ij (row sums: of sum_j Gross_ij)
 
-LAST_BITS = 1e-12          # of Gross_ij (row sums: of sum_j Gross_ij)
 SLAB_BITS = 1e-14          # slabs against the whole: the same compensated sums, cut in three
 NAMES = ("cbet_exchange_matrix_work_bytes", "cbet_exchange_matrix", "cbet_exchange_matrix_host")
 
@@ -34,7 +35,7 @@ def api():
 
 @pytest.fixture(scope="module")
 def traced(api, oracle, inputs):
-    w = SC.traced_world(api, oracle, inputs, NCPU)
+    w = W.traced_world(api, oracle, inputs, NCPU)
     if "xfields" not in w:
         w["xfields"], w["xI"], w["xk"] = XC.normalised(w["restated"], w["ofields"])
     return w
@@ -42,7 +43,7 @@ def traced(api, oracle, inputs):
 
 @pytest.fixture(scope="module")
 def crowded(api, oracle, inputs):
-    w = SC.crowded_world(api, oracle, inputs, NCPU)
+    w = W.crowded_world(api, oracle, inputs, NCPU)
     if "xfields" not in w:
         w["xfields"], w["xI"], w["xk"] = XC.normalised(w["plain"], w["raw"])
     return w
@@ -84,10 +85,10 @@ def test_header_compiles_as_c(tmp_path):
 def test_work_bytes_follow_the_grid_and_the_beam_count(api):
     cap = 768                                                               # CBET_EXCHANGE_MAX_GROUPS
     for shape, nb in (((6, 9, 13), 2), ((6, 9, 13), 1), ((13, 11, 148), 60), ((48, 21, 134), 6), ((5, 4, 37), 64), ((256, 256, 256), 60)):
-        p = SC.params(api, shape, nb)
+        p = W.params(api, shape, nb)
         rows = (shape[0] + 2) * (shape[1] + 2)
         assert api.exchange_matrix_work_bytes(p) == min(rows, cap) * 2 * (nb * (nb - 1) // 2) * 8, (shape, nb)
-    assert api.exchange_matrix_work_bytes(SC.params(api, (5, 4, 37), 65)) == 0
+    assert api.exchange_matrix_work_bytes(W.params(api, (5, 4, 37), 65)) == 0
     assert api.lib().cbet_exchange_matrix_work_bytes(None) == 0
 
 
@@ -108,7 +109,7 @@ def test_device_entry_refuses_bad_arguments_and_names_them(api):
 
 
 def test_host_twin_refuses_bad_arguments_and_names_them(api):
-    p, g = SC.params(api, (6, 9, 13), 2), api.default_gain_params()
+    p, g = W.params(api, (6, 9, 13), 2), api.default_gain_params()
     f, n, o = np.zeros((4, 2, 8, 11, 15)), np.zeros((6, 9, 13)), np.zeros((2, 2))
     call = lambda ff, nn, oo, lo, hi, pp=p, dn=0.0: api.lib().cbet_exchange_matrix_host(  # noqa: E731
         api._addr(ff), api._addr(nn), api._addr(oo), None, lo, hi, C.byref(pp), C.byref(g), None, None, dn)
@@ -119,9 +120,9 @@ def test_host_twin_refuses_bad_arguments_and_names_them(api):
         assert call(f, n, o, lo, hi) == api.EINVAL and "slab [%d,%d)" % (lo, hi) in _error(api)
     for dn in (-1.0, float("nan"), float("inf")):
         assert call(f, n, o, 0, 8, dn=dn) == api.EINVAL and "dn_max" in _error(api)
-    assert call(f, n, o, 0, 8, pp=SC.params(api, (6, 9, 13), 65)) == api.EINVAL and "nbeams = 65" in _error(api)
+    assert call(f, n, o, 0, 8, pp=W.params(api, (6, 9, 13), 65)) == api.EINVAL and "nbeams = 65" in _error(api)
     assert call(f, n, o, 0, 8) == api.OK and not o.any()                                 # empty fields: zeros
-    one = SC.params(api, (6, 9, 13), 1)
+    one = W.params(api, (6, 9, 13), 1)
     assert call(np.ones((4, 1, 8, 11, 15)), n, np.zeros((1, 1)), 0, 8, pp=one) == api.OK  # one beam: nothing to do
 
 

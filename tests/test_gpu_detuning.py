@@ -1,6 +1,7 @@
 """Wavelength detuning in the gain stage on the device (cbet_grid_kernels.hip: the DETUNE arms of k_gain_field,
 k_gain_field_sym, k_pair_amplitude and k_exchange_matrix) against the numpy restatement of
-helpers/detuning_cases.py and the shifted host twin, on the two grids of helpers/saturation_cases.py:
+helpers/gain_reference.py with the shifts of helpers/detuning_cases.py and the shifted host twin, on the two grids of
+helpers/gain_worlds.py:
 
   TRACED  48 x 21 x 134, six beams, the oracle's traced fields.
   CROWDED 13 x 11 x 148, sixty beams, synthetic fields: 9-54 beams per cell, so a run's slots are not its beam numbers.
@@ -18,14 +19,14 @@ import pytest
 from conftest import NCPU
 from helpers import detuning_cases as DC
 from helpers import exchange_cases as XC
+from helpers import gain_calls as D
+from helpers import gain_worlds as W
 from helpers import saturation_cases as SC
+from helpers.gain_reference import halo
+from helpers.gain_worlds import CUTS, LAST_BITS, SLABS, TOL       # LAST_BITS also bounds the amplitude map, of its maximum
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                 # against a CPU reference, of max |K|; the exchange matrix against the twin, of Gross_ij
-LAST_BITS = 1e-12          # pair-once against ordered, of max |K|; the amplitude map, of its maximum
-SLABS = {"traced": (9, 22), "crowded": (9, 14)}
-CUTS = {"traced": [0, 1, 12, 13, 29, 50], "crowded": [0, 1, 6, 9, 14, 15]}
 KERNELS = [False, True]
 KERNEL_IDS = ["ordered", "pair_once"]
 
@@ -44,95 +45,18 @@ def api():
     return a
 
 
-def _tracer(api, inputs, p, beam_norm):
-    from cbet_raytracing_3d_amd.tracer import RayTracer
-    _, r, ne, te = inputs
-    tr = RayTracer(p, r, ne, te, beam_norm=beam_norm)
-    tr.tabulate()
-    return tr
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
 @pytest.fixture(scope="module")
 def worlds(api, oracle, inputs, torch_cuda):
     """Per grid: the CPU world, a tracer that gets shifts (`tr`), one that never has any (`base`), the device fields."""
-    out = {}
-    for name, world in (("traced", SC.traced_world(api, oracle, inputs, NCPU)), ("crowded", SC.crowded_world(api, oracle, inputs, NCPU))):
-        tr, base = _tracer(api, inputs, world["p"], world["bn"]), _tracer(api, inputs, world["p"], world["bn"])
-        dev = {k: torch_cuda.from_numpy(np.ascontiguousarray(world[k])).cuda() for k in ("raw", "flow", "shifted", "state")}
-        out[name] = dict(world, name=name, tr=tr, base=base, dev=dev)
+    out = D.device_worlds(api, oracle, inputs, torch_cuda, NCPU)
     yield out
-    for w in out.values():
-        w["tr"].close()
-        w["base"].close()
-
-
-def _select(torch, api, w, tr, which):
-    """The table set-ups of tests/test_gpu_saturation.py (detuning_cases.TABLES): "none"; "flow" the sphere's own table handed
-    in as a caller's; "uniform" flow plus a state table holding the scalars; "three" flow plus the three-state pattern;
-    "tabled" the offset target's flow plus the three-state pattern."""
-    dev = w["dev"]
-    flow, state = None, None
-    if which == "flow":
-        flow = dev["flow"]
-    elif which == "uniform":
-        _, cs, gc = api.gain_constants(w["p"], w["gp"])
-        state = torch.empty_like(dev["state"])
-        state[0], state[1] = cs, gc
-        flow = dev["flow"]
-    elif which == "three":
-        flow, state = dev["flow"], dev["state"]
-    elif which == "tabled":
-        flow, state = dev["shifted"], dev["state"]
-    else:
-        assert which == "none", which
-    tr.set_flow(flow)
-    tr.set_gain_state(state)
+    D.close_worlds(out)
 
 
 def _clear(tr):
     tr.set_detuning()
     tr.set_saturation(0.0)
-    tr.set_flow(None)
-    tr.set_gain_state(None)
-
-
-def _update(torch, tr, raw, gp, pair_once, frozen=False, x=(0, None), change=True):
-    f = raw.clone()
-    k = tr.new_grid(per_beam=True)
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda") if change else None
-    tr.gain_field(f, k, gp, ch, pair_once=pair_once, frozen=frozen, x_lo=x[0], x_hi=x[1])
-    return f, k, ch
-
-
-def _packed(torch, api, tr, raw, gp, pair_once, slab, frozen=False):
-    from cbet_raytracing_3d_amd.tracer import _frozen
-    x0, x1 = slab
-    f = raw[:, :, x0:x1].contiguous()
-    k = torch.zeros((raw.shape[1], x1 - x0) + tuple(raw.shape[3:]), dtype=torch.float64, device="cuda")
-    api.gain_field_packed(f, None, k, torch.empty_like(k) if pair_once else None, None, x0, x1, tr.params, _frozen(gp, frozen), tr.ctx,
-                          _stream(torch))
-    return f, k
-
-
-def _all_calls(torch, api, tr, raw, gp, pair_once, slab):
-    """First call, frozen call on fresh energy, slab, packed slab, frozen call on the packed slab: [(what, tensor)]."""
-    f, k, _ = _update(torch, tr, raw, gp, pair_once, change=False)
-    f2 = f.clone()
-    f2[0] = raw[0]
-    k2 = torch.zeros_like(k)
-    tr.gain_field(f2, k2, gp, None, pair_once=pair_once, frozen=True)
-    fs, ks, _ = _update(torch, tr, raw, gp, pair_once, x=slab, change=False)
-    fp, kp = _packed(torch, api, tr, raw, gp, pair_once, slab)
-    f3 = f.clone()
-    f3[0] = raw[0]
-    fq, kq = _packed(torch, api, tr, f3, gp, pair_once, slab, frozen=True)
-    torch.cuda.synchronize()
-    return [("first fields", f), ("first gain", k), ("frozen fields", f2), ("frozen gain", k2), ("slab fields", fs),
-            ("slab gain", ks), ("packed fields", fp), ("packed gain", kp), ("packed frozen fields", fq), ("packed frozen gain", kq)]
+    D.select(tr)
 
 
 # ---- 1. off is off --------------------------------------------------------------------------------------------------------
@@ -147,27 +71,32 @@ def test_off_is_off(api, torch_cuda, worlds, grid, pair_once):
     w = worlds[grid]
     tr, base, gp, raw, slab = w["tr"], w["base"], w["gp"], w["dev"]["raw"], SLABS[grid]
     nb = w["p"].nbeams
+
+    def calls(tracer, fields):
+        """First call, frozen call on fresh energy, slab, packed slab, frozen call on the packed slab: [(what, tensor)]."""
+        return D.all_calls(torch, api, tracer, fields, gp, pair_once, slab, change=False, packed_frozen=True)
+
     try:
         assert base.detuning() is None and tr.detuning() is None                # a new context has none
-        want = _all_calls(torch, api, base, raw, gp, pair_once, slab)
+        want = calls(base, raw)
         assert float(want[1][1].abs().max()) > 1.0 and float(want[5][1].abs().max()) > 1.0
         for mode, kw in (("none", dict()), ("zeros", dict(domega=np.zeros(nb))), ("equal", dict(domega=np.full(nb, 3.3e12))),
                          ("equal wavelengths", dict(dlambda_angstrom=np.full(nb, -2.0)))):
             tr.set_detuning(**kw)
             assert tr.detuning() is None, mode
-            got = _all_calls(torch, api, tr, raw, gp, pair_once, slab)
+            got = calls(tr, raw)
             for (what, a), (_, b) in zip(want, got):
                 assert torch.equal(a, b), (mode, what)
         last = nb - 1
         without = raw.clone()
         without[:, last] = 0.0
-        want = _all_calls(torch, api, base, without, gp, pair_once, slab)
+        want = calls(base, without)
         assert float(want[1][1].abs().max()) > 1.0
         arm = np.full(nb, 3.3e12)
         arm[last] = 0.0
         tr.set_detuning(domega=arm)
         assert np.array_equal(tr.detuning(), arm)                                # shifts are selected: the DETUNE instantiations run
-        got = _all_calls(torch, api, tr, without, gp, pair_once, slab)
+        got = calls(tr, without)
         for (what, a), (_, b) in zip(want, got):
             assert torch.equal(a, b), ("the DETUNE arm with equal shifts", what)
     finally:
@@ -188,22 +117,18 @@ def test_detuned_update_matches_the_restatement(api, torch_cuda, worlds, grid, t
     ref = DC.reference(w, tables)
     want = ref["K"] if limit == "none" else ref["Khalf"]
     scale = float(np.abs(ref["K"]).max())
-    _select(torch, api, w, tr, tables)
+    D.select(tr, *D.tables(api, torch, w, tables))
     tr.set_detuning(domega=ref["shift"])
     tr.set_saturation(0.0 if limit == "none" else ref["half"])
     try:
         assert np.array_equal(tr.detuning(), ref["shift"])
         got = {}
         for pair_once in KERNELS:
-            f, k, ch = _update(torch, tr, raw, gp, pair_once)
-            f2 = f.clone()
-            f2[0] = raw[0]
-            k2 = torch.zeros_like(k)
-            tr.gain_field(f2, k2, gp, None, pair_once=pair_once, frozen=True)
+            f, k, ch, _, k2, _ = D.first_and_frozen(torch, tr, raw, gp, pair_once)
             parts, fields = tr.new_grid(per_beam=True), raw.clone()
             for x0, x1 in zip(CUTS[grid][:-1], CUTS[grid][1:]):
                 tr.gain_field(fields, parts, gp, None, pair_once=pair_once, x_lo=x0, x_hi=x1)
-            _, kp = _packed(torch, api, tr, raw, gp, pair_once, slab)
+            _, kp, _ = D.packed(torch, api, tr, raw, gp, pair_once, slab, change=False)
             got[pair_once] = dict(first=k.cpu().numpy(), frozen=k2.cpu().numpy(), slabs=parts.cpu().numpy(), packed=kp.cpu().numpy(),
                                   change=ch.cpu().numpy(), fields=torch.equal(fields, f), nf=f.cpu().numpy())
     finally:
@@ -241,8 +166,8 @@ def test_detuned_update_matches_the_restatement(api, torch_cuda, worlds, grid, t
 def _two_beams(api, inputs, torch, parallel):
     """Two synthetic beams on a 12 x 10 x 37 grid (rows of 39 cells: three runs, the last of 7), crossing at a right angle or
     exactly parallel, present in most cells, absent (zero) or touched-only (negative energy) in some."""
-    p = SC.params(api, (12, 10, 37), 2)
-    tr = _tracer(api, inputs, p, inputs[0][[0, 29]])
+    p = W.params(api, (12, 10, 37), 2)
+    tr = D.tracer(inputs, p, inputs[0][[0, 29]])
     shape = (2,) + tr.grid_shape
     rng = np.random.default_rng(19)
     u = rng.random(shape)
@@ -265,15 +190,15 @@ def test_red_shifted_beam_gains_in_still_plasma(api, inputs, torch_cuda):
         assert shift[0] < 0 < shift[1]
         ne3d = torch.zeros((p.nx, p.ny, p.nz), dtype=torch.float64, device="cuda")
         api.moveToAndFromGPU(ne3d, tr.ctx.tables()[0], ne3d.numel() * 8, tr.gpu)
-        sub = SC.halo(ne3d.cpu().numpy()) < api.derive(p).ncrit
+        sub = halo(ne3d.cpu().numpy()) < api.derive(p).ncrit
         assert sub.any()
         for pair_once in KERNELS:
-            _, k0, _ = _update(torch, tr, raw, gp, pair_once, change=False)
+            _, k0, _ = D.update(torch, tr, raw, gp, pair_once, change=False)
             assert not bool(k0.any())                                        # one colour, no flow: K == 0 exactly
             tr.set_detuning(domega=shift)
-            f, k, _ = _update(torch, tr, raw, gp, pair_once, change=False)
+            f, k, _ = D.update(torch, tr, raw, gp, pair_once, change=False)
             tr.set_detuning(domega=shift[::-1].copy())
-            _, ks, _ = _update(torch, tr, raw, gp, pair_once, change=False)
+            _, ks, _ = D.update(torch, tr, raw, gp, pair_once, change=False)
             tr.set_detuning()
             nf, K, Ks = f.cpu().numpy(), k.cpu().numpy(), ks.cpu().numpy()
             both = (nf[0, 0] > 0) & (nf[0, 1] > 0) & sub
@@ -302,7 +227,7 @@ def test_parallel_beams_of_different_colour_exchange_nothing(api, inputs, torch_
         for shift in (DC.shifts(2), np.array([1e-10, -1e-10]), np.array([0.0, 5e-11])):   # the scale of the tests, and of D at q = 0
             tr.set_detuning(domega=shift)
             for pair_once in KERNELS:
-                f, k, _ = _update(torch, tr, raw, gp, pair_once, change=False)
+                f, k, _ = D.update(torch, tr, raw, gp, pair_once, change=False)
                 assert not bool(k.any()), (pair_once, shift)
             assert bool((f[0] > 0).any())
             T, G = tr.exchange_matrix(f, gp, gross=True)
@@ -328,7 +253,7 @@ def test_far_off_resonance(api, torch_cuda, worlds, grid, scale):
         assert share < DC.FAR_SHARE
     tr.set_detuning(domega=ref["shift"])
     try:
-        got = [_update(torch, tr, raw, gp, pair_once, change=False)[1].cpu().numpy() for pair_once in KERNELS]
+        got = [D.update(torch, tr, raw, gp, pair_once, change=False)[1].cpu().numpy() for pair_once in KERNELS]
     finally:
         _clear(tr)
     errs = [float(np.abs(g - ref["K"]).max() / k0) for g in got]
@@ -350,11 +275,11 @@ def test_exchange_matrix_and_amplitude_map_with_shifts(api, torch_cuda, worlds, 
     tabled = tables == "tabled"
     ref = DC.reference(w, tabled)
     dn = 0.0 if limit == "none" else ref["half"]
-    _select(torch, api, w, tr, tables)
+    D.select(tr, *D.tables(api, torch, w, tables))
     tr.set_detuning(domega=ref["shift"])
     tr.set_saturation(dn)
     try:
-        f, k, _ = _update(torch, tr, raw, gp, True, change=False)
+        f, k, _ = D.update(torch, tr, raw, gp, True, change=False)
         T, G = tr.exchange_matrix(f, gp, gross=True)
         T2, G2 = tr.exchange_matrix(f, gp, gross=True)
         amp = tr.pair_amplitude(f, gp)
@@ -402,15 +327,15 @@ def test_context_refuses_names_and_remembers(api, torch_cuda, worlds):
             assert np.array_equal(tr.detuning(), first)                      # a refused call changes nothing
         with pytest.raises(ValueError):
             tr.set_detuning(dlambda_angstrom=np.zeros(60), domega=first)
-        _, k1, _ = _update(torch, tr, raw, gp, True, change=False)
+        _, k1, _ = D.update(torch, tr, raw, gp, True, change=False)
         tr.set_detuning(domega=second)                                       # replaces the first for launches made after it
         assert np.array_equal(tr.detuning(), second)
-        _, k2, _ = _update(torch, tr, raw, gp, True, change=False)
-        _, k1_again, _ = _update(torch, w["base"], raw, gp, True, change=False)
+        _, k2, _ = D.update(torch, tr, raw, gp, True, change=False)
+        _, k1_again, _ = D.update(torch, w["base"], raw, gp, True, change=False)
         ref = DC.reference(w, False)
         scale = float(np.abs(ref["K"]).max())
         assert float(np.abs(k1.cpu().numpy() - ref["K"]).max()) < TOL * scale
-        want2 = DC.update(w["plain"], w["raw"], second)["K"][0]
+        want2 = w["plain"].update(w["raw"], second)["K"][0]
         assert float(np.abs(k2.cpu().numpy() - want2).max()) < TOL * float(np.abs(want2).max())
         assert float((k2 - k1).abs().max()) > DC.MOVES * scale
         assert float(np.abs(k1_again.cpu().numpy() - ref["K0"]).max()) < TOL * float(np.abs(ref["K0"]).max())   # another context is untouched
@@ -440,7 +365,7 @@ def test_solve_loops_run_with_shifts(api, inputs, torch_cuda):
     solve's fields afterwards differs from the unshifted solve's."""
     from conftest import parity_err
     torch = torch_cuda
-    tr = _tracer(api, inputs, api.default_params(32, nbeams=len(SC.BEAMS)), inputs[0][SC.BEAMS])
+    tr = D.tracer(inputs, api.default_params(32, nbeams=len(W.BEAMS)), inputs[0][W.BEAMS])
     gp = api.default_gain_params(tolerance=1e-6, max_passes=12, relax=1.0)
 
     def solves():
@@ -455,7 +380,7 @@ def test_solve_loops_run_with_shifts(api, inputs, torch_cuda):
         e = tr.new_grid()
         ws = torch.zeros(api.cbet_workspace_bytes(tr.params) // 8 + 1, dtype=torch.float64, device="cuda")
         api.cbet_solve(tr.d_te, tr.d_r, tr.d_ne, e, tr.d_bbeam_norm, tr.d_beam_norm, tr.d_pow_r, tr.d_phase_r, tr.params, gp,
-                       workspace=ws, ctx=tr.ctx, stream=_stream(torch))
+                       workspace=ws, ctx=tr.ctx, stream=D.stream(torch))
         torch.cuda.synchronize()
         n = tr.params.nbeams * e.numel()
         off = (api.cbet_workspace_gain(tr.params, ws) - ws.data_ptr()) // 8
@@ -468,7 +393,7 @@ def test_solve_loops_run_with_shifts(api, inputs, torch_cuda):
 
     try:
         plain, t_plain = solves()
-        tr.set_detuning(dlambda_angstrom=DC.three_colours(len(SC.BEAMS)))
+        tr.set_detuning(dlambda_angstrom=DC.three_colours(len(W.BEAMS)))
         tinted, t_tinted = solves()
         for loop in plain:
             moved = float((tinted[loop][1] - plain[loop][1]).abs().max() / plain[loop][1].abs().max())

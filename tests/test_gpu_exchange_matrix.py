@@ -1,5 +1,5 @@
 """The pairwise exchange matrix on the device (cbet_grid_kernels.hip k_exchange_matrix + k_exchange_reduce; DESIGN.md section
-18) against its host twin cbet_exchange_matrix_host, on the two grids of helpers/saturation_cases.py and three small shapes.
+18) against its host twin cbet_exchange_matrix_host, on the two grids of helpers/gain_worlds.py and three small shapes.
 
   TRACED  48 x 21 x 134, six beams, the oracle's traced fields.
   CROWDED 13 x 11 x 148, sixty beams, 9-54 beams per cell: runs staged whole (up to 32 present beams) and in halves.
@@ -13,12 +13,12 @@ import pytest
 
 from conftest import NCPU
 from helpers import exchange_cases as XC
-from helpers import saturation_cases as SC
-from helpers import state_cases as S
+from helpers import gain_calls as D
+from helpers import gain_worlds as W
+from helpers.gain_worlds import TOL        # here: device (pair-once arithmetic) against the host twin (ordered statements), of Gross_ij
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                 # device (pair-once arithmetic) against the host twin (ordered statements), of Gross_ij
 SLAB_BITS = 1e-12          # slab calls summed against the whole grid's call, of Gross_ij
 WHICH = {"traced": "restated", "crowded": "plain"}
 
@@ -37,14 +37,6 @@ def api():
     return a
 
 
-def _tracer(inputs, p, beam_norm):
-    from cbet_raytracing_3d_amd.tracer import RayTracer
-    _, r, ne, te = inputs
-    tr = RayTracer(p, r, ne, te, beam_norm=beam_norm)
-    tr.tabulate()
-    return tr
-
-
 def _up(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
@@ -61,8 +53,8 @@ def worlds(api, oracle, inputs, torch_cuda):
     """Per grid: the CPU world, a tracer, the device tables, the device fields normalised once and their host copy."""
     torch = torch_cuda
     out = {}
-    for name, world in (("traced", SC.traced_world(api, oracle, inputs, NCPU)), ("crowded", SC.crowded_world(api, oracle, inputs, NCPU))):
-        tr = _tracer(inputs, world["p"], world["bn"])
+    for name, world in (("traced", W.traced_world(api, oracle, inputs, NCPU)), ("crowded", W.crowded_world(api, oracle, inputs, NCPU))):
+        tr = D.tracer(inputs, world["p"], world["bn"])
         dev = {k: _up(torch, world[k]) for k in ("raw", "flow", "state", "ne3d")}
         f, k = _normalise(torch, tr, dev["raw"], world["gp"], dev["ne3d"])
         torch.cuda.synchronize()
@@ -230,8 +222,8 @@ def _small(api, oracle, inputs, torch, shape, nb, raw):
     bn = np.concatenate([bn_all, bn_all])[:nb]
     cfg = oracle.default_config(shape[0], nbeams=nb, ny=shape[1], nz=shape[2])
     ne3d, _ = oracle.node_tables(cfg, r, ne, te)
-    p, gp = SC.params(api, shape, nb), api.default_gain_params(relax=1.0)
-    tr = _tracer(inputs, p, bn)
+    p, gp = W.params(api, shape, nb), api.default_gain_params(relax=1.0)
+    tr = D.tracer(inputs, p, bn)
     try:
         dne = _up(torch, ne3d)
         f, _ = _normalise(torch, tr, _up(torch, raw), gp, dne)
@@ -258,7 +250,7 @@ def test_two_beams_and_one_beam_on_rows_shorter_than_a_run(api, oracle, inputs, 
 
 def test_sixty_four_beams_reach_the_last_triangular_index(api, oracle, inputs, torch_cuda):
     shape = (5, 4, 37)
-    raw, _ = S.crowded_fields((64,) + tuple(n + 2 for n in shape))
+    raw, _ = W.crowded_fields((64,) + tuple(n + 2 for n in shape))
     T, G, want, gross = _small(api, oracle, inputs, torch_cuda, shape, 64, raw)
     err, gerr = XC.worst(T, want, gross), XC.worst(G, gross, gross)
     print("5 x 4 x 37, 64 beams: device vs host twin %.3e of Gross (Gross itself %.3e); %d of 2016 pairs exchange; T[62][63] %.6e"

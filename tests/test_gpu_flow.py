@@ -8,16 +8,17 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, parity_err
+from helpers import gain_calls as D
+from helpers import gain_worlds as W
 from helpers.device_tables import context_flow
+from helpers.gain_worlds import BEAMS, TOL
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                 # tests/test_gpu_cbet.py's bound, of max |K|
 UM = 1e-4                  # cm
 OFFSET = (20 * UM, -35 * UM, 10 * UM)
-SHIFT = (20 * UM, 0.0, -15 * UM)         # the offset of the oracle comparisons and of the end-to-end target
+SHIFT = W.OFFSET                         # the offset of the oracle comparisons and of the end-to-end target
 N = 32
-BEAMS = [0, 16, 29, 38, 47, 55]          # the six beams of tests/test_gpu_cbet.py
 
 
 @pytest.fixture(scope="module")
@@ -40,11 +41,7 @@ def _random_coeffs(lmax, seed, total=0.05):
 
 
 def _tracer(api, inputs, shape, beams):
-    from cbet_raytracing_3d_amd.tracer import RayTracer
-    bn, r, ne, te = inputs
-    p = api.default_params(shape[0], nbeams=len(beams))
-    p.ny, p.nz = shape[1], shape[2]
-    return RayTracer(p, r, ne, te, beam_norm=bn[beams])
+    return D.tracer(inputs, W.params(api, shape, len(beams)), inputs[0][beams], tabulate=False)
 
 
 def _flow_bits(api, tr):
@@ -52,10 +49,6 @@ def _flow_bits(api, tr):
     flow = context_flow(api, tr.ctx, tr.params, tr.gpu)
     assert flow is not None
     return flow
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---- 1. device = host twin, bitwise -----------------------------------------------------------------------------------
@@ -82,7 +75,7 @@ def test_device_table_equals_the_host_twin_bitwise(api, torch_cuda, table_tracer
     p, gp = tr.params, api.default_gain_params()
     targets, node = _targets(api, p)
     target = targets[name]
-    api.tabulate_flow(tr.ctx, p, gp, target, _stream(torch_cuda))
+    api.tabulate_flow(tr.ctx, p, gp, target, D.stream(torch_cuda))
     torch_cuda.cuda.synchronize()
     got = _flow_bits(api, tr)
     want = api.flow_table(p, gp, target)
@@ -104,12 +97,12 @@ def test_second_and_replayed_calls_give_the_same_bits(api, inputs, torch_cuda):
     want = api.flow_table(p, gp, target).view(np.int64)
     junk = np.full(3 * N ** 3, -3.0)
     assert tr.ctx.flow() is None
-    api.tabulate_flow(tr.ctx, p, gp, target, _stream(torch_cuda))
+    api.tabulate_flow(tr.ctx, p, gp, target, D.stream(torch_cuda))
     torch_cuda.cuda.synchronize()
     addr = tr.ctx.flow()
     assert np.array_equal(_flow_bits(api, tr), want)
     api.moveToAndFromGPU(addr, junk, junk.nbytes, tr.gpu)
-    api.tabulate_flow(tr.ctx, p, gp, target, _stream(torch_cuda))
+    api.tabulate_flow(tr.ctx, p, gp, target, D.stream(torch_cuda))
     torch_cuda.cuda.synchronize()
     assert tr.ctx.flow() == addr and np.array_equal(_flow_bits(api, tr), want)
     side = torch_cuda.cuda.Stream()
@@ -160,17 +153,9 @@ def world(api, oracle, inputs, torch_cuda):
     k_shift, _ = oracle.gain_field(_shifted(oracle, SHIFT), og, ofields, ne3d, relax=1.0, nthreads=NCPU)
     k_centre, _ = oracle.gain_field(cfg, og, ofields, ne3d, relax=1.0, nthreads=NCPU)
     yield dict(sphere=sphere, tr=tr, gp=gp, cfg=cfg, og=og, bn=bn, ne3d=ne3d, kap=kap, ofields=ofields,
-               osteps=traced[0][1], k_shift=k_shift, k_centre=k_centre)
+               raw=torch_cuda.from_numpy(ofields).cuda(), osteps=traced[0][1], k_shift=k_shift, k_centre=k_centre)
     sphere.close()
     tr.close()
-
-
-def _update(torch, tr, fields_np, gp, pair_once, frozen=False, x=(0, None), change=True):
-    f = torch.from_numpy(fields_np.copy()).cuda()
-    k = tr.new_grid(per_beam=True)
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda") if change else None
-    tr.gain_field(f, k, gp, ch, pair_once=pair_once, frozen=frozen, x_lo=x[0], x_hi=x[1])
-    return f, k, ch
 
 
 # ---- 2. the sphere's table is a no-op ---------------------------------------------------------------------------------
@@ -185,25 +170,25 @@ def test_the_spheres_table_changes_no_bit(api, torch_cuda, world, pair_once):
 
     def calls():
         out = []
-        f, k, ch = _update(torch, tr, world["ofields"], gp, pair_once)
+        f, k, ch = D.update(torch, tr, world["raw"], gp, pair_once)
         out += [f, k, ch]
         f2 = f.clone()
         f2[0] = torch.from_numpy(world["ofields"][0].copy()).cuda()        # fresh energy on the k entries of that call
         k2, ch2 = tr.new_grid(per_beam=True), torch.zeros(2, dtype=torch.float64, device="cuda")
         tr.gain_field(f2, k2, gp, ch2, pair_once=pair_once, frozen=True)
         out += [f2, k2, ch2]
-        out += list(_update(torch, tr, world["ofields"], gp, pair_once, x=(x0, x1)))
+        out += list(D.update(torch, tr, world["raw"], gp, pair_once, x=(x0, x1)))
         f_pk = torch.from_numpy(world["ofields"][:, :, x0:x1].copy()).cuda()
         g_pk = torch.zeros_like(f_pk[0])
         ch_pk = torch.zeros(2, dtype=torch.float64, device="cuda")
-        api.gain_field_packed(f_pk, None, g_pk, g_pk if pair_once else None, ch_pk, x0, x1, tr.params, gp, tr.ctx, _stream(torch))
+        api.gain_field_packed(f_pk, None, g_pk, g_pk if pair_once else None, ch_pk, x0, x1, tr.params, gp, tr.ctx, D.stream(torch))
         out += [f_pk, g_pk, ch_pk]
         torch.cuda.synchronize()
         return [t.cpu().numpy() for t in out]
 
     assert tr.ctx.flow() is None
     plain = calls()
-    api.tabulate_flow(tr.ctx, tr.params, gp, None, _stream(torch))
+    api.tabulate_flow(tr.ctx, tr.params, gp, None, D.stream(torch))
     try:
         assert tr.ctx.flow() is not None
         table = calls()
@@ -234,7 +219,7 @@ def test_offset_target_matches_the_oracle_with_a_shifted_box(api, torch_cuda, wo
     print("offset: the oracle's shifted and centred gains differ by %.3e of max |K|" % (moved / scale))
     assert moved >= 100 * TOL * scale                                       # a kernel that ignores the table cannot pass
     for pair_once in (False, True):
-        _, k, _ = _update(torch_cuda, world["tr"], world["ofields"], world["gp"], pair_once)
+        _, k, _ = D.update(torch_cuda, world["tr"], world["raw"], world["gp"], pair_once)
         err = np.abs(k.cpu().numpy() - want).max() / scale
         print("offset, %s kernel: max |K - oracle| / max |K| = %.3e" % ("pair-once" if pair_once else "ordered", err))
         assert err < TOL, (pair_once, err)
@@ -257,7 +242,7 @@ def test_monopole_target_matches_the_oracle_with_scaled_radii(api, oracle, input
     scale = np.abs(want).max()
     assert np.abs(want - plain).max() >= 100 * TOL * scale
     for pair_once in (False, True):
-        _, k, _ = _update(torch_cuda, tr, world["ofields"], gp, pair_once)
+        _, k, _ = D.update(torch_cuda, tr, world["raw"], gp, pair_once)
         err = np.abs(k.cpu().numpy() - want).max() / scale
         print("monopole, %s kernel: max |K - oracle| / max |K| = %.3e" % ("pair-once" if pair_once else "ordered", err))
         assert err < TOL, (pair_once, err)
@@ -274,15 +259,15 @@ def test_callers_table(api, torch_cuda, world):
         for pair_once in (False, True):
             tr.set_flow("target", gp)
             tr.tabulate()
-            f0, k0, ch0 = _update(torch, tr, world["ofields"], gp, pair_once, change=False)
+            f0, k0, ch0 = D.update(torch, tr, world["raw"], gp, pair_once, change=False)
             own = tr.ctx.flow()
             tr.set_flow(torch.from_numpy(host).cuda())
             assert tr.ctx.flow() not in (None, own)
-            f1, k1, _ = _update(torch, tr, world["ofields"], gp, pair_once, change=False)
+            f1, k1, _ = D.update(torch, tr, world["raw"], gp, pair_once, change=False)
             assert torch.equal(k1, k0) and torch.equal(f1, f0)              # the host twin's array: tabulate_flow's bits
             assert float(k0.abs().max()) > 1.0
             tr.set_flow(torch.zeros((3, p.nx, p.ny, p.nz), dtype=torch.float64, device="cuda"))
-            _, kz, _ = _update(torch, tr, world["ofields"], gp, pair_once, change=False)
+            _, kz, _ = D.update(torch, tr, world["raw"], gp, pair_once, change=False)
             assert not bool(kz.any())                                       # no flow: eta = 0, P = 0, K = 0 exactly
         for bad in (torch.zeros((3, p.nx, p.ny, p.nz + 1), dtype=torch.float64, device="cuda"),
                     torch.zeros((p.nx, p.ny, p.nz, 3), dtype=torch.float64, device="cuda"),
@@ -368,14 +353,14 @@ def test_native_loop_refuses_a_selected_flow(api, torch_cuda, world):
     tr, gp = world["sphere"], world["gp"]
     args = (tr.d_te, tr.d_r, tr.d_ne, tr.new_grid(), tr.d_bbeam_norm, tr.d_beam_norm, tr.d_pow_r, tr.d_phase_r, tr.params,
             api.default_gain_params(max_passes=1))
-    api.tabulate_flow(tr.ctx, tr.params, gp, None, _stream(torch_cuda))
+    api.tabulate_flow(tr.ctx, tr.params, gp, None, D.stream(torch_cuda))
     try:
         with pytest.raises(api.CbetError) as ei:
-            api.cbet_solve(*args, ctx=tr.ctx, stream=_stream(torch_cuda))
+            api.cbet_solve(*args, ctx=tr.ctx, stream=D.stream(torch_cuda))
         assert ei.value.code == api.EINVAL and "flow" in str(ei.value)
     finally:
         tr.ctx.set_flow(None)
-    api.cbet_solve(*args, ctx=tr.ctx, stream=_stream(torch_cuda))          # and runs again without one
+    api.cbet_solve(*args, ctx=tr.ctx, stream=D.stream(torch_cuda))          # and runs again without one
     torch_cuda.cuda.synchronize()
 
 

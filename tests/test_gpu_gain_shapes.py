@@ -2,31 +2,26 @@
 more than 64 cells -- the pair-once kernel computes the plasma state for 64 cells at a time and hands it to four 16-cell runs
 by lane shuffle -- and grids whose three sides differ, against oracle.gain_field cell by cell.
 
-  48 x 21 x 134, six beams, the oracle's traced fields: haloed 50 x 23 x 136 -- a ragged last brick in y, whole bricks in z,
-      three 64-cell state groups per row, planes of 23 * 136 doubles;
-  13 x 11 x 148, sixty beams, synthetic crowded fields: haloed 15 x 13 x 150 -- odd in x, ragged bricks in y and z, the last
-      state group holds 22 cells, the halves and quarters arms in runs beyond the first group;
+  TRACED and CROWDED of helpers/gain_worlds.py (48 x 21 x 134 with six traced beams, 13 x 11 x 148 with sixty crowded ones),
+      whose builders assert the regime: most of the gain beyond the first 64 cells of a z-row, all three run classes there;
   on the first grid the FLOW arms (the sphere's table, a caller's table of an offset target), slab-wise and slab-packed
       updates, and arrays that start 1 and 8 doubles into an allocation.
 
-The bounds are those of tests/test_gpu_cbet.py and tests/test_gpu_flow.py."""
+The bounds are those of tests/test_gpu_cbet.py and tests/test_gpu_flow.py; the device calls are helpers/gain_calls.py's."""
 import numpy as np
 import pytest
 
 from conftest import NCPU
+from helpers import gain_calls as D
+from helpers import gain_worlds as W
+from helpers.gain_worlds import LAST_BITS, TOL, Z_GROUPS
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                 # tests/test_gpu_cbet.py's bound, of max |K|
-LAST_BITS = 1e-12          # pair-once against ordered kernel, of max |K| (the crowded-cells test's bound)
-BEAMS = [0, 16, 29, 38, 47, 55]
-SHAPE = (48, 21, 134)
-CROWDED = (13, 11, 148)
-SHIFT = (20e-4, 0.0, -15e-4)             # tests/test_gpu_flow.py's offset target, cm
-# hk of the pair-once kernel's 64-cell state groups (up to a row's shift of 0 or 8 cells on these grids)
-Z_GROUPS = (slice(0, 64), slice(64, 128), slice(128, None))
-SLAB = (9, 22)
-CUTS = [0, 1, 12, 13, 29, SHAPE[0] + 2]
+BEAMS, SHAPE = W.BEAMS, W.TRACED
+SHIFT = W.OFFSET                         # tests/test_gpu_flow.py's offset target, cm
+SLAB = W.SLABS["traced"]
+CUTS = W.CUTS["traced"]
 
 
 @pytest.fixture(scope="module")
@@ -43,74 +38,15 @@ def api():
     return a
 
 
-def _tracer(api, inputs, shape, beam_norm):
-    from cbet_raytracing_3d_amd.tracer import RayTracer
-    _, r, ne, te = inputs
-    p = api.default_params(shape[0], nbeams=len(beam_norm))
-    p.ny, p.nz = shape[1], shape[2]
-    tr = RayTracer(p, r, ne, te, beam_norm=beam_norm)
-    tr.tabulate()
-    return tr
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _update(torch, tr, raw, gp, pair_once, frozen=False, x=(0, None), change=True):
-    """One gain update from a zero gain on a copy of the device fields `raw`: (fields, gain, change)."""
-    f = raw.clone()
-    k = tr.new_grid(per_beam=True)
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda") if change else None
-    tr.gain_field(f, k, gp, ch, pair_once=pair_once, frozen=frozen, x_lo=x[0], x_hi=x[1])
-    return f, k, ch
-
-
-def _first_and_frozen(torch, tr, raw, gp, pair_once):
-    """A first call, then a frozen call on fresh energy over the k entries of the first: numpy f, k, change, f2, k2."""
-    f, k, ch = _update(torch, tr, raw, gp, pair_once)
-    f2 = f.clone()
-    f2[0] = raw[0]
-    k2 = torch.zeros_like(k)
-    tr.gain_field(f2, k2, gp, None, pair_once=pair_once, frozen=True)
-    return tuple(t.cpu().numpy() for t in (f, k, ch, f2, k2))
-
-
-def _waves(tr, pair_once, x_lo, x_hi):
-    """Wavefronts of one gain launch over the planes [x_lo, x_hi) (launch_gain_field): each adds its share of the two
-    convergence sums with one atomicAdd."""
-    hy, hz = tr.grid_shape[1], tr.grid_shape[2]
-    if pair_once:
-        return (x_hi - x_lo) * hy                                       # one single-wavefront workgroup per z-row
-    bricks = (((x_hi + 1) >> 1) - (x_lo >> 1)) * ((hy + 3) // 4) * ((hz + 7) // 8)
-    return 4 * min((bricks + 3) // 4, 256 * 64)                         # four wavefronts per workgroup
-
-
-def _group_errors(a, b, scale):
-    return [float(np.abs(a[..., z] - b[..., z]).max() / scale) for z in Z_GROUPS]
-
-
 # ---- A1. real fields on 48 x 21 x 134 ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def world(api, oracle, inputs, torch_cuda):
-    bn = inputs[0][BEAMS].copy()
-    _, r, ne, te = inputs
-    tr = _tracer(api, inputs, SHAPE, bn)
-    cfg = oracle.default_config(SHAPE[0], nbeams=len(BEAMS), ny=SHAPE[1], nz=SHAPE[2])
-    assert oracle.grid_shape(cfg) == tr.grid_shape == (50, 23, 136)
-    ne3d, kap = oracle.node_tables(cfg, r, ne, te)
-    og = oracle.gain_default()
-    ofields = np.stack([oracle.trace_cbet(cfg, og, bn, ne3d, kap, quantity=q, per_beam=True, nthreads=NCPU)[0]
-                        for q in (1, 2, 3, 4)])
-    ogain, _ = oracle.gain_field(cfg, og, ofields, ne3d, relax=1.0, nthreads=NCPU)
-    scale = float(np.abs(ogain).max())
-    # the regime: a non-trivial gain (1/cm), and most of it beyond the first 64 cells of its z-row
-    assert scale > 1.0
-    assert int((ogain[..., 64:] != 0).sum()) >= 10000
-    assert all(np.abs(ogain[..., z]).max() > 1e-3 * scale for z in Z_GROUPS[:2])
-    gp = api.default_gain_params(relax=1.0)
-    raw = torch_cuda.from_numpy(ofields).cuda()
-    yield dict(tr=tr, cfg=cfg, og=og, ne3d=ne3d, ofields=ofields, ogain=ogain, scale=scale, gp=gp, raw=raw)
+    """The CPU side of W.traced_world, a tracer of this module's own and the device fields."""
+    w = W.traced_world(api, oracle, inputs, NCPU)
+    tr = D.tracer(inputs, w["p"], w["bn"])
+    assert tr.grid_shape == (50, 23, 136)
+    yield dict(tr=tr, cfg=w["cfg"], og=w["og"], ne3d=w["ne3d"], ofields=w["ofields"], ogain=w["ogain"], scale=w["scale"], gp=w["gp"],
+               raw=torch_cuda.from_numpy(w["ofields"]).cuda())
     tr.close()
 
 
@@ -120,9 +56,9 @@ def updates(api, world, torch_cuda):
     tr, raw = world["tr"], world["raw"]
     out = {}
     for pair_once in (False, True):
-        res = _first_and_frozen(torch_cuda, tr, raw, world["gp"], pair_once)
-        _, k3, _ = _update(torch_cuda, tr, raw, api.default_gain_params(relax=0.25), pair_once, change=False)
-        out[pair_once] = res + (k3.cpu().numpy(),)
+        res = D.first_and_frozen(torch_cuda, tr, raw, world["gp"], pair_once)[:5]
+        _, k3, _ = D.update(torch_cuda, tr, raw, api.default_gain_params(relax=0.25), pair_once, change=False)
+        out[pair_once] = tuple(t.cpu().numpy() for t in res + (k3,))
     return out
 
 
@@ -130,7 +66,7 @@ def test_ordered_kernel_equals_the_oracle_bitwise(world, updates):
     f, k, ch, f2, k2, k3 = updates[False]
     want, scale = world["ogain"], world["scale"]
     print("48x21x134 ordered: max |K - oracle| / max |K| = %.3e, by 64-cell z group %s" %
-          (np.abs(k - want).max() / scale, _group_errors(k, want, scale)))
+          (np.abs(k - want).max() / scale, D.group_errors(k, want, scale)))
     assert np.array_equal(k, want)
 
 
@@ -138,8 +74,8 @@ def test_pair_once_kernel_matches_oracle_and_ordered_in_every_z_group(world, upd
     k_o, k_p = updates[False][1], updates[True][1]
     want, scale = world["ogain"], world["scale"]
     err = float(np.abs(k_p - want).max() / scale)
-    by_group_oracle = _group_errors(k_p, want, scale)
-    by_group = _group_errors(k_p, k_o, scale)
+    by_group_oracle = D.group_errors(k_p, want, scale)
+    by_group = D.group_errors(k_p, k_o, scale)
     print("48x21x134 pair-once: max |K - oracle| / max |K| = %.3e (by z group %s); against the ordered kernel %.3e (by z group %s)"
           % (err, by_group_oracle, float(np.abs(k_p - k_o).max() / scale), by_group))
     assert err < TOL
@@ -182,49 +118,20 @@ def test_both_kernels_normalise_to_the_same_bits(updates):
 
 
 # ---- A2. synthetic crowded fields on 13 x 11 x 148, 60 beams ----------------------------------------------------------
-def _crowded_fields(shape):
-    """The generator of test_pair_once_kernel_on_crowded_cells_equals_the_ordered_kernel in numpy, energies of the order of
-    real deposits (x 1e11): (fields [4, 60, ...], present mask)."""
-    rng = np.random.default_rng(20261018)
-    u = rng.random(shape)
-    row = rng.random(shape[:3] + (1,))                          # a beam crosses a z-row or not
-    x = np.arange(shape[1]).reshape(1, -1, 1, 1)
-    density = np.where(x < 5, 0.15, np.where(x < 10, 0.45, 0.9))
-    present = (row < density) & (u < 0.8)
-    touched_only = (row < density + 0.03) & ~present & (u < 0.9)
-    e = (rng.random(shape) * 1e3 + 1.0) * 1e11
-    raw = np.zeros((4,) + shape)
-    raw[0] = np.where(present, e, np.where(touched_only, -e, 0.0))
-    raw[1:] = (rng.random((3,) + shape) - 0.5) * (raw[0] != 0)
-    return raw, present
-
-
 def test_crowded_long_rows_match_the_oracle(api, oracle, inputs, torch_cuda):
     """Up to ~54 beams per cell in rows of 150 cells: the halves and quarters arms (sh = 3, 2) in runs of the second and
     third state group, touched-but-absent and untouched entries, super-critical nodes -- oracle, ordered kernel (bitwise)
     and pair-once kernel, first call and frozen."""
-    bn, r, ne, te = inputs
-    tr = _tracer(api, inputs, CROWDED, bn)
+    w = W.crowded_world(api, oracle, inputs, NCPU)         # its builder asserts the regime the docstring names
+    classes, want, scale, gp = w["classes"], w["ogain"], w["scale"], w["gp"]
+    tr = D.tracer(inputs, w["p"], w["bn"])
     assert tr.grid_shape == (15, 13, 150)
-    raw, present = _crowded_fields((60,) + tr.grid_shape)
-    assert (raw[0] < 0).any() and (raw[0] == 0).any()
-    windows = np.stack([present[..., z0:z0 + 16].any(-1).sum(0) for z0 in range(64, tr.grid_shape[2], 16)])
-    classes = [int((windows <= 20).sum()), int(((windows > 20) & (windows <= 40)).sum()), int((windows > 40).sum())]
-    assert min(classes) >= 50, classes           # whole runs, halves and quarters, all beyond the first 64 cells
-    cfg = oracle.default_config(CROWDED[0], nbeams=60, ny=CROWDED[1], nz=CROWDED[2])
-    ne3d, _ = oracle.node_tables(cfg, r, ne, te)
-    assert (ne3d >= tr.derived.ncrit).any()      # the eps <= 0 arm runs
-    want, _ = oracle.gain_field(cfg, oracle.gain_default(), raw, ne3d, relax=1.0, nthreads=NCPU)
-    scale = float(np.abs(want).max())
-    assert scale > 1.0
-    assert all(np.abs(want[..., z]).max() > 1e-3 * scale for z in Z_GROUPS)         # something in all three groups
-    gp = api.default_gain_params(relax=1.0)
-    d_raw = torch_cuda.from_numpy(raw).cuda()
-    f_o, k_o, ch_o, f2_o, k2_o = _first_and_frozen(torch_cuda, tr, d_raw, gp, False)
-    f_p, k_p, ch_p, f2_p, k2_p = _first_and_frozen(torch_cuda, tr, d_raw, gp, True)
+    d_raw = torch_cuda.from_numpy(w["raw"]).cuda()
+    f_o, k_o, ch_o, f2_o, k2_o = [t.cpu().numpy() for t in D.first_and_frozen(torch_cuda, tr, d_raw, gp, False)[:5]]
+    f_p, k_p, ch_p, f2_p, k2_p = [t.cpu().numpy() for t in D.first_and_frozen(torch_cuda, tr, d_raw, gp, True)[:5]]
     tr.close()
     err_o, err_p = float(np.abs(k_o - want).max() / scale), float(np.abs(k_p - want).max() / scale)
-    by_group = _group_errors(k_p, k_o, scale)
+    by_group = D.group_errors(k_p, k_o, scale)
     print("13x11x148 crowded (windows by class %s, max |K| %.3e): ordered vs oracle %.3e, pair-once vs oracle %.3e, "
           "pair-once vs ordered by z group %s, frozen vs first %.3e / %.3e"
           % (classes, scale, err_o, err_p, by_group, np.abs(k2_o - k_o).max() / scale, np.abs(k2_p - k_o).max() / scale))
@@ -250,13 +157,13 @@ def test_the_spheres_table_changes_no_bit_off_the_cube(api, torch_cuda, world, p
     tr, gp, raw = world["tr"], world["gp"], world["raw"]
 
     def calls():
-        out = list(_update(torch, tr, raw, gp, pair_once)) + list(_update(torch, tr, raw, gp, pair_once, x=SLAB))
+        out = list(D.update(torch, tr, raw, gp, pair_once)) + list(D.update(torch, tr, raw, gp, pair_once, x=SLAB))
         torch.cuda.synchronize()
         return [t.cpu().numpy() for t in out]
 
     assert tr.ctx.flow() is None
     plain = calls()
-    api.tabulate_flow(tr.ctx, tr.params, gp, None, _stream(torch))
+    api.tabulate_flow(tr.ctx, tr.params, gp, None, D.stream(torch))
     try:
         assert tr.ctx.flow() is not None
         table = calls()
@@ -267,7 +174,7 @@ def test_the_spheres_table_changes_no_bit_off_the_cube(api, torch_cuda, world, p
     # need not agree in the last bits.  Every wavefront's addend is the same bits in both calls (the gain is); sums of n
     # non-negative addends taken in two orders differ by at most (n - 1) 2^-53 relative (tests/test_gpu_flow.py), with n this
     # launch's own wavefront count:
-    waves = {"": _waves(tr, pair_once, 0, tr.grid_shape[0]), "slab ": _waves(tr, pair_once, *SLAB)}
+    waves = {"": D.waves(tr, pair_once, 0, tr.grid_shape[0]), "slab ": D.waves(tr, pair_once, *SLAB)}
     assert waves[""] == (1150 if pair_once else 2552) and waves["slab "] == (299 if pair_once else 716)
     for (where, what), a, b in zip([(w, n) for w in ("", "slab ") for n in ("fields", "gain", "change")], plain, table):
         if what == "change":
@@ -297,11 +204,11 @@ def test_callers_table_of_an_offset_target_matches_the_shifted_oracle(api, oracl
     tr.set_flow(torch.from_numpy(table).cuda())
     try:
         for pair_once in (False, True):
-            _, k, _ = _update(torch, tr, world["raw"], gp, pair_once, change=False)
+            _, k, _ = D.update(torch, tr, world["raw"], gp, pair_once, change=False)
             k = k.cpu().numpy()
             err = float(np.abs(k - want).max() / scale)
             print("48x21x134 offset, %s kernel: max |K - oracle| / max |K| = %.3e, by z group %s" %
-                  ("pair-once" if pair_once else "ordered", err, _group_errors(k, want, scale)))
+                  ("pair-once" if pair_once else "ordered", err, D.group_errors(k, want, scale)))
             assert err < TOL, (pair_once, err)
     finally:
         tr.set_flow(None)
@@ -339,12 +246,8 @@ def test_packed_slab_equals_whole_grid_storage_off_the_cube(api, torch_cuda, wor
     tr, gp = world["tr"], world["gp"]
     x0, x1 = SLAB
     assert (x0 * tr.grid_shape[1] * tr.grid_shape[2]) % 16 == 8
-    f_ref, ref, ch_ref = _update(torch, tr, world["raw"], gp, pair_once, x=SLAB)
-    f_pk = world["raw"][:, :, x0:x1].contiguous()
-    g_pk = torch.zeros_like(ref[:, x0:x1]).contiguous()
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
-    api.gain_field_packed(f_pk, None, g_pk, torch.empty_like(g_pk) if pair_once else None, ch, x0, x1, tr.params, gp,
-                          tr.ctx, _stream(torch))
+    f_ref, ref, ch_ref = D.update(torch, tr, world["raw"], gp, pair_once, x=SLAB)
+    f_pk, g_pk, ch = D.packed(torch, api, tr, world["raw"], gp, pair_once, SLAB)
     scale = float(ref.abs().max())
     assert scale > 1.0 and not bool(ref[:, :x0].any()) and not bool(ref[:, x1:].any())
     err = float((g_pk - ref[:, x0:x1]).abs().max()) / scale

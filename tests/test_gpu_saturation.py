@@ -1,6 +1,6 @@
 """Saturation of the ion-acoustic wave in both CBET gain kernels and the amplitude map (cbet_grid_kernels.hip: the SAT arms
-of k_gain_field and k_gain_field_sym, k_pair_amplitude) on the two grids of
-tests/test_gpu_gain_shapes.py, against the two CPU references of helpers/saturation_cases.py.
+of k_gain_field and k_gain_field_sym, k_pair_amplitude) on the two grids of helpers/gain_worlds.py,
+against the two CPU references of helpers/gain_reference.py with the limits of helpers/saturation_cases.py.
 
   TRACED  48 x 21 x 134, six beams, the oracle's traced fields; reference: the oracle composed per pair.
   CROWDED 13 x 11 x 148, sixty beams, synthetic fields (9-54 beams per cell: whole runs, halves, quarters); reference: the
@@ -18,16 +18,14 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, parity_err
+from helpers import gain_calls as D
+from helpers import gain_worlds as W
 from helpers import saturation_cases as SC
-from helpers.state_cases import Z_GROUPS
+from helpers.gain_worlds import CUTS, LAST_BITS, SLABS, TOL, Z_GROUPS
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                 # against a CPU reference, of max |K|
-LAST_BITS = 1e-12          # pair-once against ordered, of max |K|
 ACTS = 1e-3                # the clamp moves K by more than this, of max |K|, in every z group that has a gain
-SLABS = {"traced": (9, 22), "crowded": (9, 14)}
-CUTS = {"traced": [0, 1, 12, 13, 29, 50], "crowded": [0, 1, 6, 9, 14, 15]}
 KERNELS = [False, True]
 KERNEL_IDS = ["ordered", "pair_once"]
 
@@ -46,99 +44,12 @@ def api():
     return a
 
 
-def _tracer(api, inputs, p, beam_norm):
-    from cbet_raytracing_3d_amd.tracer import RayTracer
-    _, r, ne, te = inputs
-    tr = RayTracer(p, r, ne, te, beam_norm=beam_norm)
-    tr.tabulate()
-    return tr
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
 @pytest.fixture(scope="module")
 def worlds(api, oracle, inputs, torch_cuda):
     """Per grid: the CPU world, a tracer that gets limits (`tr`), one that never has one (`base`), the device fields."""
-    out = {}
-    for name, world in (("traced", SC.traced_world(api, oracle, inputs, NCPU)), ("crowded", SC.crowded_world(api, oracle, inputs, NCPU))):
-        tr, base = _tracer(api, inputs, world["p"], world["bn"]), _tracer(api, inputs, world["p"], world["bn"])
-        dev = {k: torch_cuda.from_numpy(np.ascontiguousarray(world[k])).cuda() for k in ("raw", "flow", "shifted", "state")}
-        out[name] = dict(world, name=name, tr=tr, base=base, dev=dev)
+    out = D.device_worlds(api, oracle, inputs, torch_cuda, NCPU)
     yield out
-    for w in out.values():
-        w["tr"].close()
-        w["base"].close()
-
-
-def _tables(api, torch, w, which):
-    """The table set-ups of the tests as (flow, state) device tensors or None: "none"; "flow" the sphere's own table handed in
-    as a caller's; "uniform" flow plus a state table holding the scalars everywhere; "three" flow plus the three-state
-    pattern with kz = 1; "tabled" the reference's: the offset target's flow plus the three-state pattern."""
-    dev = w["dev"]
-    if which == "none":
-        return None, None
-    if which == "flow":
-        return dev["flow"], None
-    if which == "uniform":
-        _, cs, gc = api.gain_constants(w["p"], w["gp"])
-        uni = torch.empty_like(dev["state"])
-        uni[0], uni[1] = cs, gc
-        return dev["flow"], uni
-    return (dev["shifted"] if which == "tabled" else dev["flow"]), dev["state"]
-
-
-def _select(tr, flow, state):
-    tr.set_flow(flow)
-    tr.set_gain_state(state)
-
-
-def _update(torch, tr, raw, gp, pair_once, frozen=False, x=(0, None), change=True):
-    """One gain update from a zero gain on a copy of the device fields `raw`: (fields, gain, change)."""
-    f = raw.clone()
-    k = tr.new_grid(per_beam=True)
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda") if change else None
-    tr.gain_field(f, k, gp, ch, pair_once=pair_once, frozen=frozen, x_lo=x[0], x_hi=x[1])
-    return f, k, ch
-
-
-def _packed(torch, api, tr, raw, gp, pair_once, slab):
-    x0, x1 = slab
-    f = raw[:, :, x0:x1].contiguous()
-    k = torch.zeros((raw.shape[1], x1 - x0) + tuple(raw.shape[3:]), dtype=torch.float64, device="cuda")
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
-    api.gain_field_packed(f, None, k, torch.empty_like(k) if pair_once else None, ch, x0, x1, tr.params, gp, tr.ctx, _stream(torch))
-    return f, k, ch
-
-
-def _all_calls(torch, api, tr, raw, gp, pair_once, slab):
-    """First call, frozen call on fresh energy, slab, packed slab: [(what, tensor)] with the change sums marked."""
-    f, k, ch = _update(torch, tr, raw, gp, pair_once)
-    f2 = f.clone()
-    f2[0] = raw[0]
-    k2 = torch.zeros_like(k)
-    ch2 = torch.zeros_like(ch)
-    tr.gain_field(f2, k2, gp, ch2, pair_once=pair_once, frozen=True)
-    fs, ks, chs = _update(torch, tr, raw, gp, pair_once, x=slab)
-    fp, kp, chp = _packed(torch, api, tr, raw, gp, pair_once, slab)
-    torch.cuda.synchronize()
-    return [("first fields", f), ("first gain", k), ("first change", ch), ("frozen fields", f2), ("frozen gain", k2),
-            ("frozen change", ch2), ("slab fields", fs), ("slab gain", ks), ("slab change", chs), ("packed fields", fp),
-            ("packed gain", kp), ("packed change", chp)]
-
-
-def _waves(tr, pair_once, x_lo, x_hi):
-    """Wavefronts of one gain launch over the planes [x_lo, x_hi) (launch_gain_field), as tests/test_gpu_gain_shapes.py counts."""
-    hy, hz = tr.grid_shape[1], tr.grid_shape[2]
-    if pair_once:
-        return (x_hi - x_lo) * hy
-    bricks = (((x_hi + 1) >> 1) - (x_lo >> 1)) * ((hy + 3) // 4) * ((hz + 7) // 8)
-    return 4 * min((bricks + 3) // 4, 256 * 64)
-
-
-def _group_errors(a, b, scale):
-    return [float(np.abs(a[..., z] - b[..., z]).max() / scale) for z in Z_GROUPS]
+    D.close_worlds(out)
 
 
 # ---- 0. the context's limit -----------------------------------------------------------------------------------------------
@@ -173,29 +84,29 @@ def test_a_limit_never_reached_and_a_limit_taken_back_change_no_bit(api, torch_c
     torch = torch_cuda
     w = worlds[grid]
     tr, base, gp, raw, slab = w["tr"], w["base"], w["gp"], w["dev"]["raw"], SLABS[grid]
-    flow, state = _tables(api, torch, w, tables)
+    flow, state = D.tables(api, torch, w, tables)
     never = 100.0 * max(SC.reference(w, k)["limits"]["never"] for k in (("restated", "tabled") if grid == "traced" else ("plain", "tabled")))
-    _select(base, flow, state)
-    _select(tr, flow, state)
+    D.select(base, flow, state)
+    D.select(tr, flow, state)
     try:
         assert base.ctx.saturation() == 0.0
-        want = _all_calls(torch, api, base, raw, gp, pair_once, slab)
+        want = D.all_calls(torch, api, base, raw, gp, pair_once, slab)
         assert float(want[1][1].abs().max()) > 1.0 and float(want[7][1].abs().max()) > 1.0
         for mode, dn in (("never", never), ("taken back", 0.0)):
             tr.set_saturation(dn)
             assert tr.ctx.saturation() == dn
-            got = _all_calls(torch, api, tr, raw, gp, pair_once, slab)
+            got = D.all_calls(torch, api, tr, raw, gp, pair_once, slab)
             for (what, a), (_, b) in zip(want, got):
                 if what.endswith("change"):
                     x = (0, tr.grid_shape[0]) if what.split()[0] in ("first", "frozen") else slab
-                    n = _waves(tr, pair_once, *x)
+                    n = D.waves(tr, pair_once, *x)
                     assert bool(torch.all((a - b).abs() <= (n - 1) * 2.0 ** -53 * a.abs())), (mode, what, a.tolist(), b.tolist())
                 else:
                     assert torch.equal(a, b), (mode, what)
     finally:
         tr.set_saturation(0.0)
-        _select(tr, None, None)
-        _select(base, None, None)
+        D.select(tr, None, None)
+        D.select(base, None, None)
 
 
 # ---- 2. clamped, against the references -----------------------------------------------------------------------------------
@@ -224,32 +135,28 @@ def test_clamped_update_matches_the_reference(api, torch_cuda, worlds, grid, whi
     tr, gp, raw, slab = w["tr"], w["gp"], w["dev"]["raw"], SLABS[grid]
     K0, want, dn = _reference(w, which, name)
     scale = float(np.abs(K0).max())
-    _select(tr, *_tables(api, torch, w, "tabled" if which == "tabled" else "none"))
+    D.select(tr, *D.tables(api, torch, w, "tabled" if which == "tabled" else "none"))
     tr.set_saturation(dn)
     try:
         got = {}
         for pair_once in KERNELS:
-            f, k, ch = _update(torch, tr, raw, gp, pair_once)
-            f2 = f.clone()
-            f2[0] = raw[0]
-            k2 = torch.zeros_like(k)
-            tr.gain_field(f2, k2, gp, None, pair_once=pair_once, frozen=True)
+            f, k, ch, _, k2, _ = D.first_and_frozen(torch, tr, raw, gp, pair_once)
             parts, fields = tr.new_grid(per_beam=True), raw.clone()
             for x0, x1 in zip(CUTS[grid][:-1], CUTS[grid][1:]):
                 tr.gain_field(fields, parts, gp, None, pair_once=pair_once, x_lo=x0, x_hi=x1)
-            _, kp, _ = _packed(torch, api, tr, raw, gp, pair_once, slab)
+            _, kp, _ = D.packed(torch, api, tr, raw, gp, pair_once, slab)
             got[pair_once] = dict(first=k.cpu().numpy(), frozen=k2.cpu().numpy(), slabs=parts.cpu().numpy(), packed=kp.cpu().numpy(),
                                   change=ch.cpu().numpy(), fields=torch.equal(fields, f))
     finally:
         tr.set_saturation(0.0)
-        _select(tr, None, None)
+        D.select(tr, None, None)
     x0, x1 = slab
     for pair_once in KERNELS:
         g = got[pair_once]
         label = "%s %s %s %s" % (grid, which, name, "pair-once" if pair_once else "ordered")
         errs = {k: float(np.abs(g[k] - want).max() / scale) for k in ("first", "frozen", "slabs")}
         errs["packed"] = float(np.abs(g["packed"] - want[:, x0:x1]).max() / scale)
-        moved = _group_errors(g["first"], K0, scale)
+        moved = D.group_errors(g["first"], K0, scale)
         print("%s (dn_max %.4e, max |K| %.3e): against the reference %s; moved from the unclamped K by z group %s; sum |K| %.3e of the reference's"
               % (label, dn, scale, {k: "%.2e" % v for k, v in errs.items()}, ["%.2e" % m for m in moved],
                  abs(g["change"][1] / np.abs(want).sum() - 1.0)))
@@ -264,7 +171,7 @@ def test_clamped_update_matches_the_reference(api, torch_cuda, worlds, grid, whi
             assert np.array_equal(g["slabs"], g["first"]) and np.array_equal(g["packed"], g["first"][:, x0:x1])
     for k in ("first", "frozen", "slabs", "packed"):
         err = float(np.abs(got[True][k] - got[False][k]).max() / scale)
-        by_group = _group_errors(got[True][k], got[False][k], scale)
+        by_group = D.group_errors(got[True][k], got[False][k], scale)
         print("%s %s %s %s: pair-once against ordered %.3e, by z group %s" % (grid, which, name, k, err, by_group))
         assert err < LAST_BITS, (k, err)
         assert all(e < LAST_BITS for e in by_group), (k, by_group)          # each group against the WHOLE grid's max |K|
@@ -282,7 +189,7 @@ def test_exchange_cancels_per_cell_under_the_clamp(api, torch_cuda, worlds, grid
     K0, want, dn = _reference(w, which, name)
     tr.set_saturation(dn)
     try:
-        f, k, _ = _update(torch, tr, w["dev"]["raw"], w["gp"], pair_once, change=False)
+        f, k, _ = D.update(torch, tr, w["dev"]["raw"], w["gp"], pair_once, change=False)
     finally:
         tr.set_saturation(0.0)
     nf, K = f.cpu().numpy(), k.cpu().numpy()
@@ -308,12 +215,12 @@ def test_every_pair_clamped_forgets_the_intensity_scale(api, torch_cuda, worlds,
     raw16 = raw.clone()
     raw16[0] *= 16.0
     for pair_once in KERNELS:
-        _, plain, _ = _update(torch, tr, raw, gp, pair_once, change=False)
-        _, plain16, _ = _update(torch, tr, raw16, gp, pair_once, change=False)
+        _, plain, _ = D.update(torch, tr, raw, gp, pair_once, change=False)
+        _, plain16, _ = D.update(torch, tr, raw16, gp, pair_once, change=False)
         tr.set_saturation(dn)
         try:
-            _, k, _ = _update(torch, tr, raw, gp, pair_once, change=False)
-            _, k16, _ = _update(torch, tr, raw16, gp, pair_once, change=False)
+            _, k, _ = D.update(torch, tr, raw, gp, pair_once, change=False)
+            _, k16, _ = D.update(torch, tr, raw16, gp, pair_once, change=False)
         finally:
             tr.set_saturation(0.0)
         err = float((k16 - k).abs().max()) / scale
@@ -340,9 +247,9 @@ def test_amplitude_map_matches_the_reference(api, torch_cuda, worlds, grid, tabl
     w = worlds[grid]
     tr, gp, raw, slab = w["tr"], w["gp"], w["dev"]["raw"], SLABS[grid]
     ref = SC.reference(w, tables if tables == "tabled" else ("restated" if grid == "traced" else "plain"))
-    _select(tr, *_tables(api, torch, w, tables))
+    D.select(tr, *D.tables(api, torch, w, tables))
     try:
-        f, _, _ = _update(torch, tr, raw, gp, True, change=False)          # normalised fields
+        f, _, _ = D.update(torch, tr, raw, gp, True, change=False)          # normalised fields
         before = f.clone()
         amp = tr.pair_amplitude(f, gp)
         tr.set_saturation(ref["limits"]["half"])                            # the map is the unclamped amplitude
@@ -353,7 +260,7 @@ def test_amplitude_map_matches_the_reference(api, torch_cuda, worlds, grid, tabl
         torch.cuda.synchronize()
     finally:
         tr.set_saturation(0.0)
-        _select(tr, None, None)
+        D.select(tr, None, None)
     assert torch.equal(f, before)
     assert torch.equal(limited, amp)
     assert torch.equal(part[slab[0]:slab[1]], amp[slab[0]:slab[1]])
@@ -389,7 +296,7 @@ def _solves(torch, api, tr, gp):
     e = tr.new_grid()
     ws = torch.zeros(api.cbet_workspace_bytes(tr.params) // 8 + 1, dtype=torch.float64, device="cuda")
     rep = api.cbet_solve(tr.d_te, tr.d_r, tr.d_ne, e, tr.d_bbeam_norm, tr.d_beam_norm, tr.d_pow_r, tr.d_phase_r, tr.params, gp,
-                         workspace=ws, ctx=tr.ctx, stream=_stream(torch))
+                         workspace=ws, ctx=tr.ctx, stream=D.stream(torch))
     torch.cuda.synchronize()
     n = tr.params.nbeams * e.numel()
     off = (api.cbet_workspace_gain(tr.params, ws) - ws.data_ptr()) // 8
@@ -415,7 +322,7 @@ def test_solve_loops_honour_the_limit(api, inputs, torch_cuda):
     amplitude map changes what is absorbed, the three loops agreeing as closely as they do without a limit (x 10)."""
     torch = torch_cuda
     bn = inputs[0]
-    tr = _tracer(api, inputs, api.default_params(32, nbeams=len(SC.BEAMS)), bn[SC.BEAMS])
+    tr = D.tracer(inputs, api.default_params(32, nbeams=len(W.BEAMS)), bn[W.BEAMS])
     gp = api.default_gain_params(tolerance=1e-6, max_passes=12, relax=1.0)
     try:
         plain, fields = _solves(torch, api, tr, gp)
@@ -450,7 +357,7 @@ def test_mesh_state_solve_runs_with_a_limit(api, inputs, torch_cuda):
     """tests/test_gpu_state.py's end-to-end case (24^3, six beams, the 3-D mesh with ti and zbar, set_flow("mesh") and
     set_gain_state("mesh")) with a limit: one solve of each Python loop runs, and the limit changes its gain."""
     from helpers import state_cases as S
-    tr = _tracer(api, inputs, api.default_params(24, nbeams=len(SC.BEAMS)), inputs[0][SC.BEAMS])
+    tr = D.tracer(inputs, api.default_params(24, nbeams=len(W.BEAMS)), inputs[0][W.BEAMS])
     try:
         _, a = S.mesh3d_ions(api, dense=10.0)
         tr.set_plasma_mesh(a["r"], a["theta"], a["phi"], a["ne"], a["te"], a["u"], a["center"], ti=a["ti"], zbar=a["zbar"])

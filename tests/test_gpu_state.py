@@ -4,9 +4,9 @@ gain kernels, with and without a flow table, whole grid, slab and packed slab), 
 against the unchanged oracle run once per state, and the CBET stage end to end on a hydro mesh with ion fields.
 
 Grids: 13 x 11 x 148 with sixty synthetic crowded beams (haloed rows of 150 cells: three 64-cell state groups, the last of 22
-cells, rows that start off a 128-byte line; tests/test_gpu_gain_shapes.py's generator) and 48 x 21 x 134 with six traced
-beams.  The bounds are the project's: bit for bit where both sides execute the same IEEE statements, 1e-12 for two
-formulations of one quantity and for the pair-once kernel against the ordered one, 1e-9 of max |K| against the oracle.
+cells, rows that start off a 128-byte line: CROWDED of helpers/gain_worlds.py) and 48 x 21 x 134 with six traced beams.
+The bounds are the project's: bit for bit where both sides execute the same IEEE statements, 1e-12 for two formulations of one
+quantity and for the pair-once kernel against the ordered one, 1e-9 of max |K| against the oracle.
 
 The two convergence sums (`change`) are compared as tests/test_gpu_gain_shapes.py compares them: every wavefront adds its share
 with one fp64 atomicAdd in the order the wavefronts finish, so two launches of the SAME kernel need not agree in the last bits;
@@ -16,19 +16,20 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, parity_err
+from helpers import gain_calls as D
+from helpers import gain_worlds as W
 from helpers import mesh_cases as M
 from helpers import state_cases as S
 from helpers.device_tables import download
+from helpers.gain_worlds import BEAMS, LAST_BITS, TOL
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9                 # tests/test_gpu_cbet.py's bound, of max |K|
-LAST_BITS = 1e-12          # pair-once against ordered kernel, of max |K|
-BEAMS = [0, 16, 29, 38, 47, 55]
 BIG = (104, 101, 103)      # 1,081,912 nodes: more than the launch's 4096 x 256 threads, so the grid-stride loop turns
-SHIFT = (20e-4, 0.0, -15e-4)
-SLABS = {S.TRACED: (9, 22), S.CROWDED: (9, 15)}          # (9, 22) clipped to the crowded grid's fifteen planes
-CUTS = {S.TRACED: [0, 1, 12, 13, 29, 50], S.CROWDED: [0, 1, 12, 13, 15]}
+SHIFT = W.OFFSET
+# this module's own slab and cuts on the crowded grid: (9, 22) and the traced cuts clipped to its fifteen planes
+SLABS = {W.TRACED: W.SLABS["traced"], W.CROWDED: (9, 15)}
+CUTS = {W.TRACED: W.CUTS["traced"], W.CROWDED: [0, 1, 12, 13, 15]}
 
 
 @pytest.fixture(scope="module")
@@ -46,13 +47,7 @@ def api():
 
 
 def _tracer(api, inputs, shape, beams):
-    from cbet_raytracing_3d_amd.tracer import RayTracer
-    bn, r, ne, te = inputs
-    return RayTracer(M.params(api, shape, nbeams=len(beams)), r, ne, te, beam_norm=bn[beams])
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
+    return D.tracer(inputs, W.params(api, shape, len(beams)), inputs[0][beams], tabulate=False)
 
 
 def _state(api, tr, bits=False):
@@ -94,7 +89,7 @@ def test_angle_independent_state_equals_the_host_twin_bitwise(api, inputs, torch
     mesh = _profile_mesh(api, inputs, (1, 1) if angles == "1d" else (5, 7), M.OFFSET if centre == "offset" else (0.0, 0.0, 0.0))
     gp = api.default_gain_params()
     try:
-        api.tabulate_mesh_state(tr.ctx, tr.params, gp, mesh.to(tr.device), _stream(torch_cuda), ions=ions)
+        api.tabulate_mesh_state(tr.ctx, tr.params, gp, mesh.to(tr.device), D.stream(torch_cuda), ions=ions)
         got = _state(api, tr)
     finally:
         tr.ctx.set_state(None)
@@ -112,7 +107,7 @@ def test_3d_mesh_state_agrees_with_the_host_twin(api, torch_cuda, table_tracer):
     mesh, a = S.mesh3d_ions(api)
     gp = api.default_gain_params()
     try:
-        api.tabulate_mesh_state(tr.ctx, tr.params, gp, mesh.to(tr.device), _stream(torch_cuda))
+        api.tabulate_mesh_state(tr.ctx, tr.params, gp, mesh.to(tr.device), D.stream(torch_cuda))
         got = _state(api, tr)
     finally:
         tr.ctx.set_state(None)
@@ -138,11 +133,11 @@ def test_second_and_replayed_calls_give_the_same_bits(api, inputs, torch_cuda):
     dmesh = mesh.to(tr.device)
     junk = np.full(2 * n ** 3, -3.0)
     assert tr.ctx.state() is None
-    api.tabulate_mesh_state(tr.ctx, p, gp, dmesh, _stream(torch))
+    api.tabulate_mesh_state(tr.ctx, p, gp, dmesh, D.stream(torch))
     addr = tr.ctx.state()
     eager = _state(api, tr, bits=True)
     api.moveToAndFromGPU(addr, junk, junk.nbytes, tr.gpu)
-    api.tabulate_mesh_state(tr.ctx, p, gp, dmesh, _stream(torch))
+    api.tabulate_mesh_state(tr.ctx, p, gp, dmesh, D.stream(torch))
     assert tr.ctx.state() == addr and np.array_equal(_state(api, tr, bits=True), eager)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -160,81 +155,30 @@ def test_second_and_replayed_calls_give_the_same_bits(api, inputs, torch_cuda):
     tr.close()
 
 
-# ---- the gain updates' plumbing (tests/test_gpu_gain_shapes.py's) ---------------------------------------------------------------
-def _update(torch, tr, raw, gp, pair_once, frozen=False, x=(0, None)):
-    """One gain update from a zero gain on a copy of the device fields `raw`: (fields, gain, change)."""
-    f = raw.clone()
-    k = tr.new_grid(per_beam=True)
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
-    tr.gain_field(f, k, gp, ch, pair_once=pair_once, frozen=frozen, x_lo=x[0], x_hi=x[1])
-    return f, k, ch
-
-
-def _first_and_frozen(torch, tr, raw, gp, pair_once):
-    """A first call, then a frozen call on fresh energy over the k entries of the first: f, k, change, f2, k2, change2."""
-    f, k, ch = _update(torch, tr, raw, gp, pair_once)
-    f2 = f.clone()
-    f2[0] = raw[0]
-    k2 = torch.zeros_like(k)
-    ch2 = torch.zeros_like(ch)
-    tr.gain_field(f2, k2, gp, ch2, pair_once=pair_once, frozen=True)
-    return f, k, ch, f2, k2, ch2
-
-
-def _packed(torch, api, tr, raw, gp, pair_once, slab):
-    x0, x1 = slab
-    f = raw[:, :, x0:x1].contiguous()
-    k = torch.zeros((raw.shape[1], x1 - x0) + tuple(raw.shape[3:]), dtype=torch.float64, device="cuda")
-    ch = torch.zeros(2, dtype=torch.float64, device="cuda")
-    api.gain_field_packed(f, None, k, torch.empty_like(k) if pair_once else None, ch, x0, x1, tr.params, gp, tr.ctx, _stream(torch))
-    return f, k, ch
-
-
-def _waves(tr, pair_once, x_lo, x_hi):
-    """Wavefronts of one gain launch over the planes [x_lo, x_hi) (launch_gain_field)."""
-    hy, hz = tr.grid_shape[1], tr.grid_shape[2]
-    if pair_once:
-        return (x_hi - x_lo) * hy
-    bricks = (((x_hi + 1) >> 1) - (x_lo >> 1)) * ((hy + 3) // 4) * ((hz + 7) // 8)
-    return 4 * min((bricks + 3) // 4, 256 * 64)
-
-
-def _group_errors(a, b, scale):
-    return [float(np.abs(a[..., z] - b[..., z]).max() / scale) for z in S.Z_GROUPS]
-
-
+# ---- the gain updates: helpers/gain_calls.py on the CPU side of helpers/gain_worlds.py ----------------------------------------
 @pytest.fixture(scope="module")
 def crowded(api, oracle, inputs, torch_cuda):
-    """13 x 11 x 148, sixty beams, the crowded synthetic fields, with the preconditions of
-    test_crowded_long_rows_match_the_oracle: all three run classes beyond the first 64 cells, super-critical nodes."""
-    bn, r, ne, te = inputs
-    tr = _tracer(api, inputs, S.CROWDED, list(range(60)))
+    """13 x 11 x 148, sixty beams, the crowded synthetic fields of W.crowded_world, whose builder asserts the preconditions:
+    all three run classes beyond the first 64 cells, super-critical nodes, rows that start off a 128-byte line."""
+    w = W.crowded_world(api, oracle, inputs, NCPU)
+    tr = _tracer(api, inputs, W.CROWDED, list(range(60)))
     tr.tabulate()
     assert tr.grid_shape == (15, 13, 150)
-    raw, present = S.crowded_fields((60,) + tr.grid_shape)
-    assert (raw[0] < 0).any() and (raw[0] == 0).any()
-    windows = np.stack([present[..., z0:z0 + 16].any(-1).sum(0) for z0 in range(64, tr.grid_shape[2], 16)])
-    classes = [int((windows <= 20).sum()), int(((windows > 20) & (windows <= 40)).sum()), int((windows > 40).sum())]
-    assert min(classes) >= 50, classes           # whole runs, halves and quarters, all beyond the first 64 cells
-    cfg = oracle.default_config(S.CROWDED[0], nbeams=60, ny=S.CROWDED[1], nz=S.CROWDED[2])
-    ne3d, _ = oracle.node_tables(cfg, r, ne, te)
-    assert (ne3d >= tr.derived.ncrit).any()      # the eps <= 0 arm runs
-    assert tr.grid_shape[2] % 16 != 0            # rows of 150 doubles: most start off a 128-byte line
-    yield dict(tr=tr, raw=torch_cuda.from_numpy(raw).cuda(), raw_host=raw, cfg=cfg, ne3d=ne3d, shape=S.CROWDED)
+    yield dict(tr=tr, raw=torch_cuda.from_numpy(w["raw"]).cuda(), raw_host=w["raw"], cfg=w["cfg"], ne3d=w["ne3d"], shape=W.CROWDED)
     tr.close()
 
 
 @pytest.fixture(scope="module")
 def traced(api, inputs, torch_cuda):
     """48 x 21 x 134, six beams, the device's own traced fields."""
-    tr = _tracer(api, inputs, S.TRACED, BEAMS)
+    tr = _tracer(api, inputs, W.TRACED, BEAMS)
     tr.tabulate()
     raw = tr.new_fields()
     tr.launch_cbet(raw, api.default_gain_params(), fields=True)
     torch_cuda.cuda.synchronize()
     assert tr.grid_shape == (50, 23, 136) and float(raw[0].max()) > 0
     assert int((raw[0][..., 64:] > 0).sum()) >= 10000                           # most of it beyond the first 64-cell group
-    yield dict(tr=tr, raw=raw, shape=S.TRACED)
+    yield dict(tr=tr, raw=raw, shape=W.TRACED)
     tr.close()
 
 
@@ -256,17 +200,14 @@ def test_uniform_table_changes_no_bit(request, api, torch_cuda, grid, flow, pair
     table[0], table[1] = cs, gc
 
     def calls():
-        out = list(_first_and_frozen(torch, tr, raw, gp, pair_once)) + list(_update(torch, tr, raw, gp, pair_once, x=slab)) + \
-            list(_packed(torch, api, tr, raw, gp, pair_once, slab))
-        torch.cuda.synchronize()
-        return out
+        return [t for _, t in D.all_calls(torch, api, tr, raw, gp, pair_once, slab)]
 
     names = ["fields", "gain", "change", "frozen fields", "frozen gain", "frozen change", "slab fields", "slab gain",
              "slab change", "packed fields", "packed gain", "packed change"]
-    waves = [_waves(tr, pair_once, 0, tr.grid_shape[0])] * 6 + [_waves(tr, pair_once, *slab)] * 6
+    waves = [D.waves(tr, pair_once, 0, tr.grid_shape[0])] * 6 + [D.waves(tr, pair_once, *slab)] * 6
     try:
         if flow:
-            api.tabulate_flow(tr.ctx, tr.params, gp, api.Target(SHIFT), _stream(torch))
+            api.tabulate_flow(tr.ctx, tr.params, gp, api.Target(SHIFT), D.stream(torch))
         assert tr.ctx.state() is None and (tr.ctx.flow() is not None) == flow
         plain = calls()
         tr.set_gain_state(table)
@@ -292,31 +233,31 @@ def per_state(api, oracle, crowded):
     that state's sound speed, and the oracle's gain of the crowded fields -- each computed once."""
     tr = crowded["tr"]
     out = []
-    for st in S.STATES:
+    for st in W.STATES:
         gp = api.default_gain_params(relax=1.0, **st)
         _, cs, gc = api.gain_constants(tr.params, gp)
         want, _ = oracle.gain_field(crowded["cfg"], oracle.gain_default(**st), crowded["raw_host"], crowded["ne3d"], relax=1.0,
                                     nthreads=NCPU)
         out.append(dict(cs=cs, gc=gc, flow=api.flow_table(tr.params, gp), want=want))
-    assert max(s["te_ev"] for s in S.STATES) >= 4 * min(s["te_ev"] for s in S.STATES)
+    assert max(s["te_ev"] for s in W.STATES) >= 4 * min(s["te_ev"] for s in W.STATES)
     return out
 
 
 @pytest.fixture(scope="module", params=[3, 1], ids=["i+2j+3k", "i+2j+k"])
 def varying(request, api, torch_cuda, crowded, per_state):
     """The caller's state and flow tables composed node by node, and the reference composed cell by cell, for one node
-    pattern (helpers/state_cases.node_pattern: 3 as the request words it, 1 the cell-to-cell change along z it describes)."""
+    pattern (helpers/gain_worlds.node_pattern: 3 as the request words it, 1 the cell-to-cell change along z it describes)."""
     torch = torch_cuda
     kz = request.param
-    nodes, cells = S.node_pattern(S.CROWDED, kz), S.cell_pattern(S.CROWDED, kz)
+    nodes, cells = W.node_pattern(W.CROWDED, kz), W.cell_pattern(W.CROWDED, kz)
     if kz == 1:                                  # the state changes from cell to cell along z: in every run, in every group
         assert np.all(cells[:, :, 1:-2] != cells[:, :, 2:-1])
-    assert all((cells[..., z] == s).any() for z in S.Z_GROUPS for s in range(3))
+    assert all((cells[..., z] == s).any() for z in W.Z_GROUPS for s in range(3))
     state = np.stack([np.choose(nodes, [s["cs"] for s in per_state]), np.choose(nodes, [s["gc"] for s in per_state])])
     flow = np.choose(nodes[None], [s["flow"] for s in per_state])
     want = np.choose(cells[None], [s["want"] for s in per_state])
     scale = float(np.abs(want).max())
-    assert scale > 1.0 and all(np.abs(want[..., z]).max() > 1e-3 * scale for z in S.Z_GROUPS)
+    assert scale > 1.0 and all(np.abs(want[..., z]).max() > 1e-3 * scale for z in W.Z_GROUPS)
     # a kernel that ignores the table, or reads it at another node, cannot pass: the states' gains differ far beyond the bounds
     assert min(np.abs(a["want"] - b["want"]).max() for a in per_state for b in per_state if a is not b) > 1e-2 * scale
     tr = crowded["tr"]
@@ -332,17 +273,17 @@ def test_varying_table_matches_the_oracle_per_state(torch_cuda, crowded, varying
     whole grid and per 64-cell z group, first call and frozen."""
     torch = torch_cuda
     tr, raw, want, scale, gp = crowded["tr"], crowded["raw"], varying["want"], varying["scale"], varying["gp"]
-    f_o, k_o, ch_o, f2_o, k2_o, _ = [t.cpu().numpy() for t in _first_and_frozen(torch, tr, raw, gp, False)]
-    f_p, k_p, ch_p, f2_p, k2_p, _ = [t.cpu().numpy() for t in _first_and_frozen(torch, tr, raw, gp, True)]
+    f_o, k_o, ch_o, f2_o, k2_o, _ = [t.cpu().numpy() for t in D.first_and_frozen(torch, tr, raw, gp, False, change2=True)]
+    f_p, k_p, ch_p, f2_p, k2_p, _ = [t.cpu().numpy() for t in D.first_and_frozen(torch, tr, raw, gp, True, change2=True)]
     err_o, err_p = float(np.abs(k_o - want).max() / scale), float(np.abs(k_p - want).max() / scale)
-    by_group, by_group_oracle = _group_errors(k_p, k_o, scale), _group_errors(k_p, want, scale)
+    by_group, by_group_oracle = D.group_errors(k_p, k_o, scale), D.group_errors(k_p, want, scale)
     print("13x11x148 varying state (max |K| %.3e): ordered vs oracle %.3e, pair-once vs oracle %.3e (by z group %s), pair-once "
           "vs ordered by z group %s, frozen vs first %.3e / %.3e" % (scale, err_o, err_p, by_group_oracle, by_group,
                                                                      np.abs(k2_o - k_o).max() / scale, np.abs(k2_p - k_o).max() / scale))
     assert np.array_equal(k_o, want)                                    # the oracle's operations in the oracle's order
     assert err_p < TOL
     assert np.abs(k_p - k_o).max() < LAST_BITS * scale
-    for z, e, eo in zip(S.Z_GROUPS, by_group, by_group_oracle):
+    for z, e, eo in zip(W.Z_GROUPS, by_group, by_group_oracle):
         assert e < LAST_BITS, (z, e)
         assert eo < TOL, (z, eo)
         assert np.array_equal(k_o[..., z], want[..., z]), z
@@ -365,16 +306,16 @@ def test_varying_table_by_slabs_and_packed(api, torch_cuda, crowded, varying):
     tr.gain_field(raw.clone(), ref, gp, None, pair_once=False)
     parts = tr.new_grid(per_beam=True).fill_(-7.0)
     fields = raw.clone()
-    cuts = CUTS[S.CROWDED]
+    cuts = CUTS[W.CROWDED]
     for x0, x1 in zip(cuts[:-1], cuts[1:]):
         before = parts.clone()
         tr.gain_field(fields, parts, gp, None, pair_once=False, x_lo=x0, x_hi=x1)
         assert torch.equal(parts[:, :x0], before[:, :x0]) and torch.equal(parts[:, x1:], before[:, x1:])
     assert torch.equal(parts, ref)
-    x0, x1 = SLABS[S.CROWDED]
+    x0, x1 = SLABS[W.CROWDED]
     for pair_once in (False, True):
-        f_ref, k_ref, _ = _update(torch, tr, raw, gp, pair_once, x=(x0, x1))
-        f_pk, k_pk, _ = _packed(torch, api, tr, raw, gp, pair_once, (x0, x1))
+        f_ref, k_ref, _ = D.update(torch, tr, raw, gp, pair_once, x=(x0, x1))
+        f_pk, k_pk, _ = D.packed(torch, api, tr, raw, gp, pair_once, (x0, x1))
         err = float((k_pk - k_ref[:, x0:x1]).abs().max()) / scale
         print("13x11x148 varying state, packed slab [%d, %d), %s: max |K packed - K whole| / max |K| = %.3e" %
               (x0, x1, "pair-once" if pair_once else "ordered", err))
@@ -398,9 +339,7 @@ def test_cbet_stage_on_the_mesh_state(api, inputs, torch_cuda):
     args = (a["r"], a["theta"], a["phi"], a["ne"], a["te"], a["u"], a["center"])
 
     def update(fields, pair_once=True):
-        f, k = fields.clone(), tr.new_grid(per_beam=True)
-        tr.gain_field(f, k, gp, pair_once=pair_once)
-        return f, k
+        return D.update(torch, tr, fields, gp, pair_once, change=False)[:2]
 
     try:
         # the scalar path on the profiles, for the end
@@ -466,7 +405,7 @@ def test_cbet_stage_on_the_mesh_state(api, inputs, torch_cuda):
         tr.ctx.set_flow(None)                                           # (so that the state is what it objects to)
         with pytest.raises(api.CbetError) as ei:
             api.cbet_solve(tr.d_te, tr.d_r, tr.d_ne, tr.new_grid(), tr.d_bbeam_norm, tr.d_beam_norm, tr.d_pow_r, tr.d_phase_r,
-                           tr.params, api.default_gain_params(max_passes=1), ctx=tr.ctx, stream=_stream(torch))
+                           tr.params, api.default_gain_params(max_passes=1), ctx=tr.ctx, stream=D.stream(torch))
         assert ei.value.code == api.EINVAL and "state" in str(ei.value)
         # the mesh gone, the scalar path's bits are back
         tr.set_plasma_mesh(None)
@@ -475,7 +414,7 @@ def test_cbet_stage_on_the_mesh_state(api, inputs, torch_cuda):
         f_again, k_again = update(plain_fields)
         assert torch.equal(k_again, k_plain) and torch.equal(f_again, f_plain)
         api.cbet_solve(tr.d_te, tr.d_r, tr.d_ne, tr.new_grid(), tr.d_bbeam_norm, tr.d_beam_norm, tr.d_pow_r, tr.d_phase_r,
-                       tr.params, api.default_gain_params(max_passes=1), ctx=tr.ctx, stream=_stream(torch))    # and the native loop runs
+                       tr.params, api.default_gain_params(max_passes=1), ctx=tr.ctx, stream=D.stream(torch))    # and the native loop runs
         torch.cuda.synchronize()
     finally:
         tr.close()

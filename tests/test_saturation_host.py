@@ -1,6 +1,6 @@
 """Saturation of the ion-acoustic wave in the gain kernels, the part that needs no device: the new
 entries of the C ABI are exported, declared and refuse bad arguments, and the two CPU references of
-tests/test_gpu_saturation.py (helpers/saturation_cases.py) agree with the oracle and with each other before any kernel is
+tests/test_gpu_saturation.py (helpers/gain_reference.py, with the limits of helpers/saturation_cases.py) agree with the oracle and with each other before any kernel is
 measured against them.  A context cannot be created without a device: the setter's round trip is in the GPU tests."""
 import ctypes as C
 import math
@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 from conftest import NCPU, ROOT
+from helpers import gain_worlds as W
 from helpers import saturation_cases as SC
-
-LAST_BITS = 1e-12          # of max |K|: two CPU formulations of the same update
+from helpers.gain_worlds import LAST_BITS         # here of max |K|: two CPU formulations of the same update
 
 
 @pytest.fixture(scope="module")
@@ -26,12 +26,12 @@ def api():
 
 @pytest.fixture(scope="module")
 def traced(api, oracle, inputs):
-    return SC.traced_world(api, oracle, inputs, NCPU)
+    return W.traced_world(api, oracle, inputs, NCPU)
 
 
 @pytest.fixture(scope="module")
 def crowded(api, oracle, inputs):
-    return SC.crowded_world(api, oracle, inputs, NCPU)
+    return W.crowded_world(api, oracle, inputs, NCPU)
 
 
 def _error(api):
