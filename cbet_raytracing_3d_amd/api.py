@@ -366,15 +366,16 @@ EXPORTS = [
     "cbet_context_set_saturation", "cbet_context_saturation", "cbet_pair_amplitude",
     "cbet_exchange_matrix_work_bytes", "cbet_exchange_matrix", "cbet_exchange_matrix_host",
     "cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted",
+    "cbet_context_set_polarization", "cbet_context_polarization", "cbet_exchange_matrix_host_polarized",
 ]
 
 _lib = None
 
 
 def lib(tolerate=()):
-    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning entries that an
-    OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack; such a build must then
-    not be asked for shifts."""
+    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning and polarization
+    entries that an OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack; such a
+    build must then not be asked for shifts or for a polarization mode."""
     global _lib
     if _lib is not None:
         return _lib
@@ -483,7 +484,9 @@ def lib(tolerate=()):
     L.cbet_exchange_matrix_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp,
                                             C.c_double]
     detuning = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
-                "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp]}
+                "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp],
+                "cbet_context_set_polarization": [vp, C.c_int], "cbet_context_polarization": [vp, ip],
+                "cbet_exchange_matrix_host_polarized": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int]}
     absent = [name for name in detuning if name in tolerate and not hasattr(L, name)]
     for name, types in detuning.items():
         if name not in absent:
@@ -716,6 +719,18 @@ class Context:
         _check(lib().cbet_context_detuning(self._h, _dptr(out), C.byref(n)))
         return out[:n.value].copy() if n.value else None
 
+    def set_polarization(self, mode):
+        """cbet_context_set_polarization: "aligned" (every beam pair polarized alike, the default) or "smoothed" (every beam
+        an equal incoherent mix of two orthogonal polarizations: each pair's gain times (1 + cos^2 theta) / 4, theta the
+        pair's crossing angle in the cell), or the CBET_POL_* integer.  An unknown mode raises and changes nothing."""
+        _check(lib().cbet_context_set_polarization(self._h, polarization_mode(mode)))
+
+    def polarization(self):
+        """The mode in use (cbet_context_polarization): "aligned" or "smoothed"."""
+        mode = C.c_int()
+        _check(lib().cbet_context_polarization(self._h, C.byref(mode)))
+        return POLARIZATIONS[mode.value]
+
     def close(self):
         if self._h:
             lib().cbet_context_destroy(self._h)
@@ -925,6 +940,20 @@ def exchange_matrix(fields, ne3d, out, gross, work, hx_lo, hx_hi, params, gain_p
                                       C.byref(params), C.byref(gain_params), ctx.handle if ctx is not None else None, _addr(stream)))
 
 
+POL_ALIGNED, POL_SMOOTHED = 0, 1                # CBET_POL_* of the header
+POLARIZATIONS = ("aligned", "smoothed")
+
+
+def polarization_mode(mode):
+    """A polarization mode by name ("aligned", "smoothed") as the header's CBET_POL_* integer; an integer passes as it is (the
+    library judges it)."""
+    if isinstance(mode, str):
+        if mode not in POLARIZATIONS:
+            raise ValueError("polarization is one of %s, got %r" % (", ".join(repr(m) for m in POLARIZATIONS), mode))
+        return POLARIZATIONS.index(mode)
+    return int(mode)
+
+
 def wavelength_shift_to_domega(params, dlambda_angstrom):
     """Wavelength shifts (Angstrom, scalar or array; > 0 = red) of the nominal wavelength l0 = 2 pi c / omega of `params` as
     angular-frequency shifts in rad/s: omega l0 / (l0 + dl) - omega, not its first-order form."""
@@ -935,11 +964,12 @@ def wavelength_shift_to_domega(params, dlambda_angstrom):
 
 
 def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=None, dn_max=0.0, hx_lo=0, hx_hi=None, out=None,
-                         gross=None, shift=None):
+                         gross=None, shift=None, polarization="aligned"):
     """cbet_exchange_matrix_host, the host twin: numpy (T, Gross), each (nbeams, nbeams), of normalised HOST fields
     [4, nbeams, nx + 2, ny + 2, nz + 2] over the planes [hx_lo, hx_hi).  ne3d (nx, ny, nz); flow (3, nx, ny, nz) or None = the
     closed-form ramp; state (2, nx, ny, nz) or None = the scalars; dn_max 0 = no limit; shift (nbeams,) per-beam frequency
-    shifts in rad/s or None (cbet_exchange_matrix_host_shifted).  out / gross: arrays to ADD into (default: new zeroed ones)."""
+    shifts in rad/s or None; polarization "aligned" or "smoothed" (cbet_exchange_matrix_host_polarized).  out / gross: arrays
+    to ADD into (default: new zeroed ones)."""
     nb = params.nbeams
     host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
     fields, ne3d, flow, state, shift = host(fields), host(ne3d), host(flow), host(state), host(shift)
@@ -947,9 +977,10 @@ def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=Non
         raise ValueError("shift holds one value per beam: shape (%d,), got %r" % (nb, shift.shape))
     out = np.zeros((nb, nb)) if out is None else out
     gross = np.zeros((nb, nb)) if gross is None else gross
-    _check(lib().cbet_exchange_matrix_host_shifted(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
-                                                   params.nx + 2 if hx_hi is None else hx_hi, C.byref(params), C.byref(gain_params),
-                                                   _addr(flow), _addr(state), dn_max, _addr(shift)))
+    pol = polarization_mode(polarization)
+    _check(lib().cbet_exchange_matrix_host_polarized(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
+                                                     params.nx + 2 if hx_hi is None else hx_hi, C.byref(params),
+                                                     C.byref(gain_params), _addr(flow), _addr(state), dn_max, _addr(shift), pol))
     return out, gross
 
 

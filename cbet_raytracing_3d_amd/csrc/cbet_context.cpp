@@ -346,4 +346,21 @@ int cbet_context_detuning(cbet_context *ctx, double *out, int *nbeams)
     return CBET_OK;
 }
 
+int cbet_context_set_polarization(cbet_context *ctx, int mode)
+{
+    if (mode != CBET_POL_ALIGNED && mode != CBET_POL_SMOOTHED)
+        return fail(CBET_EINVAL, "cbet_context_set_polarization: mode = %d is unknown (CBET_POL_ALIGNED = %d or CBET_POL_SMOOTHED = %d)",
+                    mode, CBET_POL_ALIGNED, CBET_POL_SMOOTHED);
+    if (!ctx) return fail(CBET_EINVAL, "cbet_context_set_polarization: NULL context");
+    ctx->pol = mode;
+    return CBET_OK;
+}
+
+int cbet_context_polarization(cbet_context *ctx, int *mode)
+{
+    if (!ctx || !mode) return fail(CBET_EINVAL, "NULL context/mode");
+    *mode = ctx->pol;
+    return CBET_OK;
+}
+
 }  // extern "C"

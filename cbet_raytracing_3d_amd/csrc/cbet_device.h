@@ -129,6 +129,7 @@ struct GainArgs {
     const double *state;                    // [2][nx*ny*nz] node state table (cs, gain_const; cbet_tabulate_mesh_state), or NULL: the scalars cs / gain_const above
     double sat;                             // limit dn_max of the ion-acoustic amplitude a pair's gain corresponds to (cbet_context_set_saturation), 0 = none
     const double *shift;                    // [CBET_MAX_CBET_BEAMS] per-beam angular-frequency shifts, rad/s (cbet_context_set_detuning; entries past nbeams are 0), or NULL: one colour
+    int pol;                                // CBET_POL_*: 0 = every pair polarized alike; 1 = polarization smoothing, every pair gain times (1 + cos^2 theta) / 4 (cbet_context_set_polarization)
 };
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);

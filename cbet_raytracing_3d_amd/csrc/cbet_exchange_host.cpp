@@ -4,7 +4,8 @@
 // pair_clamp), on an argument block filled by the kernels' own builder (gain_args) -- one IEEE operation per written
 // operator, the library is built with -ffp-contract=off -- with every pair's two sums compensated (Neumaier).
 // No HIP call: it is the reference of the device path at any size.  cbet_exchange_matrix_host_shifted is the twin with per-beam
-// frequency shifts; the argument builder the kernels and the twin share (gain_args) lives here too.
+// frequency shifts, cbet_exchange_matrix_host_polarized the one with a polarization mode on top (section
+// 20): the loop itself; the argument builder the kernels and the twin share (gain_args) lives here too.
 #include <cmath>
 #include <vector>
 
@@ -30,7 +31,7 @@ inline void add_compensated(double &sum, double &comp, double x)
 // here, beside the twin, so that the twin links without the HIP runtime.
 cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
                                const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                               const double *shift, int hx_lo, int hx_hi, bool packed)
+                               const double *shift, int pol, int hx_lo, int hx_hi, bool packed)
 {
     GainArgs a{};
     grid_args(a, p, d);
@@ -38,7 +39,7 @@ cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, cons
     a.ncrit = d.ncrit; a.k0 = d.omega / kC;
     ramp_args(a, g, cs);
     a.gain_const = gc; a.iaw = g->iaw; a.relax = g->relax;
-    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat; a.shift = shift;
+    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat; a.shift = shift; a.pol = pol;
     a.hx_lo = hx_lo; a.hx_hi = hx_hi;
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
     a.store0 = packed ? (long)hx_lo * plane : 0;
@@ -60,13 +61,25 @@ extern "C" int cbet_exchange_matrix_host(const double *fields, const double *ne3
     return cbet_exchange_matrix_host_shifted(fields, ne3d, out, gross, hx_lo, hx_hi, p, g, flow, state, dn_max, nullptr);
 }
 
-// ... with per-beam frequency shifts: shift[nbeams] rad/s, or NULL.  The ordered statement with the
-// beat frequency (pair_gain's second form) wherever shift is given -- equal shifts add an exact zero to every pair.
+// ... with per-beam frequency shifts: shift[nbeams] rad/s, or NULL.
 extern "C" int cbet_exchange_matrix_host_shifted(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo,
                                                  int hx_hi, const cbet_params *p, const cbet_gain_params *g, const double *flow,
                                                  const double *state, double dn_max, const double *shift)
 {
+    return cbet_exchange_matrix_host_polarized(fields, ne3d, out, gross, hx_lo, hx_hi, p, g, flow, state, dn_max, shift, CBET_POL_ALIGNED);
+}
+
+// ... and a polarization mode: the loop.  The ordered statement with the beat frequency (pair_gain's
+// second form) wherever shift is given -- equal shifts add an exact zero to every pair -- times pair_smoothing's factor where
+// pol is CBET_POL_SMOOTHED, before the clamp.
+extern "C" int cbet_exchange_matrix_host_polarized(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo,
+                                                   int hx_hi, const cbet_params *p, const cbet_gain_params *g, const double *flow,
+                                                   const double *state, double dn_max, const double *shift, int pol)
+{
     using namespace cbet;
+    if (pol != CBET_POL_ALIGNED && pol != CBET_POL_SMOOTHED)
+        return fail(CBET_EINVAL, "cbet_exchange_matrix_host_polarized: pol = %d is unknown (CBET_POL_ALIGNED = %d or CBET_POL_SMOOTHED = %d)",
+                    pol, CBET_POL_ALIGNED, CBET_POL_SMOOTHED);
     cbet_derived d;
     if (int rc = derive_grid(p, &d)) return rc;
     if (p->nbeams > CBET_MAX_CBET_BEAMS)
@@ -86,7 +99,7 @@ extern "C" int cbet_exchange_matrix_host_shifted(const double *fields, const dou
         table[b] = shift[b];
     }
     if (nb < 2 || hx_hi == hx_lo) return CBET_OK;
-    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, shift ? table : nullptr, hx_lo, hx_hi, false);
+    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, shift ? table : nullptr, pol, hx_lo, hx_hi, false);
     const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride, total = hsize * nb;
     const double iaw2 = a.iaw * a.iaw;
@@ -105,6 +118,7 @@ extern "C" int cbet_exchange_matrix_host_shifted(const double *fields, const dou
         const double ds_node = (kC * c.rt) * a.dt;
         const double pref = cell_pref(a, c);
         const double lim = cell_sat_limit(a, c);
+        const double kmag = a.k0 * c.rt;
         for (int ia = 0; ia < n; ++ia) {
             const int bi = present[ia];
             const BeamAtCell Bi = beam_at(fI, fx, fy, fz, (long)bi * hsize);
@@ -114,6 +128,7 @@ extern "C" int cbet_exchange_matrix_host_shifted(const double *fields, const dou
                 const PairWave w = pair_wave(Bi, Bj);
                 if (!pair_present(Bi, Bj, w)) continue;
                 double gn = a.shift ? pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]) : pair_gain(c, pref, iaw2, w);
+                if (a.pol) gn = gn * pair_smoothing(Bi, Bj, kmag);
                 if (sat) gn = pair_clamp(gn, Bi.I, Bj.I, lim);
                 const double x = ((ds_node * gn) * Bi.I) * Bj.I;
                 const size_t at = (size_t)bi * nb + bj;

@@ -121,6 +121,23 @@ CBET_HD double pair_gain(const CellState &c, double pref, double iaw2, const Pai
     const double eta = ((0.0 - (w.qx * c.ux + w.qy * c.uy + w.qz * c.uz)) + dw) / (w.kiaw * c.cs + 1e-10);
     return pref * pair_resonance(eta, iaw2);
 }
+// Polarization smoothing.  Every beam is an equal, incoherent mix of two orthogonal polarizations (a
+// distributed polarization rotator on every beam); two such beams crossing at the angle theta exchange (1 + cos^2 theta) / 4
+// of what two beams polarized alike do.  In a cell a present pair has |k_i| = |k_j| = kmag = k0 sqrt(eps), the value the
+// normalisation wrote (a.k0 * c.rt), so
+//     cth = ((k_i.x k_j.x + k_i.y k_j.y) + k_i.z k_j.z) / (kmag kmag),    f = 0.25 (1.0 + cth cth),    g = (pref P(eta)) f
+// with f between 1/4 (beams at right angles) and 1/2 (parallel or opposed).  The products commute and the sum keeps its order,
+// so f is the same bits for (i, j) and (j, i): G_ji = -G_ij stays exact and a cell's exchange still cancels.  The factor
+// multiplies the gain BEFORE the clamp -- this model's choice: the clamp, pair_swing, the amplitude map and the exchange matrix
+// see f G_ij, and the ion-acoustic amplitude reported is that of the pair's total exchange, not of the s-s and p-p gratings
+// separately.  eta is untouched, so detuning composes unchanged; pair_present is unchanged (such a pair has eps > 0, so
+// kmag kmag > 0).  Left out: linearly polarized beams with per-beam polarization vectors ((e_i . e_j)^2) and the spatial offset
+// between a rotator's two sub-beams.
+CBET_HD double pair_smoothing(const BeamAtCell &bi, const BeamAtCell &bj, double kmag)
+{
+    const double cth = ((bi.kx * bj.kx + bi.ky * bj.ky) + bi.kz * bj.kz) / (kmag * kmag);
+    return 0.25 * (1.0 + cth * cth);
+}
 // The clamp: g scaled by min(1, lim / w), w = |g| sqrt(Ii Ij) (pair_swing) -- one factor for (i, j) and (j, i); a
 // pair below the limit keeps its bits.
 CBET_HD double pair_swing(double g, double Ii, double Ij) { return fabs(g) * sqrt(Ii * Ij); }

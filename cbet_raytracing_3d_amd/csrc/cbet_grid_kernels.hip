@@ -10,7 +10,8 @@
 // -- is cbet_gain_model.h's, written once for these kernels and the exchange matrix's host twin (cbet_exchange_host.cpp).  Shared
 // inside this file: brick_cell (k_gain_field, k_pair_amplitude), row_runs (k_gain_field_sym, k_exchange_matrix), pair_gain_fast
 // and saturate_fast (the two pair-once kernels), one dispatch of run-time switches onto template arguments (all four).
-// DETUNE, the last switch of all four (GainArgs.shift != NULL): per-beam frequency shifts, DESIGN.md section 19.
+// DETUNE (GainArgs.shift != NULL): per-beam frequency shifts, DESIGN.md section 19.  POL, the last switch of all four
+// (GainArgs.pol != 0): polarization smoothing, every pair gain times (1 + cos^2 theta) / 4 before the clamp, DESIGN.md section 20.
 // Built with -ffp-contract=off like the rest of the library: every statement of the ordered kernel and of the
 // normalisation is one IEEE operation in the order written, which is the order the CPU checker of the CBET stage
 // uses; the pair-once kernel's pair function (pair_gain_fast) is the exception and says so.
@@ -93,7 +94,8 @@ __device__ __forceinline__ BrickCell brick_cell(const GainArgs &a, long brick, i
 // exchange still cancels; a pair below the limit keeps its bits ((pref * P) * Ij either way).
 // DETUNE (GainArgs.shift != NULL): the pair's resonance gains the beat frequency shift[bj] - shift[bi]
 // (pair_gain's second form) -- both beams are wave-uniform, the two entries come by scalar loads.
-template <bool FLOW, bool STATE, bool SAT, bool DETUNE>
+// POL (GainArgs.pol != 0): the pair gain times pair_smoothing's (1 + cos^2 theta) / 4, before the clamp.
+template <bool FLOW, bool STATE, bool SAT, bool DETUNE, bool POL>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
     const long hsize = a.bstride;                 // entries stored per beam (the whole haloed grid, or one x-slab of it)
@@ -137,6 +139,7 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
                         double g;
                         if constexpr (DETUNE) g = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
                         else g = pair_gain(c, pref, iaw2, w);
+                        if constexpr (POL) g = g * pair_smoothing(Bi, Bj, kmag);
                         if (SAT) g = pair_clamp(g, Bi.I, Bj.I, lim);
                         acc += g * Bj.I;
                     }
@@ -160,8 +163,8 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 // of the ion-acoustic amplitude the pair's unclamped gain corresponds to, A_ij = |G_ij| sqrt(Ii Ij) / kap -- the ordered
 // kernel's statements, its bricks and its presence mask; one store per valid cell, 0 where no pair exchanges anything or the
 // plasma is not sub-critical.  w / kap grows with w, so the largest w is divided once.  Reads a.fields only; a.sat is not read.
-// DETUNE: the amplitude is that of the detuned |G_ij|.
-template <bool FLOW, bool STATE, bool DETUNE>
+// DETUNE: the amplitude is that of the detuned |G_ij|.  POL: ... of the smoothed one, f |G_ij| (section 20).
+template <bool FLOW, bool STATE, bool DETUNE, bool POL>
 __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double *__restrict__ amp)
 {
     const long hsize = a.bstride;
@@ -183,6 +186,7 @@ __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double
         }
         const double pref = cell_pref(a, c);
         const double kap = cell_kap(a, c);
+        const double kmag = a.k0 * c.rt;            // POL: |k| of every beam present in the cell, as normalise_entry wrote it
         double top = 0.0;
         unsigned long long mi = mask;
         while (mi != 0ull) {
@@ -199,6 +203,7 @@ __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double
                     double gn;
                     if constexpr (DETUNE) gn = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
                     else gn = pair_gain(c, pref, iaw2, w);
+                    if constexpr (POL) gn = gn * pair_smoothing(Bi, Bj, kmag);
                     const double sw = pair_swing(gn, Bi.I, Bj.I);
                     if (sw > top) top = sw;
                 }
@@ -271,9 +276,14 @@ __device__ __forceinline__ int run_hk(int run, int c, int sft) { return LC * run
 // DETUNE: N = -(q . u) + dw with dw = w_j - w_i, the pair's beat frequency.  Two parallel beams of
 // different colour would give N = dw over D = 1e-10; the ordered kernel does not evaluate them (pair_present), so here dw
 // counts only where q != 0: one compare and one select, and q = 0 keeps N = 0 and the exact zero.
-template <bool DETUNE = false>
+// POL: the quotient times f = (1 + cth^2) / 4.  With |k_i| = |k_j| = kmag, |q|^2 = 2 kmag^2 (1 - cth), so
+// cth = 1 - q2raw * rk with rk = 1 / (2 kmag^2), the cell's (cell_rk: 0 where the plasma is not sub-critical -- nothing is
+// present there and f = 1/2 multiplies zeros): one fma on q2raw, which is held anyway, one for f, one multiply.  An absolute
+// error of an ulp of 1 in cth is a relative one of at most two ulp in f >= 1/4.  A slot whose beam is absent from the cell holds
+// k = 0: cth = 1/2 there, a finite f on a gain that only ever multiplies that beam's I = 0.
+template <bool DETUNE = false, bool POL = false>
 __device__ __forceinline__ double pair_gain_fast(const BeamAtCell &bi, const BeamAtCell &bj, double ux, double uy, double uz,
-                                                 double cs, double iaw2, double pref_iaw2, double dw = 0.0)
+                                                 double cs, double iaw2, double pref_iaw2, double dw = 0.0, double rk = 0.0)
 {
     const double qx = bj.kx - bi.kx, qy = bj.ky - bi.ky, qz = bj.kz - bi.kz;
     const double q2raw = __builtin_fma(qz, qz, __builtin_fma(qy, qy, qx * qx));
@@ -296,7 +306,17 @@ __device__ __forceinline__ double pair_gain_fast(const BeamAtCell &bi, const Bea
     double y = __builtin_amdgcn_rcp(den);
     y = __builtin_fma(__builtin_fma(-den, y, 1.0), y, y);
     const double qt = num * y;
-    return __builtin_fma(__builtin_fma(-den, qt, num), y, qt);
+    const double gn = __builtin_fma(__builtin_fma(-den, qt, num), y, qt);
+    if constexpr (POL) {
+        const double cth = __builtin_fma(-q2raw, rk, 1.0);
+        return gn * __builtin_fma(0.25 * cth, cth, 0.25);
+    } else return gn;
+}
+// rk of pair_gain_fast's POL form for a cell with rt = sqrt(eps): 1 / (2 kmag^2), kmag = k0 rt; 0 at and above critical density
+__device__ __forceinline__ double cell_rk(double k0, double rt)
+{
+    const double kmag = k0 * rt;
+    return rt > 0.0 ? 1.0 / ((kmag + kmag) * kmag) : 0.0;
 }
 
 // The clamp of the pair-once kernel on the value pair_gain_fast returned: with w^2 = (gn Ii) (gn Ij)
@@ -347,10 +367,17 @@ __device__ __forceinline__ double uniform_f64(double v)
 // padding slots of the last tile.  In phase 2 the A tile's four shifts are the same in every lane and are moved to scalar
 // registers; the B beam's slot differs between the four lane groups, so its shift is one more LDS read beside its entry.
 // The pair function takes dw = w_B - w_A once per pair, before both of its addends: the exchange still cancels.
-template <bool FROZEN, bool FLOW, bool STATE, bool SAT, bool DETUNE>
+// POL (GainArgs.pol != 0): the pair function's POL form scales the quotient by f before saturate_fast and
+// before both addends; it needs rk = 1 / (2 kmag^2), one more per-lane value of the pair loop.  rk is formed per RUN from the
+// cell's rt (cell_rk: one division per sixteen cells and lane, nothing per pair), not kept as an eighth value of the 64-cell
+// state block: the state block's values live in registers across the whole kernel, and the listing has 5 more of the 32 POL
+// instantiations in scratch that way (DESIGN.md section 20 has both sets of figures, and those of re-deriving kmag^2 from
+// the A entry per pair).  The POL arm takes the registers back that the STATE, SAT and DETUNE arms do (LEAN, and the
+// DETUNE arm's kernel-wide invariants); the instantiations without POL keep their statements.
+template <bool FROZEN, bool FLOW, bool STATE, bool SAT, bool DETUNE, bool POL>
 __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 {
-    constexpr bool LEAN = STATE || SAT || DETUNE;
+    constexpr bool LEAN = STATE || SAT || DETUNE || POL;
     constexpr int PCH = (LEAN && !FROZEN) ? 3 : LCH, QCH = (LEAN && !FROZEN) ? 4 : LCH3;
     static_assert(5 * LCAP * LC >= 64 * (LC + 1), "the slot arrays double as the staging area of the presence masks");
     __shared__ double lds[5 * LCAP * LC];
@@ -417,8 +444,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             // the plasma state of 64 cells at a time (lane = cell), handed to the four runs they make up
             if ((ibz & 3) == 0) {
                 const int hk64 = run_hk(ibz, lane, runs.sft);
-                if constexpr (DETUNE) {
-                    // The DETUNE arm gives back the registers its pair loop takes: the kernel-wide invariants of cell_state,
+                if constexpr (DETUNE || POL) {
+                    // The DETUNE and POL arms give back the registers their pair loops take: the kernel-wide invariants of cell_state,
                     // cell_pref and cell_kap -- (mach_r1 - mach_r0), (mach_1 - mach_0), 1.0 / iaw, 0.5 * k0, hoisted into vector
                     // registers or scratch in the other instantiations -- are formed here, once per 64 cells, from operands the
                     // compiler cannot see through.  The same operations on the same values: no bit changes.
@@ -443,6 +470,7 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
             const double pref = valid ? __shfl(st_pref, from, kWave) : 0.0;
             const double cs = STATE ? __shfl(st_cs, from, kWave) : a.cs;   // the cell's own, or the uniform one (scalar registers)
             const double lim = SAT ? __shfl(st_lim, from, kWave) : 0.0;
+            const double rk = POL ? cell_rk(a.k0, rt) : 0.0;
             const bool subcritical = rt > 0.0;   // eps > 0
             const double kmag = a.k0 * rt;
             const double ds_node = (kC * rt) * a.dt;
@@ -532,7 +560,16 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             P1.I = sI[p1]; P1.kx = sX[p1]; P1.ky = sY[p1]; P1.kz = sZ[p1];
                             P2.I = sI[p2]; P2.kx = sX[p2]; P2.ky = sY[p2]; P2.kz = sZ[p2];
                             double g1, g2;
-                            if constexpr (DETUNE) {
+                            if constexpr (POL) {
+                                double d1 = 0.0, d2 = 0.0;
+                                if constexpr (DETUNE) {
+                                    const double wS = sW[LG * ta + g];
+                                    d1 = sW[LG * ta + ((g + 1) & 3)] - wS;
+                                    d2 = sW[LG * ta + ((g + 2) & 3)] - wS;
+                                }
+                                g1 = pair_gain_fast<DETUNE, true>(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2, d1, rk);
+                                g2 = g < 2 ? pair_gain_fast<DETUNE, true>(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2, d2, rk) : 0.0;
+                            } else if constexpr (DETUNE) {
                                 const double wS = sW[LG * ta + g];
                                 g1 = pair_gain_fast<true>(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2, sW[LG * ta + ((g + 1) & 3)] - wS);
                                 g2 = g < 2 ? pair_gain_fast<true>(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2, sW[LG * ta + ((g + 2) & 3)] - wS) : 0.0;
@@ -575,7 +612,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 #pragma unroll
                             for (int s_ = 0; s_ < LG; ++s_) {
                                 double gn;
-                                if constexpr (DETUNE) gn = pair_gain_fast<true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, WB - WA[s_]);
+                                if constexpr (POL) gn = pair_gain_fast<DETUNE, true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, DETUNE ? WB - WA[s_] : 0.0, rk);
+                                else if constexpr (DETUNE) gn = pair_gain_fast<true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, WB - WA[s_]);
                                 else gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
                                 if (SAT) gn = saturate_fast(gn, A[s_].I, B.I, lim);
                                 KA[s_] += gn * B.I;
@@ -667,12 +705,15 @@ __device__ __forceinline__ int tri_start(int i, int n) { return i * (2 * n - i -
 
 // DETUNE (GainArgs.shift != NULL): a lane's pair is (sBeam[sa], sBeam[sb]); it forms w_j - w_i once, in
 // front of its walk over the cells.
-template <bool FLOW, bool STATE, bool SAT, bool DETUNE>
+// POL (GainArgs.pol != 0): rk = 1 / (2 kmag^2) is an eighth row of the state block (cell_rk; 512 bytes of
+// LDS more in the POL instantiations only, 53.5 KB: still three workgroups per CU) and the pair function's POL form scales the
+// quotient before saturate_fast.
+template <bool FLOW, bool STATE, bool SAT, bool DETUNE, bool POL>
 __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, double *__restrict__ work)
 {
     __shared__ double tab[2 * XPAIRS];
     __shared__ double sI[XSTAGE], sX[XSTAGE], sY[XSTAGE], sZ[XSTAGE];
-    __shared__ double sSt[7][64];
+    __shared__ double sSt[POL ? 8 : 7][64];
     __shared__ unsigned long long sMask[XT / kWave];
     __shared__ int sBeam[CBET_MAX_CBET_BEAMS];
     const int nb = a.nbeams, npairs = nb * (nb - 1) / 2;
@@ -684,7 +725,7 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
     const double iaw2 = a.iaw * a.iaw;
     for (int t = tid; t < 2 * npairs; t += XT) tab[t] = 0.0;   // pairs this workgroup never meets leave as zeros
     __syncthreads();
-    double st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_cs = 0.0, st_pi = 0.0, st_lim = 0.0, st_ds = 0.0;
+    double st_ux = 0.0, st_uy = 0.0, st_uz = 0.0, st_cs = 0.0, st_pi = 0.0, st_lim = 0.0, st_ds = 0.0, st_rk = 0.0;
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {
         const RowRuns runs = row_runs(a, a.hx_lo + (int)(row / HY), (int)(row % HY));   // k_gain_field_sym's: cut by element index
         for (int ibz = 0; ibz < runs.count; ++ibz) {
@@ -716,6 +757,7 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
                 sSt[4][tid] = cell_pref(a, c64) * iaw2;
                 sSt[5][tid] = SAT ? cell_sat_limit(a, c64) : 0.0;
                 sSt[6][tid] = (kC * c64.rt) * a.dt;
+                if constexpr (POL) sSt[7][tid] = cell_rk(a.k0, c64.rt);
             }
             __syncthreads();                     // masks and state are in LDS; the previous run's pair loops are done
             const unsigned long long mask = sMask[0] | sMask[1] | sMask[2] | sMask[3];
@@ -728,6 +770,7 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
                 const int from = XC * (ibz & 3) + c;   // lane l of every wavefront holds the state of cell l & 15 of the run
                 st_ux = sSt[0][from]; st_uy = sSt[1][from]; st_uz = sSt[2][from]; st_cs = sSt[3][from];
                 st_pi = sSt[4][from]; st_lim = sSt[5][from]; st_ds = sSt[6][from];
+                if constexpr (POL) st_rk = sSt[7][from];
             }
             // up to 32 present beams: all sixteen cells at once; more: two halves of eight cells (fewer cells, more slots)
             const int sh = n <= 32 ? 4 : 3, lc = 1 << sh, cl = c & (lc - 1), sp = n <= 32 ? 33 : 65;
@@ -777,7 +820,8 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
                         A.I = sI[k * sp + sa]; A.kx = sX[k * sp + sa]; A.ky = sY[k * sp + sa]; A.kz = sZ[k * sp + sa];
                         B.I = sI[k * sp + sb]; B.kx = sX[k * sp + sb]; B.ky = sY[k * sp + sb]; B.kz = sZ[k * sp + sb];
                         double gn;
-                        if constexpr (DETUNE) gn = pair_gain_fast<true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw);
+                        if constexpr (POL) gn = pair_gain_fast<DETUNE, true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw, readlane_f64(st_rk, cell));
+                        else if constexpr (DETUNE) gn = pair_gain_fast<true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw);
                         else gn = pair_gain_fast(A, B, ux, uy, uz, cs, iaw2, pref_iaw2);
                         if (SAT) gn = saturate_fast(gn, A.I, B.I, readlane_f64(st_lim, cell));
                         const double x = ((ds_node * gn) * A.I) * B.I;
@@ -951,11 +995,11 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
-        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr}, [&](auto... s) {
+        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
             hipLaunchKernelGGL((k_gain_field_sym<decltype(s)::value...>), dim3((unsigned)rows), dim3(64), 0, stream, a);
         });
     } else {
-        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr}, [&](auto... s) {
+        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
             hipLaunchKernelGGL((k_gain_field<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a);
         });
     }
@@ -965,7 +1009,7 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
 hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream)
 {
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
-    dispatch({a.flow != nullptr, a.state != nullptr, a.shift != nullptr}, [&](auto... s) {
+    dispatch({a.flow != nullptr, a.state != nullptr, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
         hipLaunchKernelGGL((k_pair_amplitude<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a, amp);
     });
     return hipGetLastError();
@@ -976,7 +1020,7 @@ hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, 
     if (a.hx_hi <= a.hx_lo || a.nbeams < 2) return hipSuccess;
     // the number of workgroups follows from the slab alone, never from the device: the same partial sums everywhere
     const long groups = exchange_groups((long)(a.hx_hi - a.hx_lo) * (a.ny + 2));
-    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr}, [&](auto... s) {
+    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
         hipLaunchKernelGGL((k_exchange_matrix<decltype(s)::value...>), dim3((unsigned)groups), dim3(XT), 0, stream, a, work);
     });
     if (hipError_t e = hipGetLastError()) return e;

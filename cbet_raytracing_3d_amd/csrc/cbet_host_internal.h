@@ -39,6 +39,8 @@ struct cbet_context {
     double *shift_own = nullptr;        // the context's own [CBET_MAX_CBET_BEAMS] table, allocated by the first cbet_context_set_detuning that selects shifts
     const double *shift = nullptr;      // the table in use: shift_own, or NULL
     double shift_host[CBET_MAX_CBET_BEAMS] = {};   // what shift_own holds (cbet_context_detuning)
+    // polarization mode of the gain kernels (cbet_context_set_polarization): CBET_POL_ALIGNED = every pair polarized alike
+    int pol = CBET_POL_ALIGNED;
 };
 
 namespace cbet {
@@ -151,10 +153,10 @@ int mesh_check(const cbet_mesh *mesh, bool whole);
 // The gain kernels', k_pair_amplitude's, k_exchange_matrix's and its host twin's (cbet_exchange_host.cpp).  cs, gc: cbet_gain_constants';
 // packed: the arrays hold the slab's planes only.  gain, scratch, change, consume and frozen stay zero: the gain update sets them.
 // shift: the per-beam frequency shifts, a table of CBET_MAX_CBET_BEAMS doubles (device memory for a kernel, host memory for the
-// twin), or NULL.
+// twin), or NULL.  pol: the polarization mode, CBET_POL_*.
 GainArgs gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
                    const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                   const double *shift, int hx_lo, int hx_hi, bool packed);
+                   const double *shift, int pol, int hx_lo, int hx_hi, bool packed);
 // The slab [hx_lo, hx_hi) lies in the haloed grid; who: the entry point's name and ": " in front of the message, or "".
 int slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p);
 

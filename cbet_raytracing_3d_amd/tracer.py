@@ -113,6 +113,8 @@ class RayTracer:
         if ctx is not self.ctx and ctx.detuning_source is not own:
             ctx.set_detuning(own, self._stream())
             ctx.detuning_source = own
+        if ctx is not self.ctx:                     # ... and its polarization mode (set_polarization)
+            ctx.set_polarization(self.ctx.polarization())
 
     def _tabulate_other(self, ctx, params):
         """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False
@@ -304,6 +306,23 @@ class RayTracer:
     def detuning(self):
         """The frequency shifts in use (rad/s, one per beam; the context's own record), or None if none."""
         return self.ctx.detuning()
+
+    # ---- polarization smoothing (include/cbet_mi355x.h cbet_context_set_polarization; DESIGN.md section 20) -------------
+    def set_polarization(self, mode="aligned"):
+        """How the beams are polarized in the gain kernels.
+        "aligned" (the default): every pair of beams is polarized alike -- the pair gain is pref P(eta).
+        "smoothed": every beam is an equal, incoherent mix of two orthogonal polarizations (a distributed polarization
+        rotator on every beam, OMEGA's); the gain of every pair is scaled by (1 + cos^2 theta) / 4, theta the angle between
+        the two beams in the cell -- between 1/4 and 1/2 -- BEFORE the saturation clamp, so pair_amplitude() maps the
+        amplitude of the pair's total exchange.
+        The mode is the context's: gain_field, pair_amplitude, exchange_matrix, both loops of cbet_solve and
+        api.cbet_solve(ctx=tracer.ctx) honour it from the next launch on, and so does every context prepared for this tracer
+        later (the pipeline's).  An unknown mode raises and changes nothing."""
+        self.ctx.set_polarization(mode)
+
+    def polarization(self):
+        """The polarization mode in use ("aligned" or "smoothed"; the context's own record)."""
+        return self.ctx.polarization()
 
     def pair_amplitude(self, fields, gain_params, x_lo=0, x_hi=None, ne3d=None, out=None):
         """The largest ion-acoustic amplitude any beam pair's UNCLAMPED gain corresponds to, per cell of the planes

@@ -827,6 +827,46 @@ int cbet_exchange_matrix_host_shifted(const double *fields, const double *ne3d, 
                                       const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
                                       double dn_max, const double *shift);
 
+/* ---- polarization smoothing --------------------------------------------------------------- */
+/*
+ * How the beams are polarized in the gain stage.  CBET_POL_ALIGNED (0, a new context's default): every pair of beams is
+ * polarized alike and the pair gain is G_ij = pref P(eta_ij), as in the sections above.  CBET_POL_SMOOTHED (1): every beam is
+ * an equal, incoherent mix of two orthogonal polarizations -- a distributed polarization rotator on every beam, as on
+ * OMEGA -- and two such beams crossing at the angle theta exchange (1 + cos^2 theta) / 4 of the aligned value.  In a cell a
+ * present pair has |k_i| = |k_j| = kmag = k0 sqrt(eps), the value the normalisation wrote, and the ordered kernel runs
+ *     cth = ((k_i.x*k_j.x + k_i.y*k_j.y) + k_i.z*k_j.z) / (kmag*kmag)
+ *     f   = 0.25 * (1.0 + cth*cth)
+ *     g   = (pref * P(eta_ij)) * f
+ * -- every written operator ONE IEEE fp64 operation in the written order, no fused multiply-add -- while the pair-once
+ * kernels form cth = 1 - |k_j - k_i|^2 / (2 kmag^2) from the |q|^2 they hold (a few ulp from it).
+ * Identities: 1/4 <= f <= 1/2, exactly 1/4 for beams at right angles and 1/2 for parallel or opposed ones; f is the same bits
+ * for (i, j) and (j, i), so G_ji = -G_ij stays exact and a cell's exchange sum_i I_i K_i still cancels, with or without a
+ * saturation limit; eta is untouched, so detuning composes unchanged; which pairs are present is unchanged.
+ * The model's choice: f multiplies the gain BEFORE the saturation clamp.  The clamp, cbet_pair_amplitude and the exchange
+ * matrix see f G_ij, and the ion-acoustic amplitude reported is that of the pair's total exchange, not of the s-s and p-p
+ * gratings separately.
+ * Out of scope: linearly polarized beams with per-beam polarization vectors (the factor would be (e_i . e_j)^2), the spatial
+ * offset between a rotator's two sub-beams, and the trace kernels, which only gather K.  The mode is an int so that a later
+ * mode needs no new entry point.
+ *
+ * cbet_context_set_polarization: a SET-UP call like cbet_context_set_detuning, it applies to launches made after it (no
+ * device work, no synchronisation).  CBET_EINVAL naming the offence: a mode that is neither of the two, a NULL context; a
+ * refused call changes nothing.  Every entry that builds its gain arguments from that context honours the mode --
+ * cbet_gain_field, cbet_gain_field_slab, cbet_gain_field_packed, cbet_pair_amplitude (the amplitude is the smoothed
+ * |G_ij|'s), cbet_exchange_matrix, and cbet_cbet_solve with a caller's context; with ctx == NULL the solve runs aligned.
+ * cbet_context_polarization: *mode = the mode in use.
+ * cbet_exchange_matrix_host_polarized: cbet_exchange_matrix_host_shifted with a mode: the ordered statements above,
+ * compensated sums as there; an unknown mode is CBET_EINVAL.  cbet_exchange_matrix_host_shifted calls it with
+ * CBET_POL_ALIGNED.
+ */
+#define CBET_POL_ALIGNED 0
+#define CBET_POL_SMOOTHED 1
+int cbet_context_set_polarization(cbet_context *ctx, int mode);
+int cbet_context_polarization(cbet_context *ctx, int *mode);
+int cbet_exchange_matrix_host_polarized(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo, int hx_hi,
+                                        const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
+                                        double dn_max, const double *shift, int pol);
+
 /* ---- exit pass --------------------------------------------------------------- */
 /*
  * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
