@@ -367,15 +367,16 @@ EXPORTS = [
     "cbet_exchange_matrix_work_bytes", "cbet_exchange_matrix", "cbet_exchange_matrix_host",
     "cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted",
     "cbet_context_set_polarization", "cbet_context_polarization", "cbet_exchange_matrix_host_polarized",
+    "cbet_context_set_bandwidth", "cbet_context_bandwidth", "cbet_exchange_matrix_host_banded",
 ]
 
 _lib = None
 
 
 def lib(tolerate=()):
-    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning and polarization
-    entries that an OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack; such a
-    build must then not be asked for shifts or for a polarization mode."""
+    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning, polarization
+    and bandwidth entries that an OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack;
+    such a build must then not be asked for shifts, for a polarization mode or for a line spectrum."""
     global _lib
     if _lib is not None:
         return _lib
@@ -486,7 +487,9 @@ def lib(tolerate=()):
     detuning = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
                 "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp],
                 "cbet_context_set_polarization": [vp, C.c_int], "cbet_context_polarization": [vp, ip],
-                "cbet_exchange_matrix_host_polarized": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int]}
+                "cbet_exchange_matrix_host_polarized": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int],
+                "cbet_context_set_bandwidth": [vp, vp, vp, C.c_int, vp], "cbet_context_bandwidth": [vp, dp, dp, ip],
+                "cbet_exchange_matrix_host_banded": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int, vp, vp, C.c_int]}
     absent = [name for name in detuning if name in tolerate and not hasattr(L, name)]
     for name, types in detuning.items():
         if name not in absent:
@@ -630,6 +633,7 @@ class Context:
         self._flow_ref = None           # set_flow(): the caller's table, kept alive
         self._state_ref = None          # set_state(): likewise
         self.detuning_source = None     # set_detuning(): the array last given (its own copy), None for none
+        self.bandwidth_source = None    # set_bandwidth(): the (offsets, weights) last given (its own copies), None for none
         _check(lib().cbet_context_create(C.byref(self._h), C.byref(params), gpu))
 
     @property
@@ -718,6 +722,28 @@ class Context:
         out, n = np.zeros(MAX_CBET_BEAMS), C.c_int()
         _check(lib().cbet_context_detuning(self._h, _dptr(out), C.byref(n)))
         return out[:n.value].copy() if n.value else None
+
+    def set_bandwidth(self, domega, weights=None, stream=None):
+        """cbet_context_set_bandwidth: the gain updates of this context give EVERY beam the same line spectrum about its own
+        centre frequency: lines at the offsets domega[a] (rad/s) with the weights weights[a] > 0 (None: equal weights), at most
+        MAX_BAND_LINES of them; the library normalises the weights to sum 1.  None, one line, or offsets that are all equal =
+        none, the default.  A set-up call: it synchronises `stream` and copies synchronously.  A NaN or infinite offset, a weight
+        that is not finite and > 0 or too many lines raise and change nothing.  A RayTracer's own context is where the tracer's
+        spectrum lives, as its shifts do (set_detuning)."""
+        if domega is None:
+            _check(lib().cbet_context_set_bandwidth(self._h, None, None, 0, _addr(stream)))
+            self.bandwidth_source = None
+            return
+        off, wts = line_arrays(domega, weights)
+        _check(lib().cbet_context_set_bandwidth(self._h, off.ctypes.data, wts.ctypes.data, off.size, _addr(stream)))
+        self.bandwidth_source = (off, wts)
+
+    def bandwidth(self):
+        """The spectrum in use (cbet_context_bandwidth): (offsets in rad/s, normalised weights), two numpy arrays of one double
+        per line, or None if none."""
+        off, wts, n = np.zeros(MAX_BAND_LINES), np.zeros(MAX_BAND_LINES), C.c_int()
+        _check(lib().cbet_context_bandwidth(self._h, _dptr(off), _dptr(wts), C.byref(n)))
+        return (off[:n.value].copy(), wts[:n.value].copy()) if n.value else None
 
     def set_polarization(self, mode):
         """cbet_context_set_polarization: "aligned" (every beam pair polarized alike, the default) or "smoothed" (every beam
@@ -963,13 +989,45 @@ def wavelength_shift_to_domega(params, dlambda_angstrom):
     return omega * lam0 / (lam0 + dl) - omega
 
 
+MAX_BAND_LINES = 8                              # CBET_MAX_BAND_LINES of the header
+LINE_SHAPES = ("flat", "gaussian")
+
+
+def line_arrays(domega, weights=None):
+    """A line spectrum as two contiguous float64 arrays of equal length (offsets, weights); weights None = equal weights.  The
+    library judges the values."""
+    off = np.array(domega, dtype=np.float64).reshape(-1)
+    wts = np.ones(off.size) if weights is None else np.array(weights, dtype=np.float64).reshape(-1)
+    if wts.size != off.size:
+        raise ValueError("a line spectrum holds one weight per offset: %d offsets, %d weights" % (off.size, wts.size))
+    return off, wts
+
+
+def line_spectrum(params, width_angstrom, nlines, shape="flat"):
+    """A line spectrum of `nlines` lines equally spaced in wavelength across `width_angstrom` (the distance between the outermost
+    lines, centred on the nominal wavelength of `params`) as (domega, weights): offsets in rad/s through the exact
+    wavelength_shift_to_domega, red lines first; weights that sum to 1 -- "flat": equal; "gaussian": exp(-4 ln 2 (dl / width)^2),
+    the width taken as the full width at half maximum, so the outermost lines carry half the centre's weight.  One line is
+    (0, 1): no spectrum."""
+    if shape not in LINE_SHAPES:
+        raise ValueError("shape is one of %s, got %r" % (", ".join(repr(s) for s in LINE_SHAPES), shape))
+    if not 1 <= int(nlines) <= MAX_BAND_LINES:
+        raise ValueError("nlines = %r: 1 .. %d lines" % (nlines, MAX_BAND_LINES))
+    if not np.isfinite(width_angstrom) or width_angstrom < 0:
+        raise ValueError("width_angstrom = %r: a finite width >= 0" % (width_angstrom,))
+    nlines = int(nlines)
+    dl = np.linspace(0.5 * width_angstrom, -0.5 * width_angstrom, nlines) if nlines > 1 else np.zeros(1)
+    weights = np.ones(nlines) if shape == "flat" or width_angstrom == 0 else np.exp(-4.0 * np.log(2.0) * (dl / width_angstrom) ** 2)
+    return wavelength_shift_to_domega(params, dl), weights / weights.sum()
+
+
 def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=None, dn_max=0.0, hx_lo=0, hx_hi=None, out=None,
-                         gross=None, shift=None, polarization="aligned"):
+                         gross=None, shift=None, polarization="aligned", lines=None):
     """cbet_exchange_matrix_host, the host twin: numpy (T, Gross), each (nbeams, nbeams), of normalised HOST fields
     [4, nbeams, nx + 2, ny + 2, nz + 2] over the planes [hx_lo, hx_hi).  ne3d (nx, ny, nz); flow (3, nx, ny, nz) or None = the
     closed-form ramp; state (2, nx, ny, nz) or None = the scalars; dn_max 0 = no limit; shift (nbeams,) per-beam frequency
-    shifts in rad/s or None; polarization "aligned" or "smoothed" (cbet_exchange_matrix_host_polarized).  out / gross: arrays
-    to ADD into (default: new zeroed ones)."""
+    shifts in rad/s or None; polarization "aligned" or "smoothed"; lines (offsets in rad/s, weights) of the spectrum every beam
+    carries, or None (cbet_exchange_matrix_host_banded).  out / gross: arrays to ADD into (default: new zeroed ones)."""
     nb = params.nbeams
     host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
     fields, ne3d, flow, state, shift = host(fields), host(ne3d), host(flow), host(state), host(shift)
@@ -978,9 +1036,11 @@ def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=Non
     out = np.zeros((nb, nb)) if out is None else out
     gross = np.zeros((nb, nb)) if gross is None else gross
     pol = polarization_mode(polarization)
-    _check(lib().cbet_exchange_matrix_host_polarized(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
-                                                     params.nx + 2 if hx_hi is None else hx_hi, C.byref(params),
-                                                     C.byref(gain_params), _addr(flow), _addr(state), dn_max, _addr(shift), pol))
+    off, wts = (None, None) if lines is None else line_arrays(*lines)
+    _check(lib().cbet_exchange_matrix_host_banded(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), hx_lo,
+                                                  params.nx + 2 if hx_hi is None else hx_hi, C.byref(params),
+                                                  C.byref(gain_params), _addr(flow), _addr(state), dn_max, _addr(shift), pol,
+                                                  _addr(off), _addr(wts), 0 if off is None else off.size))
     return out, gross
 
 

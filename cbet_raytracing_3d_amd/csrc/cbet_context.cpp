@@ -114,6 +114,7 @@ int cbet_context_destroy(cbet_context *ctx)
     (void)hipFree(ctx->flow_own);
     (void)hipFree(ctx->state_own);
     (void)hipFree(ctx->shift_own);
+    (void)hipFree(ctx->band_own);
     delete ctx;
     return CBET_OK;
 }
@@ -360,6 +361,48 @@ int cbet_context_polarization(cbet_context *ctx, int *mode)
 {
     if (!ctx || !mode) return fail(CBET_EINVAL, "NULL context/mode");
     *mode = ctx->pol;
+    return CBET_OK;
+}
+
+// The lines are judged before the context, as cbet_context_set_detuning judges its shifts: a refusal needs no device.
+int cbet_context_set_bandwidth(cbet_context *ctx, const double *line_domega, const double *line_weight, int nlines, void *stream)
+{
+    if (int rc = band_check("cbet_context_set_bandwidth", line_domega, line_weight, nlines)) return rc;
+    if (!ctx) return fail(CBET_EINVAL, "cbet_context_set_bandwidth: NULL context");
+    constexpr int kTable = 1 + 2 * kBandMax;
+    double fresh[kTable + CBET_MAX_CBET_BEAMS] = {}, norm[CBET_MAX_BAND_LINES] = {};   // the table, then the zero shifts
+    const int M = (line_domega && line_weight && nlines > 1) ? band_table(line_domega, line_weight, nlines, fresh, norm) : 0;
+    if (M == 0) {                           // no lines, one line or equal offsets: only differences enter the model
+        ctx->band = nullptr;
+        ctx->nband = 0;
+        ctx->nlines = 0;
+        return CBET_OK;
+    }
+    CBET_ENTER_DEVICE(ctx);
+    if (!ctx->band_own) {
+        hipError_t e = hipMalloc((void **)&ctx->band_own, sizeof fresh);
+        if (e != hipSuccess) {
+            ctx->band_own = nullptr;
+            return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(bandwidth table): %s", hipGetErrorString(e));
+        }
+    }
+    CBET_HIP(hipStreamSynchronize((hipStream_t)stream));   // a launch in flight may still read the old values
+    CBET_HIP(hipMemcpy(ctx->band_own, fresh, sizeof fresh, hipMemcpyHostToDevice));
+    ctx->band = ctx->band_own;
+    ctx->nband = M;
+    ctx->nlines = nlines;
+    for (int a = 0; a < nlines; ++a) { ctx->line_domega[a] = line_domega[a]; ctx->line_weight[a] = norm[a]; }
+    return CBET_OK;
+}
+
+int cbet_context_bandwidth(cbet_context *ctx, double *line_domega, double *line_weight, int *nlines)
+{
+    if (!ctx || !nlines) return fail(CBET_EINVAL, "NULL context/nlines");
+    *nlines = ctx->band ? ctx->nlines : 0;
+    for (int a = 0; a < *nlines; ++a) {
+        if (line_domega) line_domega[a] = ctx->line_domega[a];
+        if (line_weight) line_weight[a] = ctx->line_weight[a];
+    }
     return CBET_OK;
 }
 

@@ -130,6 +130,12 @@ struct GainArgs {
     double sat;                             // limit dn_max of the ion-acoustic amplitude a pair's gain corresponds to (cbet_context_set_saturation), 0 = none
     const double *shift;                    // [CBET_MAX_CBET_BEAMS] per-beam angular-frequency shifts, rad/s (cbet_context_set_detuning; entries past nbeams are 0), or NULL: one colour
     int pol;                                // CBET_POL_*: 0 = every pair polarized alike; 1 = polarization smoothing, every pair gain times (1 + cos^2 theta) / 4 (cbet_context_set_polarization)
+    // laser bandwidth (cbet_context_set_bandwidth): the difference table of the line spectrum every beam
+    // carries, [1 + 2 nband] doubles {c_0, d_0, c_0', d_1, c_1', ...} -- the centre weight, then per entry the difference d_m > 0
+    // (rad/s, ascending) and its weight c_m' (band_table, cbet_exchange_host.cpp) -- or NULL: monochromatic beams.  A block with
+    // a table always carries `shift` too (zeros where the context has no shifts).
+    const double *band;
+    int nband;                              // M, the entries behind c_0: 1 .. CBET_MAX_BAND_LINES (CBET_MAX_BAND_LINES - 1) / 2; 0 with band == NULL
 };
 
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);

@@ -5,8 +5,12 @@
 // operator, the library is built with -ffp-contract=off -- with every pair's two sums compensated (Neumaier).
 // No HIP call: it is the reference of the device path at any size.  cbet_exchange_matrix_host_shifted is the twin with per-beam
 // frequency shifts, cbet_exchange_matrix_host_polarized the one with a polarization mode on top (section
-// 20): the loop itself; the argument builder the kernels and the twin share (gain_args) lives here too.
+// 20), cbet_exchange_matrix_host_banded the one with a line spectrum on top of that (section 21): the loop itself; the argument
+// builder the kernels and the twin share (gain_args) and the builder of the spectrum's difference table (band_table), which
+// the twin and the context share, live here too.
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "cbet_gain_model.h"
@@ -31,7 +35,7 @@ inline void add_compensated(double &sum, double &comp, double x)
 // here, beside the twin, so that the twin links without the HIP runtime.
 cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
                                const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                               const double *shift, int pol, int hx_lo, int hx_hi, bool packed)
+                               const double *shift, int pol, const double *band, int nband, int hx_lo, int hx_hi, bool packed)
 {
     GainArgs a{};
     grid_args(a, p, d);
@@ -40,11 +44,63 @@ cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, cons
     ramp_args(a, g, cs);
     a.gain_const = gc; a.iaw = g->iaw; a.relax = g->relax;
     a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat; a.shift = shift; a.pol = pol;
+    a.band = band; a.nband = band ? nband : 0;
     a.hx_lo = hx_lo; a.hx_hi = hx_hi;
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
     a.store0 = packed ? (long)hx_lo * plane : 0;
     a.bstride = packed ? (long)(hx_hi - hx_lo) * plane : d.edep_size;
     return a;
+}
+
+// The lines of a spectrum as the caller gives them: what cbet_context_set_bandwidth and the banded twin refuse, by one text.
+int cbet::band_check(const char *who, const double *line_domega, const double *line_weight, int nlines)
+{
+    if (nlines < 0) return fail(CBET_EINVAL, "%s: nlines = %d is negative (0 = no spectrum)", who, nlines);
+    if (nlines > CBET_MAX_BAND_LINES) return fail(CBET_EINVAL, "%s: nlines = %d exceeds CBET_MAX_BAND_LINES = %d", who, nlines, CBET_MAX_BAND_LINES);
+    if (nlines == 0 || (!line_domega && !line_weight)) return CBET_OK;
+    if (!line_domega) return fail(CBET_EINVAL, "%s: line_domega is NULL but line_weight is not (both, or neither = no spectrum)", who);
+    if (!line_weight) return fail(CBET_EINVAL, "%s: line_weight is NULL but line_domega is not (both, or neither = no spectrum)", who);
+    for (int a = 0; a < nlines; ++a) {
+        if (std::isnan(line_domega[a])) return fail(CBET_EINVAL, "%s: line_domega[%d] is NaN (finite offsets in rad/s)", who, a);
+        if (std::isinf(line_domega[a])) return fail(CBET_EINVAL, "%s: line_domega[%d] is infinite (finite offsets in rad/s)", who, a);
+        if (!std::isfinite(line_weight[a]) || !(line_weight[a] > 0.0))
+            return fail(CBET_EINVAL, "%s: line_weight[%d] = %g is not finite and > 0", who, a, line_weight[a]);
+    }
+    return CBET_OK;
+}
+
+// The difference table of a line spectrum (GainArgs.band; cbet_gain_model.h pair_gain_band), deterministic:
+//   * the weights are normalised, p_a = w_a / (w_0 + w_1 + ...), the sum taken in line order (norm[] receives them);
+//   * c_0 = p_0 p_0 + p_1 p_1 + ..., in line order;
+//   * the differences |o_b - o_a| in fp64 for a < b, a ascending and b ascending inside a, each with p_a p_b; a difference of
+//     exactly zero (two lines at one offset) adds 2 p_a p_b to c_0; bitwise-equal differences are merged, their weights added
+//     in the order met;
+//   * the entries are sorted by d, ascending.
+// table holds 1 + 2 M doubles {c_0, d_0, c_0', d_1, c_1', ...}; returns M (0: one line, or all offsets equal -- no spectrum).
+int cbet::band_table(const double *line_domega, const double *line_weight, int nlines, double *table, double *norm)
+{
+    double p[CBET_MAX_BAND_LINES], sum = 0.0;
+    for (int a = 0; a < nlines; ++a) sum = sum + line_weight[a];
+    for (int a = 0; a < nlines; ++a) p[a] = line_weight[a] / sum;
+    if (norm) std::memcpy(norm, p, (size_t)nlines * sizeof(double));
+    double c0 = 0.0, d[kBandMax], c[kBandMax];
+    int M = 0;
+    for (int a = 0; a < nlines; ++a) c0 = c0 + p[a] * p[a];
+    for (int a = 0; a < nlines; ++a)
+        for (int b = a + 1; b < nlines; ++b) {
+            const double diff = std::fabs(line_domega[b] - line_domega[a]), w = p[a] * p[b];
+            if (diff == 0.0) { c0 = c0 + (w + w); continue; }
+            int m = 0;
+            while (m < M && d[m] != diff) ++m;
+            if (m == M) { d[M] = diff; c[M] = w; ++M; }
+            else c[m] = c[m] + w;
+        }
+    int order[kBandMax];
+    for (int m = 0; m < M; ++m) order[m] = m;
+    std::sort(order, order + M, [&](int x, int y) { return d[x] < d[y]; });   // the differences are distinct
+    table[0] = c0;
+    for (int m = 0; m < M; ++m) { table[1 + 2 * m] = d[order[m]]; table[2 + 2 * m] = c[order[m]]; }
+    return M;
 }
 
 int cbet::slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p)
@@ -69,14 +125,25 @@ extern "C" int cbet_exchange_matrix_host_shifted(const double *fields, const dou
     return cbet_exchange_matrix_host_polarized(fields, ne3d, out, gross, hx_lo, hx_hi, p, g, flow, state, dn_max, shift, CBET_POL_ALIGNED);
 }
 
-// ... and a polarization mode: the loop.  The ordered statement with the beat frequency (pair_gain's
-// second form) wherever shift is given -- equal shifts add an exact zero to every pair -- times pair_smoothing's factor where
-// pol is CBET_POL_SMOOTHED, before the clamp.
+// ... and a polarization mode.
 extern "C" int cbet_exchange_matrix_host_polarized(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo,
                                                    int hx_hi, const cbet_params *p, const cbet_gain_params *g, const double *flow,
                                                    const double *state, double dn_max, const double *shift, int pol)
 {
+    return cbet_exchange_matrix_host_banded(fields, ne3d, out, gross, hx_lo, hx_hi, p, g, flow, state, dn_max, shift, pol, nullptr, nullptr, 0);
+}
+
+// ... and a line spectrum: the loop.  The ordered statement with the beat frequency (pair_gain's
+// second form) wherever shift is given -- equal shifts add an exact zero to every pair --, pair_gain_band's sum over the
+// spectrum's difference table where the lines make one (no lines, one line or equal offsets: the statements above, bit for
+// bit), times pair_smoothing's factor where pol is CBET_POL_SMOOTHED, before the clamp.
+extern "C" int cbet_exchange_matrix_host_banded(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo,
+                                                int hx_hi, const cbet_params *p, const cbet_gain_params *g, const double *flow,
+                                                const double *state, double dn_max, const double *shift, int pol,
+                                                const double *line_domega, const double *line_weight, int nlines)
+{
     using namespace cbet;
+    if (int rc = band_check("cbet_exchange_matrix_host_banded", line_domega, line_weight, nlines)) return rc;
     if (pol != CBET_POL_ALIGNED && pol != CBET_POL_SMOOTHED)
         return fail(CBET_EINVAL, "cbet_exchange_matrix_host_polarized: pol = %d is unknown (CBET_POL_ALIGNED = %d or CBET_POL_SMOOTHED = %d)",
                     pol, CBET_POL_ALIGNED, CBET_POL_SMOOTHED);
@@ -99,7 +166,11 @@ extern "C" int cbet_exchange_matrix_host_polarized(const double *fields, const d
         table[b] = shift[b];
     }
     if (nb < 2 || hx_hi == hx_lo) return CBET_OK;
-    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, shift ? table : nullptr, pol, hx_lo, hx_hi, false);
+    double band[1 + 2 * kBandMax];
+    const int nband = (line_domega && line_weight && nlines > 1) ? band_table(line_domega, line_weight, nlines, band, nullptr) : 0;
+    // a block with a spectrum carries shifts, as the kernels' does: zeros where none are given
+    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, (shift || nband) ? table : nullptr, pol,
+                                 nband ? band : nullptr, nband, hx_lo, hx_hi, false);
     const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride, total = hsize * nb;
     const double iaw2 = a.iaw * a.iaw;
@@ -127,7 +198,9 @@ extern "C" int cbet_exchange_matrix_host_polarized(const double *fields, const d
                 const BeamAtCell Bj = beam_at(fI, fx, fy, fz, (long)bj * hsize);
                 const PairWave w = pair_wave(Bi, Bj);
                 if (!pair_present(Bi, Bj, w)) continue;
-                double gn = a.shift ? pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]) : pair_gain(c, pref, iaw2, w);
+                double gn;
+                if (a.band) gn = pair_gain_band(c, pref, iaw2, w, a.shift[bj] - a.shift[bi], a.band, a.nband);
+                else gn = a.shift ? pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]) : pair_gain(c, pref, iaw2, w);
                 if (a.pol) gn = gn * pair_smoothing(Bi, Bj, kmag);
                 if (sat) gn = pair_clamp(gn, Bi.I, Bj.I, lim);
                 const double x = ((ds_node * gn) * Bi.I) * Bj.I;

@@ -138,6 +138,35 @@ CBET_HD double pair_smoothing(const BeamAtCell &bi, const BeamAtCell &bj, double
     const double cth = ((bi.kx * bj.kx + bi.ky * bj.ky) + bi.kz * bj.kz) / (kmag * kmag);
     return 0.25 * (1.0 + cth * cth);
 }
+// Laser bandwidth.  Every beam carries the SAME spectrum about its own centre frequency omega + w_b: L
+// lines with offsets o_a (rad/s) and weights p_a > 0, sum p_a = 1.  The lines are mutually incoherent (line spacing >> the
+// ion-acoustic damping rate): line a of beam i and line b of beam j drive their own grating at the beat
+// (w_j - w_i) + (o_b - o_a), and the pair gain is the weighted sum of their resonances,
+//     G_ij = pref sum_a sum_b p_a p_b P((N + (o_b - o_a)) / D),    N = (0.0 - q . u) + (w_j - w_i),    D = |q| cs + 1e-10.
+// The spectrum is shared, so the double sum collapses onto its autocorrelation, the difference table `band` of M entries
+// (GainArgs.band, built by band_table): c_0 = sum p_a^2, and per entry d_m > 0 with c_m = sum_{a < b, |o_b - o_a| = d_m} p_a p_b:
+//     S = c_0 P(N / D)
+//     for m = 0 .. M-1:   S = S + c_m (P((N + d_m) / D) + P((N - d_m) / D))
+//     g = pref S          then the factor f (section 20), then the clamp (section 17), as without a spectrum.
+// N -> -N exactly for (j, i), (-N + d) = -(N - d) exactly, P is odd and the bracket is one commutative add: G_ji = -G_ij stays
+// exact and a cell's exchange still cancels.  Still plasma without shifts has N = 0, every bracket is P(d / D) + P(-(d / D)) = 0
+// and S = 0 exactly: bandwidth alone transfers nothing, it only smears a resonance that flow or detuning creates.  Far off
+// resonance (d_m >> |q| cs) only the centre term survives: G -> c_0 G_mono, 1/L for L equal lines.  M = 0 is no table at all
+// (one line, or equal offsets): the forms above run.  The field model keeps ONE intensity per beam: the spectral shape is not
+// changed by the exchange (no per-line depletion).  The clamp sees the SUMMED pair gain, and the amplitude map reports the
+// amplitude of the pair's total exchange, not of one line pair's grating -- section 20's choice.  Left out: per-beam spectra,
+// per-line fields or depletion, coherent or FM (SSD phase-modulated) spectra, any effect on refraction, ncrit or k0.
+CBET_HD double pair_gain_band(const CellState &c, double pref, double iaw2, const PairWave &w, double dw, const double *band, int nband)
+{
+    const double N = (0.0 - (w.qx * c.ux + w.qy * c.uy + w.qz * c.uz)) + dw;
+    const double D = w.kiaw * c.cs + 1e-10;
+    double S = band[0] * pair_resonance(N / D, iaw2);
+    for (int m = 0; m < nband; ++m) {
+        const double d = band[1 + 2 * m];
+        S = S + band[2 + 2 * m] * (pair_resonance((N + d) / D, iaw2) + pair_resonance((N - d) / D, iaw2));
+    }
+    return pref * S;
+}
 // The clamp: g scaled by min(1, lim / w), w = |g| sqrt(Ii Ij) (pair_swing) -- one factor for (i, j) and (j, i); a
 // pair below the limit keeps its bits.
 CBET_HD double pair_swing(double g, double Ii, double Ij) { return fabs(g) * sqrt(Ii * Ij); }

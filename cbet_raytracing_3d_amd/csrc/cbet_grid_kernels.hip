@@ -12,6 +12,8 @@
 // and saturate_fast (the two pair-once kernels), one dispatch of run-time switches onto template arguments (all four).
 // DETUNE (GainArgs.shift != NULL): per-beam frequency shifts, DESIGN.md section 19.  POL, the last switch of all four
 // (GainArgs.pol != 0): polarization smoothing, every pair gain times (1 + cos^2 theta) / 4 before the clamp, DESIGN.md section 20.
+// BAND (GainArgs.band != NULL): a line spectrum shared by all beams, the pair gain summed over its difference table, DESIGN.md
+// section 21 -- the third value of the DETUNE switch (Tune), never instantiated without the DETUNE statements.
 // Built with -ffp-contract=off like the rest of the library: every statement of the ordered kernel and of the
 // normalisation is one IEEE operation in the order written, which is the order the CPU checker of the CBET stage
 // uses; the pair-once kernel's pair function (pair_gain_fast) is the exception and says so.
@@ -23,6 +25,16 @@
 
 namespace cbet {
 namespace {
+
+// The colour switch of all four kernels: one colour; per-beam shifts (DETUNE, section 19); shifts and a line spectrum (BAND,
+// section 21: a block with a table always carries shifts, zeros if need be, so BAND is only built on top of DETUNE).
+enum Tune { kMono = 0, kDetune = 1, kBand = 2 };
+
+// The difference table as the kernels read it: by SCALAR loads.  The table is wave-uniform, written by a set-up call before
+// the launch and never by a kernel; through the constant address space every read is a scalar load into scalar registers,
+// whatever stores the kernel itself makes -- no vector register holds a table entry.
+typedef const __attribute__((address_space(4))) double *BandTable;
+__device__ __forceinline__ BandTable band_table_of(const GainArgs &a) { return (BandTable)a.band; }
 
 // The epilogue of both gain kernels: the wave's sums of |new - old| and |new| into GainArgs.change, two atomics per wave.
 __device__ __forceinline__ void report_change(const GainArgs &a, int lane, double sum_change, double sum_abs)
@@ -95,9 +107,11 @@ __device__ __forceinline__ BrickCell brick_cell(const GainArgs &a, long brick, i
 // DETUNE (GainArgs.shift != NULL): the pair's resonance gains the beat frequency shift[bj] - shift[bi]
 // (pair_gain's second form) -- both beams are wave-uniform, the two entries come by scalar loads.
 // POL (GainArgs.pol != 0): the pair gain times pair_smoothing's (1 + cos^2 theta) / 4, before the clamp.
-template <bool FLOW, bool STATE, bool SAT, bool DETUNE, bool POL>
+// BAND (TUNE == kBand, GainArgs.band != NULL): pair_gain_band's sum over the difference table instead.
+template <bool FLOW, bool STATE, bool SAT, int TUNE, bool POL>
 __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 {
+    constexpr bool DETUNE = TUNE != kMono, BAND = TUNE == kBand;
     const long hsize = a.bstride;                 // entries stored per beam (the whole haloed grid, or one x-slab of it)
     const long total = hsize * a.nbeams;
     const long bricks = brick_count(a);
@@ -137,7 +151,8 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
                     const PairWave w = pair_wave(Bi, Bj);
                     if (valid && pair_present(Bi, Bj, w)) {
                         double g;
-                        if constexpr (DETUNE) g = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
+                        if constexpr (BAND) g = pair_gain_band(c, pref, iaw2, w, a.shift[bj] - a.shift[bi], a.band, a.nband);
+                        else if constexpr (DETUNE) g = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
                         else g = pair_gain(c, pref, iaw2, w);
                         if constexpr (POL) g = g * pair_smoothing(Bi, Bj, kmag);
                         if (SAT) g = pair_clamp(g, Bi.I, Bj.I, lim);
@@ -164,9 +179,11 @@ __global__ void __launch_bounds__(256) k_gain_field(const GainArgs a)
 // kernel's statements, its bricks and its presence mask; one store per valid cell, 0 where no pair exchanges anything or the
 // plasma is not sub-critical.  w / kap grows with w, so the largest w is divided once.  Reads a.fields only; a.sat is not read.
 // DETUNE: the amplitude is that of the detuned |G_ij|.  POL: ... of the smoothed one, f |G_ij| (section 20).
-template <bool FLOW, bool STATE, bool DETUNE, bool POL>
+// BAND: ... of the pair's gain summed over the line spectrum, its total exchange, not of one line pair's grating (section 21).
+template <bool FLOW, bool STATE, int TUNE, bool POL>
 __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double *__restrict__ amp)
 {
+    constexpr bool DETUNE = TUNE != kMono, BAND = TUNE == kBand;
     const long hsize = a.bstride;
     const long total = hsize * a.nbeams;
     const long bricks = brick_count(a);
@@ -201,7 +218,8 @@ __global__ void __launch_bounds__(256) k_pair_amplitude(const GainArgs a, double
                 const PairWave w = pair_wave(Bi, Bj);
                 if (valid && pair_present(Bi, Bj, w)) {
                     double gn;
-                    if constexpr (DETUNE) gn = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
+                    if constexpr (BAND) gn = pair_gain_band(c, pref, iaw2, w, a.shift[bj] - a.shift[bi], a.band, a.nband);
+                    else if constexpr (DETUNE) gn = pair_gain(c, pref, iaw2, w, a.shift[bj] - a.shift[bi]);
                     else gn = pair_gain(c, pref, iaw2, w);
                     if constexpr (POL) gn = gn * pair_smoothing(Bi, Bj, kmag);
                     const double sw = pair_swing(gn, Bi.I, Bj.I);
@@ -281,10 +299,19 @@ __device__ __forceinline__ int run_hk(int run, int c, int sft) { return LC * run
 // present there and f = 1/2 multiplies zeros): one fma on q2raw, which is held anyway, one for f, one multiply.  An absolute
 // error of an ulp of 1 in cth is a relative one of at most two ulp in f >= 1/4.  A slot whose beam is absent from the cell holds
 // k = 0: cth = 1/2 there, a finite f on a gain that only ever multiplies that beam's I = 0.
-template <bool DETUNE = false, bool POL = false>
+// BAND: the quotient is Q(x) = x D^3 / ((x^2 - D^2)^2 + iaw^2 x^2 D^2) = P(x / D) / iaw^2, and the gain
+// pref iaw^2 (c_0 Q(N) + sum_m c_m (Q(N + d_m) + Q(N - d_m))).  The square-root chain, D, D^2 and D^3 are formed once per pair;
+// every table entry costs two more quotients of the same shape (estimate, Newton step, correction) and comes by one scalar
+// load of {d_m, c_m} (BandTable): the loop holds N, D^2, D^3 and S in vector registers beside the caller's, nothing per
+// entry.  Q is odd to the bit -- x enters the denominator squared, the numerator and both corrections change sign with it --
+// so where N = 0 (still plasma without shifts; q = 0, where dw does not count) every bracket is an exact zero whatever
+// d_m is: the guard of the DETUNE arm covers the table entries too, and parallel beams still exchange exactly nothing.
+template <bool DETUNE = false, bool POL = false, bool BAND = false>
 __device__ __forceinline__ double pair_gain_fast(const BeamAtCell &bi, const BeamAtCell &bj, double ux, double uy, double uz,
-                                                 double cs, double iaw2, double pref_iaw2, double dw = 0.0, double rk = 0.0)
+                                                 double cs, double iaw2, double pref_iaw2, double dw = 0.0, double rk = 0.0,
+                                                 BandTable band = nullptr, int nband = 0)
 {
+    static_assert(DETUNE || !BAND, "the BAND statements are built on the DETUNE ones");
     const double qx = bj.kx - bi.kx, qy = bj.ky - bi.ky, qz = bj.kz - bi.kz;
     const double q2raw = __builtin_fma(qz, qz, __builtin_fma(qy, qy, qx * qx));
     const double q2 = fmax(q2raw, 1e-280);
@@ -299,14 +326,34 @@ __device__ __forceinline__ double pair_gain_fast(const BeamAtCell &bi, const Bea
     gq = __builtin_fma(__builtin_fma(-gq, gq, q2), hq, gq);
     if constexpr (!DETUNE) N = -__builtin_fma(qz, uz, __builtin_fma(qy, uy, qx * ux));
     const double D = __builtin_fma(gq, cs, 1e-10);
-    const double N2 = N * N, D2 = D * D, t = N2 - D2;
-    const double den = __builtin_fma(t, t, (iaw2 * N2) * D2);
-    const double num = ((pref_iaw2 * N) * D) * D2;
-    // num / den: reciprocal estimate, one Newton step, one correction of the quotient
-    double y = __builtin_amdgcn_rcp(den);
-    y = __builtin_fma(__builtin_fma(-den, y, 1.0), y, y);
-    const double qt = num * y;
-    const double gn = __builtin_fma(__builtin_fma(-den, qt, num), y, qt);
+    double gn;
+    if constexpr (BAND) {
+        const double D2 = D * D, D3 = D * D2;
+        auto Q = [&](double x) {
+            const double x2 = x * x, t = x2 - D2;
+            const double den = __builtin_fma(t, t, (iaw2 * x2) * D2);
+            const double num = x * D3;
+            double y = __builtin_amdgcn_rcp(den);
+            y = __builtin_fma(__builtin_fma(-den, y, 1.0), y, y);
+            const double qt = num * y;
+            return __builtin_fma(__builtin_fma(-den, qt, num), y, qt);
+        };
+        double S = band[0] * Q(N);
+        for (int m = 0; m < nband; ++m) {
+            const double d = band[1 + 2 * m], cm = band[2 + 2 * m];
+            S = __builtin_fma(cm, Q(N + d) + Q(N - d), S);
+        }
+        gn = pref_iaw2 * S;
+    } else {
+        const double N2 = N * N, D2 = D * D, t = N2 - D2;
+        const double den = __builtin_fma(t, t, (iaw2 * N2) * D2);
+        const double num = ((pref_iaw2 * N) * D) * D2;
+        // num / den: reciprocal estimate, one Newton step, one correction of the quotient
+        double y = __builtin_amdgcn_rcp(den);
+        y = __builtin_fma(__builtin_fma(-den, y, 1.0), y, y);
+        const double qt = num * y;
+        gn = __builtin_fma(__builtin_fma(-den, qt, num), y, qt);
+    }
     if constexpr (POL) {
         const double cth = __builtin_fma(-q2raw, rk, 1.0);
         return gn * __builtin_fma(0.25 * cth, cth, 0.25);
@@ -374,9 +421,12 @@ __device__ __forceinline__ double uniform_f64(double v)
 // instantiations in scratch that way (DESIGN.md section 20 has both sets of figures, and those of re-deriving kmag^2 from
 // the A entry per pair).  The POL arm takes the registers back that the STATE, SAT and DETUNE arms do (LEAN, and the
 // DETUNE arm's kernel-wide invariants); the instantiations without POL keep their statements.
-template <bool FROZEN, bool FLOW, bool STATE, bool SAT, bool DETUNE, bool POL>
+// BAND (TUNE == kBand, GainArgs.band != NULL): the DETUNE arm's statements with the pair function's BAND
+// form -- the table by scalar loads inside it, the wave-uniform table pointer and count in scalar registers.
+template <bool FROZEN, bool FLOW, bool STATE, bool SAT, int TUNE, bool POL>
 __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 {
+    constexpr bool DETUNE = TUNE != kMono, BAND = TUNE == kBand;
     constexpr bool LEAN = STATE || SAT || DETUNE || POL;
     constexpr int PCH = (LEAN && !FROZEN) ? 3 : LCH, QCH = (LEAN && !FROZEN) ? 4 : LCH3;
     static_assert(5 * LCAP * LC >= 64 * (LC + 1), "the slot arrays double as the staging area of the presence masks");
@@ -560,7 +610,11 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
                             P1.I = sI[p1]; P1.kx = sX[p1]; P1.ky = sY[p1]; P1.kz = sZ[p1];
                             P2.I = sI[p2]; P2.kx = sX[p2]; P2.ky = sY[p2]; P2.kz = sZ[p2];
                             double g1, g2;
-                            if constexpr (POL) {
+                            if constexpr (BAND) {
+                                const double wS = sW[LG * ta + g];
+                                g1 = pair_gain_fast<true, POL, true>(S, P1, ux, uy, uz, cs, iaw2, pref_iaw2, sW[LG * ta + ((g + 1) & 3)] - wS, rk, band_table_of(a), a.nband);
+                                g2 = g < 2 ? pair_gain_fast<true, POL, true>(S, P2, ux, uy, uz, cs, iaw2, pref_iaw2, sW[LG * ta + ((g + 2) & 3)] - wS, rk, band_table_of(a), a.nband) : 0.0;
+                            } else if constexpr (POL) {
                                 double d1 = 0.0, d2 = 0.0;
                                 if constexpr (DETUNE) {
                                     const double wS = sW[LG * ta + g];
@@ -612,7 +666,8 @@ __global__ void __launch_bounds__(64, 3) k_gain_field_sym(const GainArgs a)
 #pragma unroll
                             for (int s_ = 0; s_ < LG; ++s_) {
                                 double gn;
-                                if constexpr (POL) gn = pair_gain_fast<DETUNE, true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, DETUNE ? WB - WA[s_] : 0.0, rk);
+                                if constexpr (BAND) gn = pair_gain_fast<true, POL, true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, WB - WA[s_], rk, band_table_of(a), a.nband);
+                                else if constexpr (POL) gn = pair_gain_fast<DETUNE, true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, DETUNE ? WB - WA[s_] : 0.0, rk);
                                 else if constexpr (DETUNE) gn = pair_gain_fast<true>(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2, WB - WA[s_]);
                                 else gn = pair_gain_fast(A[s_], B, ux, uy, uz, cs, iaw2, pref_iaw2);
                                 if (SAT) gn = saturate_fast(gn, A[s_].I, B.I, lim);
@@ -708,9 +763,11 @@ __device__ __forceinline__ int tri_start(int i, int n) { return i * (2 * n - i -
 // POL (GainArgs.pol != 0): rk = 1 / (2 kmag^2) is an eighth row of the state block (cell_rk; 512 bytes of
 // LDS more in the POL instantiations only, 53.5 KB: still three workgroups per CU) and the pair function's POL form scales the
 // quotient before saturate_fast.
-template <bool FLOW, bool STATE, bool SAT, bool DETUNE, bool POL>
+// BAND (TUNE == kBand, GainArgs.band != NULL): the pair function's BAND form, the table by scalar loads.
+template <bool FLOW, bool STATE, bool SAT, int TUNE, bool POL>
 __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, double *__restrict__ work)
 {
+    constexpr bool DETUNE = TUNE != kMono, BAND = TUNE == kBand;
     __shared__ double tab[2 * XPAIRS];
     __shared__ double sI[XSTAGE], sX[XSTAGE], sY[XSTAGE], sZ[XSTAGE];
     __shared__ double sSt[POL ? 8 : 7][64];
@@ -820,7 +877,8 @@ __global__ void __launch_bounds__(XT, 3) k_exchange_matrix(const GainArgs a, dou
                         A.I = sI[k * sp + sa]; A.kx = sX[k * sp + sa]; A.ky = sY[k * sp + sa]; A.kz = sZ[k * sp + sa];
                         B.I = sI[k * sp + sb]; B.kx = sX[k * sp + sb]; B.ky = sY[k * sp + sb]; B.kz = sZ[k * sp + sb];
                         double gn;
-                        if constexpr (POL) gn = pair_gain_fast<DETUNE, true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw, readlane_f64(st_rk, cell));
+                        if constexpr (BAND) gn = pair_gain_fast<true, POL, true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw, POL ? readlane_f64(st_rk, cell) : 0.0, band_table_of(a), a.nband);
+                        else if constexpr (POL) gn = pair_gain_fast<DETUNE, true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw, readlane_f64(st_rk, cell));
                         else if constexpr (DETUNE) gn = pair_gain_fast<true>(A, B, ux, uy, uz, cs, iaw2, pref_iaw2, dw);
                         else gn = pair_gain_fast(A, B, ux, uy, uz, cs, iaw2, pref_iaw2);
                         if (SAT) gn = saturate_fast(gn, A.I, B.I, readlane_f64(st_lim, cell));
@@ -973,14 +1031,18 @@ hipError_t launch_edep_average(const double *edep, double *out, int nx, int ny, 
 }
 
 // One dispatch of run-time switches onto template arguments, for the four templated kernels: dispatch({s0, s1, ...}, launch)
-// calls launch(c0, c1, ...) with ck a std::true_type or std::false_type -- the launch names <decltype(ck)::value...>.
+// calls launch(c0, c1, ...) with ck a std::integral_constant<int, v> -- the launch names <decltype(ck)::value...>.  A switch is
+// 0 or 1, but for the colour switch (tune_of), which alone may be 2 (kBand): three values, not two switches, so the kernels
+// grow by half with BAND and no BAND kernel is built without the DETUNE statements.
 template <int N, class Launch, class... Cs>
-void dispatch(const bool (&on)[N], Launch launch, Cs... cs)
+void dispatch(const int (&on)[N], Launch launch, Cs... cs)
 {
     if constexpr (sizeof...(Cs) == N) launch(cs...);
-    else if (on[sizeof...(Cs)]) dispatch(on, launch, cs..., std::true_type{});
-    else dispatch(on, launch, cs..., std::false_type{});
+    else if (on[sizeof...(Cs)] == 0) dispatch(on, launch, cs..., std::integral_constant<int, 0>{});
+    else if (on[sizeof...(Cs)] == 1) dispatch(on, launch, cs..., std::integral_constant<int, 1>{});
+    else if constexpr (sizeof...(Cs) == N - 2) dispatch(on, launch, cs..., std::integral_constant<int, kBand>{});   // the colour switch is the last but one of all four
 }
+static int tune_of(const GainArgs &a) { return a.band && a.shift ? kBand : (a.shift ? kDetune : kMono); }
 
 // k_gain_field's and k_pair_amplitude's grid: four wavefronts per workgroup, one brick per wavefront up to the cap
 static dim3 brick_grid(const GainArgs &a)
@@ -995,11 +1057,11 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
     if (a.scratch) {                       // one single-wavefront workgroup per z-row of the slab
         const long rows = (long)(a.hx_hi - a.hx_lo) * (a.ny + 2);
-        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
+        dispatch({a.frozen != 0, a.flow != nullptr, a.state != nullptr, a.sat > 0.0, tune_of(a), a.pol != 0}, [&](auto... s) {
             hipLaunchKernelGGL((k_gain_field_sym<decltype(s)::value...>), dim3((unsigned)rows), dim3(64), 0, stream, a);
         });
     } else {
-        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
+        dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, tune_of(a), a.pol != 0}, [&](auto... s) {
             hipLaunchKernelGGL((k_gain_field<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a);
         });
     }
@@ -1009,7 +1071,7 @@ hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream)
 hipError_t launch_pair_amplitude(const GainArgs &a, double *amp, hipStream_t stream)
 {
     if (a.hx_hi <= a.hx_lo) return hipSuccess;
-    dispatch({a.flow != nullptr, a.state != nullptr, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
+    dispatch({a.flow != nullptr, a.state != nullptr, tune_of(a), a.pol != 0}, [&](auto... s) {
         hipLaunchKernelGGL((k_pair_amplitude<decltype(s)::value...>), brick_grid(a), dim3(256), 0, stream, a, amp);
     });
     return hipGetLastError();
@@ -1020,7 +1082,7 @@ hipError_t launch_exchange_matrix(const GainArgs &a, double *work, double *out, 
     if (a.hx_hi <= a.hx_lo || a.nbeams < 2) return hipSuccess;
     // the number of workgroups follows from the slab alone, never from the device: the same partial sums everywhere
     const long groups = exchange_groups((long)(a.hx_hi - a.hx_lo) * (a.ny + 2));
-    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, a.shift != nullptr, a.pol != 0}, [&](auto... s) {
+    dispatch({a.flow != nullptr, a.state != nullptr, a.sat > 0.0, tune_of(a), a.pol != 0}, [&](auto... s) {
         hipLaunchKernelGGL((k_exchange_matrix<decltype(s)::value...>), dim3((unsigned)groups), dim3(XT), 0, stream, a, work);
     });
     if (hipError_t e = hipGetLastError()) return e;

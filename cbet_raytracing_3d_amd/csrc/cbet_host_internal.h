@@ -41,6 +41,13 @@ struct cbet_context {
     double shift_host[CBET_MAX_CBET_BEAMS] = {};   // what shift_own holds (cbet_context_detuning)
     // polarization mode of the gain kernels (cbet_context_set_polarization): CBET_POL_ALIGNED = every pair polarized alike
     int pol = CBET_POL_ALIGNED;
+    // line spectrum of the gain kernels (cbet_context_set_bandwidth): NULL = monochromatic beams
+    double *band_own = nullptr;         // the context's own device block, allocated by the first cbet_context_set_bandwidth that selects lines:
+                                        // the difference table [1 + 2 M_max] and behind it CBET_MAX_CBET_BEAMS zeros, the shifts of a context without detuning
+    const double *band = nullptr;       // the table in use: band_own, or NULL
+    int nband = 0;                      // its entries M
+    int nlines = 0;                     // the lines in use and their offsets and normalised weights (cbet_context_bandwidth)
+    double line_domega[CBET_MAX_BAND_LINES] = {}, line_weight[CBET_MAX_BAND_LINES] = {};
 };
 
 namespace cbet {
@@ -153,10 +160,17 @@ int mesh_check(const cbet_mesh *mesh, bool whole);
 // The gain kernels', k_pair_amplitude's, k_exchange_matrix's and its host twin's (cbet_exchange_host.cpp).  cs, gc: cbet_gain_constants';
 // packed: the arrays hold the slab's planes only.  gain, scratch, change, consume and frozen stay zero: the gain update sets them.
 // shift: the per-beam frequency shifts, a table of CBET_MAX_CBET_BEAMS doubles (device memory for a kernel, host memory for the
-// twin), or NULL.  pol: the polarization mode, CBET_POL_*.
+// twin), or NULL.  pol: the polarization mode, CBET_POL_*.  band, nband: the difference table of the line spectrum (band_table;
+// device or host memory like shift) and its entries M, or NULL: a block with a table carries a shift table too.
 GainArgs gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
                    const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                   const double *shift, int pol, int hx_lo, int hx_hi, bool packed);
+                   const double *shift, int pol, const double *band, int nband, int hx_lo, int hx_hi, bool packed);
+// The line spectrum of the gain stage (cbet_exchange_host.cpp, no HIP call).  band_check: the refusals of
+// cbet_context_set_bandwidth and of the banded twin, `who` in front.  band_table: the difference table of nlines valid lines
+// into table[1 + 2 kBandMax] = {c_0, d_0, c_0', ...} and the normalised weights into norm[nlines] (or NULL); returns M.
+constexpr int kBandMax = CBET_MAX_BAND_LINES * (CBET_MAX_BAND_LINES - 1) / 2;
+int band_check(const char *who, const double *line_domega, const double *line_weight, int nlines);
+int band_table(const double *line_domega, const double *line_weight, int nlines, double *table, double *norm);
 // The slab [hx_lo, hx_hi) lies in the haloed grid; who: the entry point's name and ": " in front of the message, or "".
 int slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p);
 

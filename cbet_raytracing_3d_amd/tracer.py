@@ -115,6 +115,10 @@ class RayTracer:
             ctx.detuning_source = own
         if ctx is not self.ctx:                     # ... and its polarization mode (set_polarization)
             ctx.set_polarization(self.ctx.polarization())
+        band = self.ctx.bandwidth_source            # ... and its line spectrum (set_bandwidth), as the shifts
+        if ctx is not self.ctx and ctx.bandwidth_source is not band:
+            ctx.set_bandwidth(*((None,) if band is None else band), stream=self._stream())
+            ctx.bandwidth_source = band
 
     def _tabulate_other(self, ctx, params):
         """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False
@@ -306,6 +310,31 @@ class RayTracer:
     def detuning(self):
         """The frequency shifts in use (rad/s, one per beam; the context's own record), or None if none."""
         return self.ctx.detuning()
+
+    # ---- laser bandwidth (include/cbet_mi355x.h cbet_context_set_bandwidth; DESIGN.md section 21) -----------------------
+    def set_bandwidth(self, domega=None, weights=None, dlambda_angstrom=None):
+        """A line spectrum in the gain kernels, the SAME for every beam about its own centre frequency (its colour of
+        set_detuning): ONE of domega (line offsets in rad/s) or dlambda_angstrom (wavelength offsets of the nominal wavelength
+        in Angstrom, > 0 = red; api.wavelength_shift_to_domega), with `weights` > 0 (None: equal; normalised to sum 1 by the
+        library), at most api.MAX_BAND_LINES lines -- api.line_spectrum makes equally spaced ones.  No argument, one line or
+        equal offsets select no spectrum, the default.  The lines are incoherent: every line pair of two beams drives its own
+        grating, and the pair gain is the weighted sum of their resonances; bandwidth alone transfers nothing, it smears a
+        resonance that flow or detuning creates.  The spectrum is the context's, like the shifts: gain_field, pair_amplitude,
+        exchange_matrix, both loops of cbet_solve and the contexts this tracer prepares later honour it; the tracer keeps no
+        copy.  A set-up call: it waits for torch's current stream.  A NaN or infinite offset or a weight that is not finite and
+        > 0 raises and changes nothing."""
+        if domega is not None and dlambda_angstrom is not None:
+            raise ValueError("set_bandwidth takes domega or dlambda_angstrom, not both")
+        if dlambda_angstrom is not None:
+            dl = np.asarray(dlambda_angstrom, dtype=np.float64)
+            if not np.isfinite(dl).all():
+                raise ValueError("set_bandwidth: dlambda_angstrom holds a NaN or infinite value")
+            domega = api.wavelength_shift_to_domega(self.params, dl)
+        self.ctx.set_bandwidth(domega, weights, self._stream())
+
+    def bandwidth(self):
+        """The line spectrum in use ((offsets in rad/s, normalised weights); the context's own record), or None if none."""
+        return self.ctx.bandwidth()
 
     # ---- polarization smoothing (include/cbet_mi355x.h cbet_context_set_polarization; DESIGN.md section 20) -------------
     def set_polarization(self, mode="aligned"):

@@ -867,6 +867,58 @@ int cbet_exchange_matrix_host_polarized(const double *fields, const double *ne3d
                                         const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
                                         double dn_max, const double *shift, int pol);
 
+/* ---- laser bandwidth ------------------------------------------------------------------------ */
+/*
+ * A line spectrum in the gain stage.  Every beam carries the SAME spectrum about its own centre frequency omega + w_b (w_b the
+ * shift of cbet_context_set_detuning): L <= CBET_MAX_BAND_LINES lines with offsets o_a in rad/s and weights p_a > 0, which the
+ * library normalises to sum p_a = 1.  The lines are mutually incoherent -- the line spacing is taken to be far above the
+ * ion-acoustic damping rate -- so line a of beam i and line b of beam j drive their own grating at the beat
+ * (w_j - w_i) + (o_b - o_a), and the pair gain is
+ *     G_ij = pref sum_a sum_b p_a p_b P((N + (o_b - o_a)) / D),    N = (0.0 - q . u) + (w_j - w_i),    D = kiaw*cs + 1e-10.
+ * The spectrum is shared, so the double sum collapses onto its autocorrelation: a difference table of M <= L (L - 1) / 2
+ * entries d_m > 0 with weights c_m = sum_{a < b, |o_b - o_a| = d_m} p_a p_b, and the centre weight c_0 = sum p_a^2.  The
+ * ordered kernel runs
+ *     S = c_0 * P(N / D)
+ *     for m = 0 .. M-1:   S = S + c_m * (P((N + d_m) / D) + P((N - d_m) / D))
+ *     g = pref * S        then the polarization factor, then the saturation clamp, as without a spectrum
+ * -- every written operator ONE IEEE fp64 operation in the written order -- and the pair-once kernels the same sum with their
+ * quotient form of P (a few ulp from it).  The table is built deterministically: weights normalised by their sum in line
+ * order; c_0 summed in line order; the differences |o_b - o_a| in fp64 for a < b in ascending order (a, then b); a zero
+ * difference adds 2 p_a p_b to c_0; bitwise-equal differences are merged; the entries are sorted by d.
+ * Identities: G_ji = -G_ij bit for bit (N -> -N and (-N + d) = -(N - d) exactly, P is odd, the bracket is one commutative
+ * add), so a cell's exchange still cancels, with or without a limit; still plasma without shifts gives exactly zero under any
+ * spectrum (N = 0 makes every bracket zero): bandwidth alone transfers nothing, it smears a resonance that flow or detuning
+ * creates; M = 0 (no lines, one line, or all offsets equal) selects no spectrum at all and the bits of the sections above; two
+ * exactly parallel beams exchange exactly nothing; far off resonance (d_m >> |q| cs) only the centre term survives and
+ * G -> c_0 G_mono, 1/L for L equal lines.
+ * The model's choices: the field model keeps ONE intensity per beam -- the spectral shape is not changed by the exchange, no
+ * per-line depletion.  The saturation limit clamps the SUMMED pair gain, and cbet_pair_amplitude reports the amplitude of the
+ * pair's total exchange, not of one line pair's grating (the choice of polarization smoothing).
+ * Out of scope: per-beam spectra; per-line fields or depletion; coherent or FM (SSD phase-modulated) spectra; any effect on
+ * refraction, ncrit or k0.  The trace kernels only gather K and do not see the spectrum.
+ *
+ * cbet_context_set_bandwidth: line_domega[nlines] and line_weight[nlines] HOST doubles.  nlines = 0, NULL arrays, one line or
+ * offsets that are all equal select none (a new context's default); otherwise the difference table goes to a device block the
+ * context owns (the first such call allocates it).  A SET-UP call like cbet_context_set_detuning: it synchronises `stream`
+ * before it overwrites the table, copies synchronously, is not capturable in a graph, and applies to launches made after it.
+ * CBET_EINVAL naming the offence, judged before the context (no device needed): a NaN or infinite offset, a weight that is not
+ * finite and > 0, nlines < 0 or above CBET_MAX_BAND_LINES, one array NULL and the other not; then a NULL context.  A refused
+ * call changes nothing.  Every entry that builds its gain arguments from that context honours the spectrum -- cbet_gain_field,
+ * cbet_gain_field_slab, cbet_gain_field_packed, cbet_pair_amplitude, cbet_exchange_matrix, and cbet_cbet_solve with a caller's
+ * context; with ctx == NULL the solve runs without one.
+ * cbet_context_bandwidth: *nlines = the lines in use, 0 for none, and their offsets and NORMALISED weights in
+ * line_domega / line_weight[0 .. *nlines) (each holds CBET_MAX_BAND_LINES doubles, or is NULL).
+ * cbet_exchange_matrix_host_banded: cbet_exchange_matrix_host_polarized with lines (HOST arrays, the same refusals): the
+ * ordered statements above on the same table, compensated sums as there.  The earlier twins call it with no lines.
+ */
+#define CBET_MAX_BAND_LINES 8
+int cbet_context_set_bandwidth(cbet_context *ctx, const double *line_domega, const double *line_weight, int nlines, void *stream);
+int cbet_context_bandwidth(cbet_context *ctx, double *line_domega, double *line_weight, int *nlines);
+int cbet_exchange_matrix_host_banded(const double *fields, const double *ne3d, double *out, double *gross, int hx_lo, int hx_hi,
+                                     const cbet_params *p, const cbet_gain_params *g, const double *flow, const double *state,
+                                     double dn_max, const double *shift, int pol, const double *line_domega,
+                                     const double *line_weight, int nlines);
+
 /* ---- exit pass --------------------------------------------------------------- */
 /*
  * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
