@@ -147,6 +147,32 @@ def farfield_numpy(records, ntheta, nphi):
     return hist
 
 
+# ---- ray path recorder (cbet_trace_paths) --------------------------------------------------------
+class PathSample(C.Structure):
+    """cbet_path_sample: a ray's state at the launch point (step 0) or after a step (64 bytes)."""
+    _fields_ = [
+        ("x", C.c_double), ("y", C.c_double), ("z", C.c_double),
+        ("uray", C.c_double), ("absorbed", C.c_double), ("gained", C.c_double),
+        ("ci", C.c_int), ("cj", C.c_int), ("ck", C.c_int), ("step", C.c_int),
+    ]
+
+
+class RayTurn(C.Structure):
+    """cbet_ray_turn: a ray's closest approach to the centre, and how it ended (64 bytes)."""
+    _fields_ = [
+        ("r2", C.c_double), ("x", C.c_double), ("y", C.c_double), ("z", C.c_double),
+        ("uray", C.c_double), ("ne", C.c_double),
+        ("step", C.c_int), ("steps", C.c_int), ("status", C.c_int), ("nsamples", C.c_int),
+    ]
+
+
+# the same records as numpy structured dtypes: view a downloaded [..., 8] float64 array with .view(PATH_DTYPE) / .view(TURN_DTYPE)
+PATH_DTYPE = np.dtype([(name, "<f8" if ct is C.c_double else "<i4") for name, ct in PathSample._fields_])
+TURN_DTYPE = np.dtype([(name, "<f8" if ct is C.c_double else "<i4") for name, ct in RayTurn._fields_])
+assert PATH_DTYPE.itemsize == C.sizeof(PathSample) == 64
+assert TURN_DTYPE.itemsize == C.sizeof(RayTurn) == 64
+
+
 # ---- perturbed targets (cbet_tabulate_target) ----------------------------------------------------
 TARGET_LMAX = 16
 
@@ -368,6 +394,7 @@ EXPORTS = [
     "cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted",
     "cbet_context_set_polarization", "cbet_context_polarization", "cbet_exchange_matrix_host_polarized",
     "cbet_context_set_bandwidth", "cbet_context_bandwidth", "cbet_exchange_matrix_host_banded",
+    "cbet_trace_paths",
 ]
 
 _lib = None
@@ -450,6 +477,8 @@ def lib(tolerate=()):
     L.cbet_cbet_workspace_gain.restype = vp
     L.cbet_trace_exits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
                                    C.POINTER(Params), C.POINTER(GainParams), vp, vp]
+    L.cbet_trace_paths.argtypes = [vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, dp, vp, vp, vp, vp, vp, vp,
+                                   C.c_double, C.c_double, C.c_double, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
     L.cbet_exit_tally.argtypes = [vp, C.c_long, C.c_int, vp, vp]
     L.cbet_farfield.argtypes = [vp, C.c_long, C.c_int, C.c_int, vp, vp]
     sph = [vp, C.c_int, C.c_long, C.POINTER(Params), dp, dp, C.c_int, C.c_int, vp, vp, vp, vp]
@@ -1084,6 +1113,39 @@ def exit_tally(exits, L, nbeams, tally, stream=None):
 def farfield(exits, n, ntheta, nphi, hist, stream=None):
     """cbet_farfield: the escaped rays' energy among n records ADDED into hist[ntheta][nphi]."""
     _check(lib().cbet_farfield(_addr(exits), n, ntheta, nphi, _addr(hist), _addr(stream)))
+
+
+# ---- ray path recorder (DESIGN.md section 22) --------------------------------------------------------------------------
+def path_items(beams, raynums):
+    """The item list of cbet_trace_paths as two contiguous int32 numpy arrays of one length, or ValueError: the arrays must
+    be one-dimensional, equally long, of an integer dtype, and hold values an int32 holds.  (Which VALUES name a ray is the
+    kernel's test: anything else is an idle item.)  No library call."""
+    out = []
+    for what, a in (("beams", beams), ("raynums", raynums)):
+        a = np.asarray(a)
+        if a.ndim != 1:
+            raise ValueError("%s must be one-dimensional, got shape %s" % (what, a.shape))
+        if a.size and a.dtype.kind not in "iu":        # (an empty list has no dtype to speak of)
+            raise ValueError("%s must hold integers, got dtype %s" % (what, a.dtype))
+        lim = np.iinfo(np.int32)
+        if a.size and (int(a.min()) < lim.min or int(a.max()) > lim.max):
+            raise ValueError("%s holds values outside the int32 range" % what)
+        out.append(np.ascontiguousarray(a, dtype=np.int32))
+    if out[0].size != out[1].size:
+        raise ValueError("beams and raynums differ in length: %d and %d" % (out[0].size, out[1].size))
+    return out[0], out[1]
+
+
+def trace_paths(ne3d, kappa3d, gain, beams, raynums, nitems, stride, capacity, center, samples, turns, bbeam_norm, beam_norm,
+                pow_r, phase_r, xconst, yconst, zconst, params, gain_params, ctx, stream=None):
+    """cbet_trace_paths: the rays (beams[k], raynums[k]) (device int32) traced with a sample every `stride` steps into
+    samples ([capacity][nitems] cbet_path_sample, device) and one closest-approach record each into turns ([nitems])."""
+    c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    _check(lib().cbet_trace_paths(
+        _addr(ne3d), _addr(kappa3d), _addr(gain), _addr(beams), _addr(raynums), nitems, stride, capacity,
+        c.ctypes.data_as(C.POINTER(C.c_double)), _addr(samples), _addr(turns), _addr(bbeam_norm), _addr(beam_norm),
+        _addr(pow_r), _addr(phase_r), xconst, yconst, zconst, C.byref(params),
+        C.byref(gain_params) if gain_params is not None else None, ctx.handle, _addr(stream)))
 
 
 # ---- mode spectra (cbet_sph_modes; DESIGN.md section 11) ------------------------------------------------------------

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcbet_mi355x.so")
-SOURCES = ["cbet_kernels.hip", "cbet_trace_window.hip", "cbet_trace_exit.hip", "cbet_grid_kernels.hip", "cbet_sph_modes.hip",
+SOURCES = ["cbet_kernels.hip", "cbet_trace_window.hip", "cbet_trace_exit.hip", "cbet_trace_path.hip", "cbet_grid_kernels.hip", "cbet_sph_modes.hip",
            "cbet_target.hip", "cbet_mesh.hip", "cbet_mesh_deposit.hip", "cbet_params.cpp", "cbet_context.cpp", "cbet_tables_abi.cpp", "cbet_trace_abi.cpp", "cbet_gain_abi.cpp",
            "cbet_host.cpp", "cbet_output.cpp", "cbet_sph_host.cpp", "cbet_target_host.cpp", "cbet_mesh_host.cpp", "cbet_mesh_deposit_host.cpp",
            "cbet_exchange_host.cpp"]

@@ -138,19 +138,39 @@ struct GainArgs {
     int nband;                              // M, the entries behind c_0: 1 .. CBET_MAX_BAND_LINES (CBET_MAX_BAND_LINES - 1) / 2; 0 with band == NULL
 };
 
+// What the path recorder (cbet_trace_path.hip) takes BESIDE TraceArgs, as a second by-value kernel
+// argument: TraceArgs keeps its members and their offsets, so no other kernel's code moves.
+struct PathArgs {
+    const int *beams, *raynums;             // device, nitems each: the rays to trace (cbet_trace_paths)
+    long nitems;
+    int nbeams, nrays;                      // an item is decoded only when 0 <= beam < nbeams and 0 <= raynum < nrays
+    int stride, capacity;                   // a sample every `stride` steps; samples m >= capacity are not written
+    double cx, cy, cz;                      // the centre of the closest approach
+    cbet_path_sample *samples;              // [capacity][nitems], sample-major
+    cbet_ray_turn *turns;                   // [nitems]
+    // bounds-audit builds (-DCBET_DEBUG_BOUNDS) only; unused otherwise: the ranges the two arrays' stores are checked against
+    const cbet_path_sample *audit_samples_lo, *audit_samples_hi;
+    const cbet_ray_turn *audit_turns_lo, *audit_turns_hi;
+};
+
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);
 hipError_t launch_step_table(const StepTableArgs &a, hipStream_t stream);
 hipError_t launch_plasma_records(const PlasmaRecordsArgs &a, hipStream_t stream);
 size_t plasma_records_lds(int nprofile);       // dynamic LDS of that launch, bytes
 hipError_t audit_violations(unsigned long long *out, bool reset, hipStream_t stream);
 // variant: CBET_KERNEL_GLOBAL_ATOMICS, _LDS_COMBINE (cbet_kernels.hip) or _LDS_WINDOW (cbet_trace_window.hip)
-hipError_t launch_trace(const TraceArgs &a, int variant, bool force_idx64, hipStream_t stream);
+// (path: the recorder's second block, variant kTracePaths only)
+hipError_t launch_trace(const TraceArgs &a, int variant, bool force_idx64, hipStream_t stream, const PathArgs *path = nullptr);
 hipError_t launch_trace_window(const TraceArgs &a, bool force_idx64, hipStream_t stream);
 // Exit pass (cbet_trace_exit.hip): launch_trace with variant kTraceExits runs it -- TraceArgs.edep is then the record array
 // as doubles and grid_stride = kExitDoubles * L -- after the bounds-audit set-up every trace gets.
 constexpr int kTraceExits = 100;
 constexpr int kExitDoubles = 10;                // sizeof(cbet_ray_exit) / sizeof(double)
 hipError_t launch_trace_exit(const TraceArgs &a, bool force_idx64, hipStream_t stream);
+// Path recorder (cbet_trace_path.hip): launch_trace with variant kTracePaths and the second block runs it, one wavefront
+// per 64 items of q, after the same bounds-audit set-up.
+constexpr int kTracePaths = 101;
+hipError_t launch_trace_path(const TraceArgs &a, const PathArgs &q, bool force_idx64, hipStream_t stream);
 hipError_t launch_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, hipStream_t stream);
 hipError_t launch_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, hipStream_t stream);
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream);

@@ -188,6 +188,7 @@ struct CbetHooks {
     double *beam_gain = nullptr;
     double max_exponent = 0.0;
     bool exits = false;     // the exit pass (cbet_trace_exits): `edep` is the record array, no deposit
+    const PathArgs *paths = nullptr;   // the path recorder (cbet_trace_paths): its second block; `edep` is the turn records, no deposit
 };
 int trace_impl(int b, unsigned nindices, const double *ne3d, const double *kappa3d, double *edep, const double *bbeam_norm,
                const double *beam_norm, const double *pow_r, const double *phase_r, double xconst, double yconst,

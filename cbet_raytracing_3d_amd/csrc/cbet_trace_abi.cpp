@@ -1,6 +1,9 @@
 // cbet_trace_abi.cpp -- the trace launch of the C ABI (include/cbet_mi355x.h): trace_impl, which every ray-tracing entry
-// goes through, its wrappers (plain, reference-shaped, exit pass) and the small kernels that consume a trace's output.
+// goes through, its wrappers (plain, reference-shaped, exit pass, path recorder) and the small kernels that consume a trace's output.
 // Citations are into /root/reference/.
+#include <climits>
+#include <cmath>
+
 #include "cbet_host_internal.h"
 
 using namespace cbet;
@@ -28,7 +31,8 @@ int cbet::trace_impl(int b, unsigned nindices, const double *ne3d, const double 
     }
     if (beam_lo < 0 || beam_hi > p->nbeams || beam_hi < beam_lo)
         return fail(CBET_EINVAL, "beam range [%d,%d) outside [0,%d)", beam_lo, beam_hi, p->nbeams);
-    if (beam_hi == beam_lo || ctx->nlive == 0) return CBET_OK;
+    // (the recorder's rays are its caller's list, not the context's)
+    if (beam_hi == beam_lo || (ctx->nlive == 0 && !hooks.paths)) return CBET_OK;
 
     int variant = p->kernel_variant;
     if (variant == CBET_KERNEL_DEFAULT) variant = CBET_KERNEL_LDS_WINDOW;
@@ -94,7 +98,8 @@ int cbet::trace_impl(int b, unsigned nindices, const double *ne3d, const double 
         if (int rc = step_records(ctx, p, ne3d, kappa3d, xconst, yconst, zconst, stream, false)) return rc;
         a.steprec = ctx->steprec;
     }
-    CBET_HIP(launch_trace(a, hooks.exits ? kTraceExits : variant, p->force_wide_index != 0, (hipStream_t)stream));
+    CBET_HIP(launch_trace(a, hooks.paths ? kTracePaths : hooks.exits ? kTraceExits : variant, p->force_wide_index != 0,
+                          (hipStream_t)stream, hooks.paths));
     return CBET_OK;
 }
 
@@ -161,6 +166,62 @@ int cbet_trace_exits(const double *ne3d, const double *kappa3d, const double *ga
     h.gain = gain; h.max_exponent = g ? g->max_exponent : 0.0; h.exits = true;
     return trace_impl(0, (unsigned)ctx->d.nindices, ne3d, kappa3d, reinterpret_cast<double *>(exits), bbeam_norm,
                       beam_norm, pow_r, phase_r, xconst, yconst, zconst, &q, ctx, stream, h);
+}
+
+// ---- path recorder --------------------------------------------------------------
+int cbet_trace_paths(const double *ne3d, const double *kappa3d, const double *gain, const int *beams, const int *raynums,
+                     long nitems, int stride, int capacity, const double *center, cbet_path_sample *samples,
+                     cbet_ray_turn *turns, const double *bbeam_norm, const double *beam_norm, const double *pow_r,
+                     const double *phase_r, double xconst, double yconst, double zconst, const cbet_params *p,
+                     const cbet_gain_params *g, cbet_context *ctx, void *stream)
+{
+    if (int rc = validate(p)) return rc;
+    // the argument checks: before the context and before any HIP call
+    if (stride < 1) return fail(CBET_EINVAL, "cbet_trace_paths: stride = %d, must be >= 1", stride);
+    if (capacity < 0) return fail(CBET_EINVAL, "cbet_trace_paths: capacity = %d, must be >= 0", capacity);
+    if (nitems < 0) return fail(CBET_EINVAL, "cbet_trace_paths: nitems = %ld, must be >= 0", nitems);
+    {
+        const long per_item = capacity > 1 ? capacity : 1, max_records = LONG_MAX / (long)sizeof(cbet_path_sample);
+        if (nitems > max_records / per_item)
+            return fail(CBET_EINVAL, "cbet_trace_paths: nitems = %ld times capacity = %d records overflow a 64-bit byte count", nitems,
+                        capacity);
+        if ((nitems + kWave - 1) / kWave > (long)INT_MAX)
+            return fail(CBET_EINVAL, "cbet_trace_paths: nitems = %ld is more than one launch takes (2^31 - 1 wavefronts of 64)", nitems);
+    }
+    if (!turns) return fail(CBET_EINVAL, "cbet_trace_paths: NULL turn-record array");
+    if (nitems > 0 && (!beams || !raynums)) return fail(CBET_EINVAL, "cbet_trace_paths: NULL beams / raynums with nitems = %ld", nitems);
+    if (capacity > 0 && !samples) return fail(CBET_EINVAL, "cbet_trace_paths: NULL sample array with capacity = %d", capacity);
+    if (!center) return fail(CBET_EINVAL, "cbet_trace_paths: NULL center");
+    if (!std::isfinite(center[0]) || !std::isfinite(center[1]) || !std::isfinite(center[2]))
+        return fail(CBET_EINVAL, "cbet_trace_paths: center is not finite");
+    if (p->absorption != 1)
+        return fail(CBET_EINVAL, "cbet_trace_paths: the recorder needs absorbing mode (absorption = 1): in bookkeeping mode the increment is no energy loss");
+    if (gain && !g) return fail(CBET_EINVAL, "cbet_trace_paths: a gain grid needs gain params (max_exponent)");
+    if (g) {
+        if (int rc = validate_gain(p, g)) return rc;
+    }
+    if (!ctx) return fail(CBET_EINVAL, "NULL context");
+    if (nitems == 0) return CBET_OK;
+    // the trace's own checks and set-up (geometry, step records), as the exit pass takes them; the beam range, the shard
+    // split, the beam-resolved arrays' range and the deposit-grid options do not apply
+    cbet_params q = *p;
+    q.kernel_variant = CBET_KERNEL_LDS_WINDOW;
+    q.per_beam_grids = 0;
+    q.edep_zpitch = 0;
+    q.window_stats = 0;
+    q.beam_lo = 0; q.beam_hi = q.nbeams;
+    q.shard_index = 0; q.shard_count = 1;
+    q.grid_beam0 = 0; q.grid_beams = 0;
+    PathArgs path{};
+    path.beams = beams; path.raynums = raynums; path.nitems = nitems;
+    path.nbeams = p->nbeams; path.nrays = ctx->d.nrays;
+    path.stride = stride; path.capacity = capacity;
+    path.cx = center[0]; path.cy = center[1]; path.cz = center[2];
+    path.samples = samples; path.turns = turns;
+    CbetHooks h;
+    h.gain = gain; h.max_exponent = g ? g->max_exponent : 0.0; h.paths = &path;
+    return trace_impl(0, (unsigned)ctx->d.nindices, ne3d, kappa3d, reinterpret_cast<double *>(turns), bbeam_norm, beam_norm,
+                      pow_r, phase_r, xconst, yconst, zconst, &q, ctx, stream, h);
 }
 
 int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, void *stream)

@@ -1,5 +1,5 @@
 // cbet_trace_common.h -- what the ray-integrator kernels share, each piece of a ray step stated once (cbet_kernels.hip: the two
-// cross-check formulations; cbet_trace_window.hip: the shipped one; cbet_trace_exit.hip: the exit pass).  Citations are into /root/reference/.
+// cross-check formulations; cbet_trace_window.hip: the shipped one; cbet_trace_exit.hip: the exit pass; cbet_trace_path.hip: the path recorder).  Citations are into /root/reference/.
 // Everything here is compiled with -ffp-contract=off: one IEEE operation per reference statement.
 #ifndef CBET_TRACE_COMMON_H_
 #define CBET_TRACE_COMMON_H_

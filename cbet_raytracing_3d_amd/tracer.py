@@ -608,6 +608,66 @@ class RayTracer:
             api.farfield(exits[b], L, ntheta, nphi, hist, stream)
         return hist
 
+    # ---- ray path recorder (include/cbet_mi355x.h cbet_trace_paths) ---------------------------
+    def ray_items(self, beams=None, bundles=False):
+        """(beams, raynums), int32 numpy arrays: every live ray (ray_ids() >= 0) of the beams listed (default: all),
+        beam by beam -- the item list of trace_paths for a whole fan.  bundles=True keeps the launch list's idle entries
+        (raynum -1, an idle item with a zero turn record), so that every 64 items are one ray bundle of the deposit pass
+        -- neighbouring rays that end together -- and a wavefront of the recorder is a wavefront of the exit pass."""
+        ids = self.ray_ids()
+        live = np.ascontiguousarray(ids if bundles else ids[ids >= 0], dtype=np.int32)
+        which = np.arange(self.params.nbeams) if beams is None else np.asarray(list(beams), dtype=np.int64).reshape(-1)
+        if which.size and (which.min() < 0 or which.max() >= self.params.nbeams):
+            raise ValueError("beams outside [0, %d)" % self.params.nbeams)
+        return np.repeat(which.astype(np.int32), live.size), np.tile(live, which.size)
+
+    def new_paths(self, nitems, capacity):
+        """Zeroed records for trace_paths: samples float64 [capacity, nitems, 8] (cbet_path_sample: x, y, z, uray, absorbed,
+        gained, then ci, cj / ck, step as int32 pairs in columns 6, 7) and turns float64 [nitems, 8] (cbet_ray_turn: r2, x,
+        y, z, uray, ne, then step, steps / status, nsamples).  Downloaded, .view(api.PATH_DTYPE)[..., 0] and
+        .view(api.TURN_DTYPE)[..., 0] name the fields."""
+        f64 = dict(dtype=torch.float64, device=self.device)
+        return torch.zeros((capacity, nitems, 8), **f64), torch.zeros((nitems, 8), **f64)
+
+    def trace_paths(self, beams, raynums, stride=1, capacity=None, center=(0.0, 0.0, 0.0), gain=None, gain_params=None,
+                    tabulate=True, out=None):
+        """The path recorder on torch's current stream: the rays (beams[k], raynums[k]) -- raynums as in ray_ids() --
+        traced as the exit pass traces them, a sample every `stride` steps and one closest-approach record (to `center`,
+        cm) per ray.  Ids that name no live ray are idle items: an all-zero turn record, no samples.  capacity: samples
+        kept per ray; the default 1 + ceil(nt / stride) never truncates, 0 means turn records only.  gain, gain_params,
+        tabulate: as trace_exits takes them.  out: (samples, turns) from new_paths to write into (samples may be None with
+        capacity 0); slots the call does not write keep what they hold.  Returns (samples, turns); samples is
+        sample-major, samples.permute(1, 0, 2) is the ray-major view, and turns' `ne` over derived.ncrit is the density
+        at the closest approach in critical densities."""
+        beams, raynums = api.path_items(beams, raynums)
+        nitems = int(beams.size)
+        if stride < 1:
+            raise ValueError("stride must be >= 1")
+        if capacity is None:
+            capacity = 1 + -(-self.derived.nt // stride)
+        if capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        if out is None:
+            samples, turns = self.new_paths(nitems, capacity)
+        else:
+            samples, turns = out
+            _require(turns, (nitems, 8), "turns (new_paths())")
+            if samples is not None or capacity > 0:
+                _require(samples, (capacity, nitems, 8), "samples (new_paths())")
+        if gain is not None:
+            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
+            if gain_params is None:
+                gain_params = api.default_gain_params()
+        if nitems == 0:                 # (empty tensors have no address to hand over)
+            return samples, turns
+        if tabulate:
+            self.tabulate()
+        d_beams, d_raynums = torch.from_numpy(beams).to(self.device), torch.from_numpy(raynums).to(self.device)
+        api.trace_paths(None, None, gain, d_beams, d_raynums, nitems, stride, capacity, center,
+                        samples if capacity > 0 else None, turns, *self._tail(), self.params, gain_params, self.ctx,
+                        self._stream())
+        return samples, turns
+
     # ---- mode spectra (include/cbet_mi355x.h cbet_sph_modes; DESIGN.md section 11) ----------------------------------
     def sph_modes(self, grid, r_edges=None, lmax=16, center=(0.0, 0.0, 0.0), geometry=False):
         """Real spherical-harmonic coefficients of a deposit grid on shells, on torch's current stream.  grid: one grid

@@ -993,6 +993,80 @@ int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tall
  */
 int cbet_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, void *stream);
 
+/* ---- ray path recorder -------------------------------------------------------- */
+/*
+ * Single rays made visible: sampled trajectories and one closest-approach record per ray, for an explicit list of rays.
+ *
+ * Items.  beams[nitems] and raynums[nitems] are int32 DEVICE arrays; item k is the ray with thread-ray id raynums[k]
+ * (the ids of cbet_live_ray_list, launch_ray_XZ.cu:125,156) of beam beams[k].  An item is TRACED when
+ *     0 <= beam < p->nbeams,   0 <= raynum < cbet_derived.nrays,   and the launch accepts the ray (:94,114: the launch
+ *     point lies inside the beam radius).
+ * Every other item is an idle lane: its turn record is all zeros (status 0) and it writes no sample.  The kernel makes
+ * that test itself, so a list may hold anything.  Which ids are safe: the launch decodes an id into the ray's column and
+ * row of the beam cross-section (:70-73), tile = id / rpz^2, within = id % rpz^2, row = tile / zones * rpz + within / rpz,
+ * column = tile % zones * rpz + within % rpz, with nrays = nrays_x * nrays_y, nrays_x = rpz * zones and nrays_y =
+ * rpz * zones_y.  For 0 <= id < nrays: tile < zones * zones_y, so row < nrays_y and column < nrays_x -- EVERY id in
+ * [0, nrays) indexes the two launch axes (nrays_x and nrays_y entries) in range, whether or not the launch shape of
+ * max_threads visits it; ids outside that interval are never decoded.  Ids the launch rule leaves out may be traced: the
+ * list is the caller's.  One wavefront takes 64 consecutive items.
+ *
+ * Samples.  Sample 0 is the launch state: the launch point, uray0, absorbed = gained = 0, the launch node, step 0.
+ * Sample m >= 1 is the state after step min(m * stride, steps); a ray of `steps` steps has nsamples = 1 +
+ * ceil(steps / stride) samples and its last sample is always its end state.  Storage is SAMPLE-major:
+ * samples[m * nitems + k] is sample m of item k, capacity * nitems records.  Samples with m >= capacity are not written,
+ * and nothing is ever written outside [0, capacity); slots the call does not write (samples a ray does not have, idle
+ * items) are left as they are.
+ */
+typedef struct cbet_path_sample {
+    double x, y, z;       /* position (cm)                                                                       */
+    double uray;          /* energy the ray carries (after the step's gain and absorption)                       */
+    double absorbed;      /* energy absorbed in the steps since the previous sample, summed in step order        */
+    double gained;        /* energy gained through CBET in those steps, summed in step order (0 without a gain)  */
+    int ci, cj, ck;       /* the ray's node (the reference's cell, after the nearest-node update)                */
+    int step;             /* 0 = launch point; t = state after step t                                            */
+} cbet_path_sample;       /* 64 bytes */
+/*
+ * Turn records, one per item: the ray's closest approach to `center`, over the launch point and the position after every
+ * step, with r2 evaluated exactly as
+ *     r2 = ((x - cx) * (x - cx) + (y - cy) * (y - cy)) + (z - cz) * (z - cz)
+ * (that parenthesisation, no fused multiply-add).  The FIRST minimum wins: a later position replaces the record only when
+ * its r2 is strictly smaller.
+ */
+typedef struct cbet_ray_turn {
+    double r2;            /* smallest squared distance to `center` (cm^2)                                        */
+    double x, y, z;       /* position there                                                                      */
+    double uray;          /* energy there (as in the sample of that step)                                        */
+    double ne;            /* ne3d at the ray's node there: the node table's entry, cm^-3                         */
+    int step;             /* where: 0 = launch point, t = after step t                                           */
+    int steps, status;    /* as cbet_ray_exit.steps / .status (CBET_RAY_* bits); status 0 = idle item            */
+    int nsamples;         /* 1 + ceil(steps / stride), whether or not `capacity` held them                       */
+} cbet_ray_turn;          /* 64 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cbet_path_sample) == 64 && sizeof(cbet_ray_turn) == 64, "path records are 64 bytes");
+#else
+_Static_assert(sizeof(cbet_path_sample) == 64 && sizeof(cbet_ray_turn) == 64, "path records are 64 bytes");
+#endif
+/*
+ * The recorder: the exit pass's integrator (a traced ray's positions, nodes, energies, step count and status are that
+ * pass's, bit for bit) on the items of the list.  stride >= 1, capacity >= 0 (0: turn records only; samples may then be
+ * NULL), center = three finite doubles (cm).  samples: device [capacity][nitems]; turns: device [nitems], every entry
+ * written.  ne3d / kappa3d NULL = the context's own tables and step records, as in cbet_trace_exits.  gain: device
+ * [nbeams][(nx+2)(ny+2)(nz+2)] indexed by the ITEM's beam, or NULL; with it every step applies the CBET hook (g supplies
+ * max_exponent).  The hook's choice of series is a vote of the wavefront, so with a gain a ray's last bits may depend on
+ * the 63 items beside it; without one, an item's records depend on neither its place in the list nor its neighbours.
+ * Absorbing mode only.  The beam range, the shard split, grid_beam0 / grid_beams, kernel_variant and the per-beam-grid
+ * options of *p do not apply.  The context's counters are not touched.  nitems == 0 succeeds and launches nothing.
+ * CBET_EINVAL, naming the offence, judged before the context and before any device call: stride < 1; capacity < 0;
+ * nitems < 0, or nitems * max(capacity, 1) records beyond what a 64-bit byte count holds (or more items than one launch
+ * takes, 2^31 - 1 wavefronts); NULL turns, NULL beams / raynums with nitems > 0, NULL samples with capacity > 0; a
+ * non-finite center; non-absorbing mode; a gain grid without gain params.  Enqueued on `stream`, no synchronisation.
+ */
+int cbet_trace_paths(const double *ne3d, const double *kappa3d, const double *gain, const int *beams, const int *raynums,
+                     long nitems, int stride, int capacity, const double *center, cbet_path_sample *samples,
+                     cbet_ray_turn *turns, const double *bbeam_norm, const double *beam_norm, const double *pow_r,
+                     const double *phase_r, double xconst, double yconst, double zconst, const cbet_params *p,
+                     const cbet_gain_params *g, cbet_context *ctx, void *stream);
+
 /* ---- mode spectra of the deposit ---------------------------------------------------------- */
 /*
  * How uniformly the energy is deposited around a centre: the real spherical-harmonic coefficients of each grid on
