@@ -139,6 +139,28 @@ int cbet_edep_average_device(const double *edep, double *edepavg, int nx, int ny
     return CBET_OK;
 }
 
+// ---- the no-deposit passes: exit pass and path recorder ------------------------------------------------
+// Absorbing mode and the gain arguments.  `prefix` and `pass` are the entry's own words in the messages.
+static int no_deposit_checks(const char *prefix, const char *pass, const double *gain, const cbet_params *p, const cbet_gain_params *g)
+{
+    if (p->absorption != 1)
+        return fail(CBET_EINVAL, "%sthe %s needs absorbing mode (absorption = 1): in bookkeeping mode the increment is no energy loss", prefix, pass);
+    if (gain && !g) return fail(CBET_EINVAL, "%sa gain grid needs gain params (max_exponent)", prefix);
+    return g ? validate_gain(p, g) : CBET_OK;
+}
+
+// The parameters such a pass hands to trace_impl for the trace's own checks and set-up (geometry, beam range against
+// grid_beam0 / grid_beams, shards, step records): the deposit-grid options do not apply.
+static cbet_params no_deposit_params(const cbet_params *p)
+{
+    cbet_params q = *p;
+    q.kernel_variant = CBET_KERNEL_LDS_WINDOW;
+    q.per_beam_grids = 0;
+    q.edep_zpitch = 0;
+    q.window_stats = 0;
+    return q;
+}
+
 // ---- exit pass ---------------------------------------------------------------
 int cbet_trace_exits(const double *ne3d, const double *kappa3d, const double *gain, cbet_ray_exit *exits,
                      const double *bbeam_norm, const double *beam_norm, const double *pow_r, const double *phase_r,
@@ -148,19 +170,8 @@ int cbet_trace_exits(const double *ne3d, const double *kappa3d, const double *ga
     if (int rc = validate(p)) return rc;
     if (!ctx) return fail(CBET_EINVAL, "NULL context");
     if (!exits) return fail(CBET_EINVAL, "NULL exit-record array");
-    if (p->absorption != 1)
-        return fail(CBET_EINVAL, "the exit pass needs absorbing mode (absorption = 1): in bookkeeping mode the increment is no energy loss");
-    if (gain && !g) return fail(CBET_EINVAL, "a gain grid needs gain params (max_exponent)");
-    if (g) {
-        if (int rc = validate_gain(p, g)) return rc;
-    }
-    // the trace's own checks and set-up (geometry, beam range against grid_beam0 / grid_beams, shards, step records);
-    // the deposit-grid options do not apply
-    cbet_params q = *p;
-    q.kernel_variant = CBET_KERNEL_LDS_WINDOW;
-    q.per_beam_grids = 0;
-    q.edep_zpitch = 0;
-    q.window_stats = 0;
+    if (int rc = no_deposit_checks("", "exit pass", gain, p, g)) return rc;
+    cbet_params q = no_deposit_params(p);
     if (q.beam_hi < 0) { q.beam_lo = 0; q.beam_hi = q.nbeams; }
     CbetHooks h;
     h.gain = gain; h.max_exponent = g ? g->max_exponent : 0.0; h.exits = true;
@@ -194,21 +205,11 @@ int cbet_trace_paths(const double *ne3d, const double *kappa3d, const double *ga
     if (!center) return fail(CBET_EINVAL, "cbet_trace_paths: NULL center");
     if (!std::isfinite(center[0]) || !std::isfinite(center[1]) || !std::isfinite(center[2]))
         return fail(CBET_EINVAL, "cbet_trace_paths: center is not finite");
-    if (p->absorption != 1)
-        return fail(CBET_EINVAL, "cbet_trace_paths: the recorder needs absorbing mode (absorption = 1): in bookkeeping mode the increment is no energy loss");
-    if (gain && !g) return fail(CBET_EINVAL, "cbet_trace_paths: a gain grid needs gain params (max_exponent)");
-    if (g) {
-        if (int rc = validate_gain(p, g)) return rc;
-    }
+    if (int rc = no_deposit_checks("cbet_trace_paths: ", "recorder", gain, p, g)) return rc;
     if (!ctx) return fail(CBET_EINVAL, "NULL context");
     if (nitems == 0) return CBET_OK;
-    // the trace's own checks and set-up (geometry, step records), as the exit pass takes them; the beam range, the shard
-    // split, the beam-resolved arrays' range and the deposit-grid options do not apply
-    cbet_params q = *p;
-    q.kernel_variant = CBET_KERNEL_LDS_WINDOW;
-    q.per_beam_grids = 0;
-    q.edep_zpitch = 0;
-    q.window_stats = 0;
+    // ... and here the beam range, the shard split and the beam-resolved arrays' range do not apply either
+    cbet_params q = no_deposit_params(p);
     q.beam_lo = 0; q.beam_hi = q.nbeams;
     q.shard_index = 0; q.shard_count = 1;
     q.grid_beam0 = 0; q.grid_beams = 0;

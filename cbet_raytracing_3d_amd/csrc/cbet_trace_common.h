@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "cbet_device.h"
 #include "cbet_relocate.h"
 
@@ -285,8 +287,8 @@ __device__ __forceinline__ double sqrt_speed(double v2)
     return __builtin_fma(__builtin_fma(-g, g, v2), h, g);
 }
 
-// ---- the CBET hook of a step: k_trace_window<., ., CBET >= 1> (the deposit passes) and k_trace_exit<true, .> (the exit pass)
-// both call the three functions below, so a ray's exit energy is what the deposition pass leaves it by construction
+// ---- the CBET hook of a step: k_trace_window<., ., CBET >= 1> (the deposit passes) and ray_step<true, ., .> (the exit pass and
+// the path recorder) both call the three functions below, so a ray's exit energy is what the deposition pass leaves it by construction
 // The two factors of an axis are d = 1 - |o| and 1 - d (:329-336); which of them comes first is the lane's
 // flip bit.  Without selects: F0 = +-(|o| - h), h = 1.0 with the sign flipped for a flipped lane (exactly
 // d), h = 0.0 otherwise (|o| itself: the reference's 1 - (1 - |o|) up to 1.1e-16), F1 = 1 - F0 (exactly
@@ -329,6 +331,116 @@ __device__ __forceinline__ double gain_exponent(const TraceArgs &a, const double
 // phi(x) of the hook by the wave's vote (the caller's ballot, masked with ITS live lanes): phi_small when every live lane's |x| < kPhiSmallBelow
 constexpr double kPhiSmallBelow = 0.03125;
 __device__ __forceinline__ double gain_phi(double x, bool wave_is_small) { return wave_is_small ? phi_small(x) : phi_det(x); }
+
+// ---- the step of the no-deposit integrators: k_trace_exit (the exit pass) and k_trace_path (the path recorder) both call
+// ray_step below, so a ray's position, node, energy, step count and status are the same in both by construction
+// The step record (cbet_device.h StepRecord) of node `cell`: a 32-byte gather.  IDX64 = false: the table is at most
+// 2^32 bytes, so the byte offset is a 32-bit one (scalar base + vector offset).
+template <bool IDX64>
+__device__ __forceinline__ StepRecord load_record(const TraceArgs &a, unsigned cell)
+{
+#ifdef CBET_DEBUG_BOUNDS
+    if (!(cell < a.audit_nodes)) { audit_fail(a); return StepRecord{0.0, 0.0, 0.0, 0.0}; }
+#endif
+    if (IDX64) return a.steprec[cell];
+    return *reinterpret_cast<const StepRecord *>(reinterpret_cast<const char *>(a.steprec) + (cell << 5));
+}
+
+// What a lane's steps do not change, built once in front of the loop: the grid's sides, the haloed gain grid's strides, the
+// shipped kernel's lane flips (cbet_trace_window.hip: which of an axis's two nodes the lane takes first, from the lane
+// index) and the lane's gain grid (GAIN only).
+struct StepFrame {
+    int nx, ny, nz, sXh, sYh;
+    int pfx, pfy, pfz;
+    const double *gk;
+};
+__device__ __forceinline__ StepFrame step_frame(const TraceArgs &a, int lane, const double *gk)
+{
+    return StepFrame{a.nx, a.ny, a.nz, a.sXh, a.sYh, lane & 1, (lane >> 1) & 1, (lane >> 3) & 1, gk};
+}
+__device__ __forceinline__ unsigned node_of(const StepFrame &f, const Ray &s) { return (unsigned)((s.ci * f.ny + s.cj) * f.nz + s.ck); }
+
+// One step of a wave (/root/reference/launch_ray_XZ.cu:268-356).  The call is wave-uniform -- the hook votes with a ballot --
+// and only lanes with `alive` step: kick from `rec`, drift, nearest-node update, the new node `cell` and its record into
+// `rec`; GAIN: the CBET hook of k_trace_window<16, ., 1> before the absorption, its energy added to `gained`; the absorption
+// (absorbing mode only: checked on the host), ABSORBED: added to `absorbed`; the stop test against the six `planes`, which
+// the caller chooses how to read.  Returns stop_test's bits, 0 for a ray that goes on and for a lane that did not step.
+template <bool GAIN, bool IDX64, bool ABSORBED>
+__device__ __forceinline__ int ray_step(const TraceArgs &a, const StepFrame &f, const double *planes, bool alive, Ray &s, StepRecord &rec,
+                                        unsigned &cell, double &absorbed, double &gained)
+{
+    double x = 0.0;                                       // GAIN: the clamped exponent K ds of the step
+    if (alive) {
+        // :268-278 kick, drift, position in cell units
+        s.vx -= rec.kx;
+        s.vy -= rec.ky;
+        s.vz -= rec.kz;
+        double fx, fy, fz;
+        drift(a, s, fx, fy, fz);
+        // :282-292 nearest-node update
+        s.ci = relocate_closed(s.ci, fx, f.nx);
+        s.cj = relocate_closed(s.cj, fy, f.ny);
+        s.ck = relocate_closed(s.ck, fz, f.nz);
+        // :296-305 the absorption coefficient now, the kicks of the next step
+        cell = node_of(f, s);
+        rec = load_record<IDX64>(a, cell);
+        if (GAIN) {
+            // K at the eight deposit nodes with the deposit weights (:319-339)
+            const double ox = (fx - (double)s.ci) - 0.5, oy = (fy - (double)s.cj) - 0.5, oz = (fz - (double)s.ck) - 0.5;
+            const bool ngx = ox < 0, ngy = oy < 0, ngz = oz < 0;
+            const int lx = s.ci + 1 - (ngx ? 1 : 0), ly = s.cj + 1 - (ngy ? 1 : 0), lz = s.ck + 1 - (ngz ? 1 : 0);
+            const bool hx = ngx != (f.pfx != 0), hy = ngy != (f.pfy != 0), hz = ngz != (f.pfz != 0);
+            const int X0 = lx + (hx ? 1 : 0), X1 = lx + (hx ? 0 : 1);
+            const int Y0 = ly + (hy ? 1 : 0), Y1 = ly + (hy ? 0 : 1);
+            const int Z0 = lz + (hz ? 1 : 0), Z1 = lz + (hz ? 0 : 1);
+            double Fx0, Fx1, Fy0, Fy1, Fz0, Fz1;
+            factor_pair(ox, f.pfx, Fx0, Fx1);
+            factor_pair(oy, f.pfy, Fy0, Fy1);
+            factor_pair(oz, f.pfz, Fz0, Fz1);
+            const double ds = sqrt_speed(__builtin_fma(s.vz, s.vz, __builtin_fma(s.vy, s.vy, s.vx * s.vx))) * a.dt;
+            x = gain_exponent<IDX64>(a, f.gk, X0, X1, Y0, Y1, Z0, Z1, Fx0, Fx1, Fy0, Fy1, Fz0, Fz1, f.sXh, f.sYh, ds);
+        }
+    }
+    if (GAIN) {
+        const bool small = __builtin_amdgcn_ballot_w64(alive && !(fabs(x) < kPhiSmallBelow)) == 0ull;
+        if (alive) {
+            const double phi = gain_phi(x, small);
+            const double dg = s.uray * (x * phi);
+            gained += dg;
+            s.uray = s.uray + dg;
+        }
+    }
+    int end = 0;
+    if (alive) {
+        const double inc = rec.kap * s.uray;              // :305-311
+        s.uray -= inc;
+        if (ABSORBED) absorbed += inc;
+        end = stop_test(s, planes);                       // :351-356; the bits say which of its conditions held
+    }
+    return end;
+}
+
+// ... and their launch.  Wide (64-bit) indexing: forced, a step-record table beyond 2^32 bytes, or a gain grid of 2^32 bytes.
+inline bool wide_index(const TraceArgs &a, bool force_idx64)
+{
+    return force_idx64 || sizeof(StepRecord) * (unsigned long long)a.nx * a.ny * a.nz > (1ull << 32) ||
+           (a.gain && 8ull * (unsigned long long)a.hsize >= (1ull << 32));
+}
+// The GAIN x IDX64 instantiation a launch needs: launch(gain, wide) gets the two as std::bool_constant values and launches
+// k<gain, wide> -- a generic lambda, since a kernel template cannot be passed by name.
+template <class Launch>
+hipError_t launch_gain_by_index(const TraceArgs &a, bool force_idx64, Launch launch)
+{
+    const bool wide = wide_index(a, force_idx64);
+    if (a.gain) {
+        if (wide) launch(std::true_type{}, std::true_type{});
+        else launch(std::true_type{}, std::false_type{});
+    } else {
+        if (wide) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
+    return hipGetLastError();
+}
 
 // The work item of workgroup `w` of a launch: which (beam, patch) bundle.  The list is beam-major -- consecutive
 // workgroups are neighbouring patches of one beam and share table lines in L2/MALL -- with each beam's patches

@@ -9,6 +9,8 @@
 //     the stop test of :351-356.  When the ray ends -- in the step where that test first holds, or after nt steps --
 //     its lane writes one cbet_ray_exit record.  GAIN: the CBET hook of k_trace_window<16, ., 1> -- that kernel's own code,
 //     cbet_trace_common.h -- before the absorption, so that a ray's exit energy is what the CBET deposition pass leaves it.
+//     The step is one function, ray_step of cbet_trace_common.h, which the path recorder (cbet_trace_path.hip) calls too;
+//     what is here is the kernel's own: the bundle prologue, the exit record, the counters.
 //   * k_exit_tally  : per-beam energy balance of the records, one workgroup per beam, fixed summation order (no atomics:
 //     bit-reproducible from run to run).
 //   * k_farfield    : the escaped rays' energy binned by exit direction (equal solid angle per polar bin), ADDED into a
@@ -26,18 +28,6 @@ static_assert(sizeof(cbet_ray_exit) == kExitDoubles * sizeof(double), "kExitDoub
 
 namespace {
 
-// The step record (cbet_device.h StepRecord) of node `cell`: a 32-byte gather.  IDX64 = false: the table is at most
-// 2^32 bytes, so the byte offset is a 32-bit one (scalar base + vector offset).
-template <bool IDX64>
-__device__ __forceinline__ StepRecord load_record(const TraceArgs &a, unsigned cell)
-{
-#ifdef CBET_DEBUG_BOUNDS
-    if (!(cell < a.audit_nodes)) { audit_fail(a); return StepRecord{0.0, 0.0, 0.0, 0.0}; }
-#endif
-    if (IDX64) return a.steprec[cell];
-    return *reinterpret_cast<const StepRecord *>(reinterpret_cast<const char *>(a.steprec) + (cell << 5));
-}
-
 template <bool GAIN, bool IDX64>
 __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
 {
@@ -51,69 +41,23 @@ __global__ void __launch_bounds__(kWave) k_trace_exit(const TraceArgs a)
     const bool has_slot = li < a.nlive;                   // (a record for every slot of the list, idle lanes' too)
     const double uray0 = s.uray;                          // :113
 
-    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    // (a beam's bundle: one gain grid for the wave)
+    const StepFrame f = step_frame(a, lane, GAIN ? a.gain + (long)(beam - a.grid_beam0) * a.hsize : nullptr);
     StepRecord rec = {0.0, 0.0, 0.0, 0.0};
-    if (launched) rec = load_record<IDX64>(a, (unsigned)((s.ci * ny + s.cj) * nz + s.ck));   // :254-270 at the launch node
-
-    const double *const gk = GAIN ? a.gain + (long)(beam - a.grid_beam0) * a.hsize : nullptr;
-    const int sYh = a.sYh, sXh = a.sXh;
-    // the shipped kernel's lane flips (cbet_trace_window.hip): which of an axis's two nodes the lane takes first
-    const int pfx = lane & 1, pfy = (lane >> 1) & 1, pfz = (lane >> 3) & 1;
-    double gained = 0.0;
+    unsigned cell = 0;
+    if (launched) rec = load_record<IDX64>(a, node_of(f, s));   // :254-270 at the launch node
+    double absorbed = 0.0, gained = 0.0;                  // (absorbed: not taken, the records give it as a difference)
 
     bool alive = launched;
     int steps = 0, status = 0;
     for (int tt = 0; tt < a.nt; ++tt) {                   // :207
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;
-        double x = 0.0;                                   // GAIN: the clamped exponent K ds of the step
-        if (alive) {
-            // :268-278 kick, drift, position in cell units
-            s.vx -= rec.kx;
-            s.vy -= rec.ky;
-            s.vz -= rec.kz;
-            double fx, fy, fz;
-            drift(a, s, fx, fy, fz);
-            // :282-292 nearest-node update
-            s.ci = relocate_closed(s.ci, fx, nx);
-            s.cj = relocate_closed(s.cj, fy, ny);
-            s.ck = relocate_closed(s.ck, fz, nz);
-            // :296-305 the absorption coefficient now, the kicks of the next step
-            rec = load_record<IDX64>(a, (unsigned)((s.ci * ny + s.cj) * nz + s.ck));
-            if (GAIN) {
-                // K at the eight deposit nodes with the deposit weights (:319-339)
-                const double ox = (fx - (double)s.ci) - 0.5, oy = (fy - (double)s.cj) - 0.5, oz = (fz - (double)s.ck) - 0.5;
-                const bool ngx = ox < 0, ngy = oy < 0, ngz = oz < 0;
-                const int lx = s.ci + 1 - (ngx ? 1 : 0), ly = s.cj + 1 - (ngy ? 1 : 0), lz = s.ck + 1 - (ngz ? 1 : 0);
-                const bool hx = ngx != (pfx != 0), hy = ngy != (pfy != 0), hz = ngz != (pfz != 0);
-                const int X0 = lx + (hx ? 1 : 0), X1 = lx + (hx ? 0 : 1);
-                const int Y0 = ly + (hy ? 1 : 0), Y1 = ly + (hy ? 0 : 1);
-                const int Z0 = lz + (hz ? 1 : 0), Z1 = lz + (hz ? 0 : 1);
-                double Fx0, Fx1, Fy0, Fy1, Fz0, Fz1;
-                factor_pair(ox, pfx, Fx0, Fx1);
-                factor_pair(oy, pfy, Fy0, Fy1);
-                factor_pair(oz, pfz, Fz0, Fz1);
-                const double ds = sqrt_speed(__builtin_fma(s.vz, s.vz, __builtin_fma(s.vy, s.vy, s.vx * s.vx))) * a.dt;
-                x = gain_exponent<IDX64>(a, gk, X0, X1, Y0, Y1, Z0, Z1, Fx0, Fx1, Fy0, Fy1, Fz0, Fz1, sXh, sYh, ds);
-            }
-        }
-        if (GAIN) {
-            const bool small = __builtin_amdgcn_ballot_w64(alive && !(fabs(x) < kPhiSmallBelow)) == 0ull;
-            if (alive) {
-                const double phi = gain_phi(x, small);
-                const double dg = s.uray * (x * phi);
-                gained += dg;
-                s.uray = s.uray + dg;
-            }
-        }
-        if (alive) {
-            s.uray -= rec.kap * s.uray;                   // :305-311 (absorbing mode only: checked on the host)
-            // :351-356 the stop test; the record says which of its conditions held
-            const int end = stop_test(s, a.bounds);
-            if (end != 0) {
-                alive = false;
-                steps = tt + 1;
-                status = CBET_RAY_LAUNCHED | end;
-            }
+        // the six planes through a.bounds: nothing is stored in this loop, so the loads are scalar ones
+        const int end = ray_step<GAIN, IDX64, false>(a, f, a.bounds, alive, s, rec, cell, absorbed, gained);
+        if (__builtin_expect(end != 0, 0)) {              // (once per ray: kept a branch, not selects in every step)
+            alive = false;
+            steps = tt + 1;
+            status = CBET_RAY_LAUNCHED | end;
         }
     }
     if (alive) {                                          // ran out of steps (:207)
@@ -215,16 +159,9 @@ hipError_t launch_trace_exit(const TraceArgs &a, bool force_idx64, hipStream_t s
     const long waves = a.item_count;
     if (waves <= 0) return hipSuccess;
     const dim3 grid((unsigned)waves), block(kWave);
-    const bool wide = force_idx64 || sizeof(StepRecord) * (unsigned long long)a.nx * a.ny * a.nz > (1ull << 32) ||
-                      (a.gain && 8ull * (unsigned long long)a.hsize >= (1ull << 32));
-    if (a.gain) {
-        if (wide) hipLaunchKernelGGL((k_trace_exit<true, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k_trace_exit<true, false>), grid, block, 0, stream, a);
-    } else {
-        if (wide) hipLaunchKernelGGL((k_trace_exit<false, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k_trace_exit<false, false>), grid, block, 0, stream, a);
-    }
-    return hipGetLastError();
+    return launch_gain_by_index(a, force_idx64, [&](auto gain, auto wide) {
+        hipLaunchKernelGGL((k_trace_exit<gain, wide>), grid, block, 0, stream, a);
+    });
 }
 
 hipError_t launch_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, hipStream_t stream)

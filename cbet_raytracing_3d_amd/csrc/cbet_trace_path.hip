@@ -3,11 +3,12 @@
 //
 //   * k_trace_path<GAIN, IDX64> : a sibling of k_trace_exit (cbet_trace_exit.hip).  One wavefront = 64 consecutive items of
 //     the caller's list, lane l of workgroup w takes item 64 w + l.  Kick, drift, nearest-node update, step-record gather,
-//     the CBET hook, absorption and the stop test are that kernel's statements through the same functions of
-//     cbet_trace_common.h in the same order, so a ray's position, node, energy, step count and status are the exit pass's
-//     by construction.  On top, per step: the squared distance to the centre, one compare and the selects that remember
-//     the closest approach; every `stride` steps, and in the step a ray ends, a 64-byte sample.  Samples are sample-major
-//     (samples[m][item]): the 64 lanes of a wave write 4 KB of consecutive whole lines per sampled step.
+//     the CBET hook, absorption and the stop test are one function, ray_step of cbet_trace_common.h, which that kernel
+//     calls too, so a ray's position, node, energy, step count and status are the exit pass's by construction.  What is
+//     here is the recorder's own: the item decoding; per step the squared distance to the centre, one compare and the
+//     selects that remember the closest approach; every `stride` steps, and in the step a ray ends, a 64-byte sample with
+//     its step-order sums; the turn record.  Samples are sample-major (samples[m][item]): the 64 lanes of a wave write
+//     4 KB of consecutive whole lines per sampled step.
 //
 // Nothing here is hand-scheduled, and the context's counters are not touched.
 #include <hip/hip_runtime.h>
@@ -19,17 +20,6 @@ namespace cbet {
 static_assert(sizeof(cbet_path_sample) == 64 && sizeof(cbet_ray_turn) == 64, "path records are 64 bytes (include/cbet_mi355x.h)");
 
 namespace {
-
-// The step record of node `cell` (cbet_trace_exit.hip load_record: the same 32-byte gather).
-template <bool IDX64>
-__device__ __forceinline__ StepRecord path_record(const TraceArgs &a, unsigned cell)
-{
-#ifdef CBET_DEBUG_BOUNDS
-    if (!(cell < a.audit_nodes)) { audit_fail(a); return StepRecord{0.0, 0.0, 0.0, 0.0}; }
-#endif
-    if (IDX64) return a.steprec[cell];
-    return *reinterpret_cast<const StepRecord *>(reinterpret_cast<const char *>(a.steprec) + (cell << 5));
-}
 
 // Sample m of `item`, if the caller's array holds it: the guard is per store and unconditional.
 __device__ __forceinline__ void store_sample(const TraceArgs &a, const PathArgs &q, long item, int m, const Ray &s, double absorbed,
@@ -71,19 +61,14 @@ __global__ void __launch_bounds__(kWave) k_trace_path(const TraceArgs a, const P
     Ray s = {};
     const bool launched = valid && launch_ray(a, beam, raynum, s);
 
-    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    // a wave may hold several beams: the gain base is per lane
+    const StepFrame f = step_frame(a, lane, (GAIN && launched) ? a.gain + (long)beam * a.hsize : a.gain);
     StepRecord rec = {0.0, 0.0, 0.0, 0.0};
     unsigned cell = 0;
     if (launched) {
-        cell = (unsigned)((s.ci * ny + s.cj) * nz + s.ck);
-        rec = path_record<IDX64>(a, cell);                   // :254-270 at the launch node
+        cell = node_of(f, s);
+        rec = load_record<IDX64>(a, cell);                   // :254-270 at the launch node
     }
-
-    // a wave may hold several beams: the gain base is per lane
-    const double *const gk = (GAIN && launched) ? a.gain + (long)beam * a.hsize : a.gain;
-    const int sYh = a.sYh, sXh = a.sXh;
-    // the shipped kernel's lane flips (cbet_trace_window.hip), from the lane index as in k_trace_exit
-    const int pfx = lane & 1, pfy = (lane >> 1) & 1, pfz = (lane >> 3) & 1;
 
     // sample 0 and the closest approach so far: the launch state
     if (launched) store_sample(a, q, item, 0, s, 0.0, 0.0, 0);
@@ -105,61 +90,15 @@ __global__ void __launch_bounds__(kWave) k_trace_path(const TraceArgs a, const P
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;
         if (++phase == q.stride) { phase = 0; ++whole; }
         const bool stepping = alive;
-        double x = 0.0;                                      // GAIN: the clamped exponent K ds of the step
-        if (alive) {
-            // :268-278 kick, drift, position in cell units
-            s.vx -= rec.kx;
-            s.vy -= rec.ky;
-            s.vz -= rec.kz;
-            double fx, fy, fz;
-            drift(a, s, fx, fy, fz);
-            // :282-292 nearest-node update
-            s.ci = relocate_closed(s.ci, fx, nx);
-            s.cj = relocate_closed(s.cj, fy, ny);
-            s.ck = relocate_closed(s.ck, fz, nz);
-            // :296-305 the absorption coefficient now, the kicks of the next step
-            cell = (unsigned)((s.ci * ny + s.cj) * nz + s.ck);
-            rec = path_record<IDX64>(a, cell);
-            if (GAIN) {
-                // K at the eight deposit nodes with the deposit weights (:319-339)
-                const double ox = (fx - (double)s.ci) - 0.5, oy = (fy - (double)s.cj) - 0.5, oz = (fz - (double)s.ck) - 0.5;
-                const bool ngx = ox < 0, ngy = oy < 0, ngz = oz < 0;
-                const int lx = s.ci + 1 - (ngx ? 1 : 0), ly = s.cj + 1 - (ngy ? 1 : 0), lz = s.ck + 1 - (ngz ? 1 : 0);
-                const bool hx = ngx != (pfx != 0), hy = ngy != (pfy != 0), hz = ngz != (pfz != 0);
-                const int X0 = lx + (hx ? 1 : 0), X1 = lx + (hx ? 0 : 1);
-                const int Y0 = ly + (hy ? 1 : 0), Y1 = ly + (hy ? 0 : 1);
-                const int Z0 = lz + (hz ? 1 : 0), Z1 = lz + (hz ? 0 : 1);
-                double Fx0, Fx1, Fy0, Fy1, Fz0, Fz1;
-                factor_pair(ox, pfx, Fx0, Fx1);
-                factor_pair(oy, pfy, Fy0, Fy1);
-                factor_pair(oz, pfz, Fz0, Fz1);
-                const double ds = sqrt_speed(__builtin_fma(s.vz, s.vz, __builtin_fma(s.vy, s.vy, s.vx * s.vx))) * a.dt;
-                x = gain_exponent<IDX64>(a, gk, X0, X1, Y0, Y1, Z0, Z1, Fx0, Fx1, Fy0, Fy1, Fz0, Fz1, sXh, sYh, ds);
-            }
-        }
-        if (GAIN) {
-            const bool small = __builtin_amdgcn_ballot_w64(alive && !(fabs(x) < kPhiSmallBelow)) == 0ull;
-            if (alive) {
-                const double phi = gain_phi(x, small);
-                const double dg = s.uray * (x * phi);
-                gained += dg;
-                s.uray = s.uray + dg;
-            }
-        }
-        if (alive) {
-            const double inc = rec.kap * s.uray;             // :305-311 (absorbing mode only: checked on the host)
-            s.uray -= inc;
-            absorbed += inc;
-            // :351-356 the stop test; the record says which of its conditions held.  The six planes come from the argument
-            // segment (TraceArgs::exit_planes, the values of a.bounds by host_exit_planes): this loop stores to memory, so
-            // the compiler could keep loads through a.bounds neither scalar nor out of the loop -- six vector loads and
-            // their wait in every step (measured at 256^3: 1.68 x the exit pass that way, 1.03 x this way)
-            const int end = stop_test(s, a.exit_planes);
-            if (end != 0) {
-                alive = false;
-                steps = tt + 1;
-                status = CBET_RAY_LAUNCHED | end;
-            }
+        // The six planes come from the argument segment (TraceArgs::exit_planes, the values of a.bounds by
+        // host_exit_planes): this loop stores to memory, so the compiler could keep loads through a.bounds neither scalar
+        // nor out of the loop -- six vector loads and their wait in every step (measured at 256^3: 1.68 x the exit pass
+        // that way, 1.03 x this way).  absorbed, gained: the sums since the previous sample, taken by lanes that step.
+        const int end = ray_step<GAIN, IDX64, true>(a, f, a.exit_planes, alive, s, rec, cell, absorbed, gained);
+        if (__builtin_expect(end != 0, 0)) {                 // (once per ray, as in k_trace_exit)
+            alive = false;
+            steps = tt + 1;
+            status = CBET_RAY_LAUNCHED | end;
         }
         if (stepping) {
             // the closest approach: the first minimum wins
@@ -213,17 +152,9 @@ hipError_t launch_trace_path(const TraceArgs &a, const PathArgs &q0, bool force_
     q.audit_turns_lo = q.turns; q.audit_turns_hi = q.turns + q.nitems;
 #endif
     const dim3 grid((unsigned)((q.nitems + kWave - 1) / kWave)), block(kWave);
-    // (the wide-index rule of launch_trace_exit)
-    const bool wide = force_idx64 || sizeof(StepRecord) * (unsigned long long)a.nx * a.ny * a.nz > (1ull << 32) ||
-                      (a.gain && 8ull * (unsigned long long)a.hsize >= (1ull << 32));
-    if (a.gain) {
-        if (wide) hipLaunchKernelGGL((k_trace_path<true, true>), grid, block, 0, stream, a, q);
-        else hipLaunchKernelGGL((k_trace_path<true, false>), grid, block, 0, stream, a, q);
-    } else {
-        if (wide) hipLaunchKernelGGL((k_trace_path<false, true>), grid, block, 0, stream, a, q);
-        else hipLaunchKernelGGL((k_trace_path<false, false>), grid, block, 0, stream, a, q);
-    }
-    return hipGetLastError();
+    return launch_gain_by_index(a, force_idx64, [&](auto gain, auto wide) {
+        hipLaunchKernelGGL((k_trace_path<gain, wide>), grid, block, 0, stream, a, q);
+    });
 }
 
 }  // namespace cbet

@@ -571,6 +571,15 @@ class RayTracer:
     def _check_exits(self, exits):
         _require(exits, (self.params.nbeams, self.ctx.list_length(), 10), "exits (new_exits())")
 
+    def _gain_args(self, gain, gain_params):
+        """The gain_params a no-deposit pass (trace_exits, trace_paths) hands on: with a gain grid, its shape checked and
+        api.default_gain_params() in place of None."""
+        if gain is not None:
+            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
+            if gain_params is None:
+                gain_params = api.default_gain_params()
+        return gain_params
+
     def trace_exits(self, exits, gain=None, gain_params=None, shard_index=0, shard_count=1, beam_lo=0, beam_hi=None,
                     tabulate=True):
         """The exit pass on torch's current stream: every traced ray's final state into `exits` (new_exits()); slots of
@@ -578,10 +587,7 @@ class RayTracer:
         solve's) -- the rays then gain energy as in the CBET deposition pass; gain_params defaults to
         api.default_gain_params().  tabulate: fill the node tables from the profiles first, as launch() does."""
         self._check_exits(exits)
-        if gain is not None:
-            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
-            if gain_params is None:
-                gain_params = api.default_gain_params()
+        gain_params = self._gain_args(gain, gain_params)
         if tabulate:
             self.tabulate()
         p = self.params.copy(beam_lo=beam_lo, beam_hi=self.params.nbeams if beam_hi is None else beam_hi,
@@ -654,11 +660,8 @@ class RayTracer:
             _require(turns, (nitems, 8), "turns (new_paths())")
             if samples is not None or capacity > 0:
                 _require(samples, (capacity, nitems, 8), "samples (new_paths())")
-        if gain is not None:
-            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
-            if gain_params is None:
-                gain_params = api.default_gain_params()
-        if nitems == 0:                 # (empty tensors have no address to hand over)
+        gain_params = self._gain_args(gain, gain_params)
+        if nitems == 0:                # (empty tensors have no address to hand over)
             return samples, turns
         if tabulate:
             self.tabulate()

@@ -109,6 +109,7 @@ def main():
         assert gain.data_ptr() == api.cbet_workspace_gain(p, ws)
         t = interleaved({"exit_gain": lambda: tr.trace_exits(ex, gain=gain, gain_params=gp, tabulate=False),
                          "paths_gain_turns_only": lambda: paths(beams, raynums, 1, 0, None, turns, gain, gp)}, reps)
+        out["exit_gain_ms"], out["paths_gain_turns_only_ms"] = t["exit_gain"], t["paths_gain_turns_only"]
         out["exit_gain_ms_median"], out["paths_gain_turns_only_ms_median"] = (
             float(np.median(t[k])) for k in ("exit_gain", "paths_gain_turns_only"))
         out["paths_over_exit_gain"] = out["paths_gain_turns_only_ms_median"] / out["exit_gain_ms_median"]

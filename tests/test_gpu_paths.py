@@ -185,20 +185,47 @@ def test_per_step_against_oracle_box_small(api, box_small):
 
 
 # ---- 2. against the exit pass, bit for bit ------------------------------------------------------------------------------
-@pytest.mark.parametrize("which", ("ragged", "box_small"))
-def test_end_state_is_the_exit_pass_bit_for_bit(api, request, which):
+@pytest.mark.parametrize("which, gain_name, wide", (
+    pytest.param("ragged", None, False, id="ragged"), pytest.param("box_small", None, False, id="box_small"),
+    pytest.param("ragged", None, True, id="ragged-wide"), pytest.param("ragged", "mixed", False, id="ragged-mixed"),
+    pytest.param("ragged", "mixed", True, id="ragged-mixed-wide")))
+def test_end_state_is_the_exit_pass_bit_for_bit(api, request, torch_cuda, which, gain_name, wide):
+    """Both kernels call one step function (ray_step): every arm of it -- plain and gain, narrow and wide index -- gives
+    the recorder the exit pass's end state.  The gain hook picks phi's form by a vote of the wave's live lanes (gain_phi),
+    and the two forms differ in the last bit or two, so under a gain the identity holds between equal wavefronts: those
+    cases take the same rays with the launch list's idle entries kept (ray_items(bundles=True): a wavefront of the recorder
+    is then a wavefront of the exit pass).  The compacted list regroups the rays, and with the `mixed` grid some rays'
+    energies then differ from the exit pass's in those last bits; test_gain_hook_against_oracle holds both to the oracle."""
     case = request.getfixturevalue(which)
-    tr = case.tr
-    rec = tr.trace_exits(tr.new_exits()).cpu().numpy().copy().view(api.EXIT_DTYPE)[..., 0]
+    tr = request.getfixturevalue("ragged_wide") if wide else case.tr
+    assert tr.params.force_wide_index == int(wide)
+    gain, gp = (None, None) if gain_name is None else _gain_args(api, torch_cuda, gain_name)
+    beams, raynums, S, T = case.beams, case.raynums, case.S, case.T
+    if gain is not None:
+        beams, raynums = tr.ray_items(bundles=True)
+        live = raynums >= 0
+        assert np.array_equal(beams[live], case.beams) and np.array_equal(raynums[live], case.raynums)     # the same rays
+    if wide or gain is not None:
+        S, T = _host(api, *tr.trace_paths(beams, raynums, gain=gain, gain_params=gp))
+    if gain is not None:
+        assert not _raw(T[~live]).any() and not _raw(S[:, ~live]).any()         # idle items
+        S, T = S[:, live], T[live]
+    rec = tr.trace_exits(tr.new_exits(), gain=gain, gain_params=gp).cpu().numpy().copy().view(api.EXIT_DTYPE)[..., 0]
     slot = {int(i): li for li, i in enumerate(tr.ray_ids()) if i >= 0}
     e = rec[case.beams, [slot[int(i)] for i in case.raynums]]
-    last = case.S[case.T["nsamples"] - 1, np.arange(len(case.beams))]
+    every = np.arange(len(case.beams))
+    last = S[T["nsamples"] - 1, every]
     assert np.all(e["status"] & api.RAY_LAUNCHED)
     for name in ("x", "y", "z", "uray"):
         assert _same(last[name], e[name]), name
     assert np.array_equal(last["step"], e["steps"])
-    assert np.array_equal(case.T["steps"], e["steps"]) and np.array_equal(case.T["status"], e["status"])
-    assert _same(case.S[0, :]["uray"], e["uray0"])
+    assert np.array_equal(T["steps"], e["steps"]) and np.array_equal(T["status"], e["status"])
+    assert _same(S[0, :]["uray"], e["uray0"])
+    if gain is not None:
+        # the record's `gained` is the stride-1 samples' summed in step order from sample 0's 0.0 (cumsum: sequential)
+        assert np.array_equal(T["nsamples"], 1 + T["steps"]) and not _raw(S["gained"][0]).any()
+        assert _same(np.cumsum(S["gained"], axis=0)[T["nsamples"] - 1, every], e["gained"])
+        assert np.abs(e["gained"]).max() > 0
 
 
 # ---- 3. stride and truncation ------------------------------------------------------------------------------------------
