@@ -12,16 +12,15 @@
  *   /root/reference/def.cuh:33-131  (derived constants; compile-time macros there, fields here)
  * Each function cites the lines it follows.
  *
- * PARITY UNPINNED (see DESIGN.md "Oracle").  The reference's only golden file, truth_100
- * (Makefile:14-17), is missing from the mount, its tree holds no other fixture or known-answer
- * test, and the reference cannot be built in this image from its own sources (def.cuh includes
- * cuda_runtime.h, H5Cpp.h and boost/multi_array.hpp; nvcc and boost are absent, and stand-in
- * headers are not an allowed build), so oracle/_ref does not exist.  What the restatement IS
- * checked against (tests/test_oracle_golden.py) are the numbers SURVEY.md section 8(c) recorded
- * when the survey session compiled the reference kernel source as host C++ against stub headers:
- * ray-step counts at 64^3/100^3/256^3, sum/max/nonzero counts, individual cell values and the md5
- * of the 6-significant-digit text dump at 100^3.  Those are strong evidence, not a reference-held
- * pin: nobody has compared anything here with truth_100.
+ * PINNED TO THE REFERENCE'S OWN KERNEL SOURCE for the reference-physics trace:
+ * oracle/ref_build.py compiles launch_ray_XZ.cu, unmodified, as host C++ against the stand-in headers of
+ * oracle/ref_shim/ into oracle/_ref/<case>/run (ignored by git), one binary per case of
+ * tests/helpers/reference_cases.py, and tests/test_reference_pin.py compares cbet_oracle_trace with them across
+ * every run-time field of cbet_oracle_config: equal ray-step counts per beam, equal zero pattern, and for
+ * one-pass launches (nindices == 1) grids equal BIT FOR BIT with nthreads = 1.  The numbers SURVEY.md section 8(c)
+ * recorded (tests/test_oracle_golden.py) are reproduced by the same binaries.  Still unpinned: the reference's
+ * golden file truth_100 (Makefile:14-17) is missing from the mount, so nobody has compared anything with it; and
+ * everything below that the reference has no counterpart of -- the CBET extension, exits, paths.
  */
 #ifndef CBET_ORACLE_H_
 #define CBET_ORACLE_H_

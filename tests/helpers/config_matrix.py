@@ -11,6 +11,8 @@ The nearest-node update looks one cell either way with a half-width of 0.5001, s
 followed: the reference keeps the old cell and the ray's cell no longer tracks its position ("far jump", "lost").
 """
 import ctypes as C
+import json
+import os
 
 import numpy as np
 
@@ -247,14 +249,14 @@ ENTRIES = [
 BY_NAME = {e.name: e for e in ENTRIES}
 NAMES = [e.name for e in ENTRIES]
 
-# the step counts the oracle gave when the table was written (tests compare with the oracle's count at run time and
-# pin these on top; an entry absent here had no recorded count)
-PINNED_STEPS = {
-    "courant_0.25": 1798509, "courant_1.0": 435413, "courant_1.6": 491072, "courant_2.5": 301307,
-    "courant_2.5_n96": 2268938, "box_off_centre": 876112, "box_small": 1535308, "box_large": 176838,
-    "box_thin_y": 811685, "box_thin_x": 1819982, "box_thin_z": 880570, "tall_y": 276430, "axis_beams": 1416273,
-    "strided_2": 857393, "strided_5": 855486, "truncated": 835259, "tpb_7": 890166,
-}
+# the step counts of the reference's own kernel source, compiled as host C++ and run on every light entry
+# (tests/golden/reference_kat.json, written by tests/golden/make_reference_golden.py; tests/test_reference_pin.py holds
+# the file to the live binaries and to the oracle).  Tests compare with the oracle's count at run time and pin these on
+# top; the heavy entry (long_nt) has no recorded count.
+with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "reference_kat.json")) as _f:
+    _KAT = json.load(_f)["cases"]
+PINNED_STEPS = {e.name: _KAT[e.name]["ray_steps"] for e in ENTRIES if not e.heavy}
+assert len(PINNED_STEPS) == 19 and PINNED_STEPS["courant_1.3"] == 410101 and PINNED_STEPS["diag_beams"] == 880381
 
 EXTRAS = ("courant_1.6", "box_small", "axis_beams", "strided_5")     # wide index, per beam, padded rows, shards
 EXIT_ENTRIES = ("courant_1.6", "box_small", "box_thin_y", "axis_beams", "strided_5")
