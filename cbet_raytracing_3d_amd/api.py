@@ -177,6 +177,28 @@ assert TURN_DTYPE.itemsize == C.sizeof(RayTurn) == 64
 TARGET_LMAX = 16
 
 
+class LpiSummary(C.Structure):
+    """cbet_lpi_summary: counts, maxima and sums over the band cells of an LPI map; merged into."""
+    _fields_ = [("band_cells", C.c_longlong), ("lit_cells", C.c_longlong),
+                ("above_max", C.c_longlong), ("above_cw", C.c_longlong), ("above_sum", C.c_longlong),
+                ("argmax_cw", C.c_longlong),
+                ("max_eta_max", C.c_double), ("max_eta_cw", C.c_double), ("max_eta_sum", C.c_double),
+                ("sum_I_sum", C.c_double), ("sum_I_cw", C.c_double),
+                ("max_present", C.c_int), ("reserved", C.c_int)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+# the quantities of an LPI map, CBET_LPI_* of the header
+LPI_NQ = 7
+LPI_BAND, LPI_I_SUM, LPI_I_CW, LPI_I_MAX, LPI_LN, LPI_ETA_SUM, LPI_ETA_CW = range(LPI_NQ)
+LPI_QUANTITIES = ("band", "I_sum", "I_cw", "I_max", "L_n", "eta_sum", "eta_cw")
+LPI_MAX_BINS = 16                               # CBET_LPI_MAX_BINS
+LPI_SUMMARY_BYTES = 96                          # sizeof(cbet_lpi_summary)
+EC, ME = 1.60217662e-19, 9.10938356e-31         # the library's electron charge and mass (csrc/cbet_device.h kEc, kMe)
+
+
 class Target(C.Structure):
     """cbet_target: a target whose centre sits at `offset` (cm) and whose iso-surfaces are displaced by
     delta(theta, phi) = sum_c coeffs[c] Y_c (relative, dR/R; modes.target_coeffs builds the vector, index l*l + l + m).
@@ -395,6 +417,7 @@ EXPORTS = [
     "cbet_context_set_polarization", "cbet_context_polarization", "cbet_exchange_matrix_host_polarized",
     "cbet_context_set_bandwidth", "cbet_context_bandwidth", "cbet_exchange_matrix_host_banded",
     "cbet_trace_paths",
+    "cbet_lpi_work_bytes", "cbet_lpi_summary_init", "cbet_lpi_map", "cbet_lpi_map_host",
 ]
 
 _lib = None
@@ -513,6 +536,13 @@ def lib(tolerate=()):
     L.cbet_exchange_matrix.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
     L.cbet_exchange_matrix_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp,
                                             C.c_double]
+    L.cbet_lpi_work_bytes.argtypes = [C.POINTER(Params)]
+    L.cbet_lpi_work_bytes.restype = C.c_size_t
+    L.cbet_lpi_summary_init.argtypes = [C.POINTER(LpiSummary)]
+    L.cbet_lpi_map.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.c_int, C.c_int,
+                               C.POINTER(Params), vp, vp]
+    L.cbet_lpi_map_host.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, C.POINTER(LpiSummary), C.c_int,
+                                    C.c_int, C.POINTER(Params)]
     detuning = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
                 "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp],
                 "cbet_context_set_polarization": [vp, C.c_int], "cbet_context_polarization": [vp, ip],
@@ -993,6 +1023,48 @@ def exchange_matrix(fields, ne3d, out, gross, work, hx_lo, hx_hi, params, gain_p
     state tables and its saturation limit are honoured."""
     _check(lib().cbet_exchange_matrix(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), _addr(work), hx_lo, hx_hi,
                                       C.byref(params), C.byref(gain_params), ctx.handle if ctx is not None else None, _addr(stream)))
+
+
+def lpi_work_bytes(params):
+    """cbet_lpi_work_bytes: device bytes of the `work` array of lpi_map, for any slab of the grid."""
+    return int(lib().cbet_lpi_work_bytes(C.byref(params)))
+
+
+def lpi_summary_new():
+    """A cbet_lpi_summary as cbet_lpi_summary_init leaves it: zeros, argmax_cw = -1."""
+    s = LpiSummary()
+    _check(lib().cbet_lpi_summary_init(C.byref(s)))
+    return s
+
+
+def lpi_summary_from(buffer):
+    """The summary a device call merged into `buffer` (a uint8 tensor or array of LPI_SUMMARY_BYTES bytes), as a dict."""
+    raw = buffer.cpu().numpy() if hasattr(buffer, "cpu") else np.asarray(buffer)
+    return LpiSummary.from_buffer_copy(np.ascontiguousarray(raw).tobytes()).as_dict()
+
+
+def lpi_map(fields, ne3d, te3d, te_ev, frac_lo, frac_hi, cone_bins, lpi, summary, work, hx_lo, hx_hi, params, ctx, stream=None):
+    """cbet_lpi_map: into `lpi` (device [LPI_NQ][hsize] doubles), for the planes [hx_lo, hx_hi), the quarter-critical LPI maps
+    of the NORMALISED device `fields`; summary: a device cbet_lpi_summary to merge into (with `work`), or None."""
+    _check(lib().cbet_lpi_map(_addr(fields), _addr(ne3d), _addr(te3d), te_ev, frac_lo, frac_hi, cone_bins, _addr(lpi),
+                              _addr(summary), _addr(work), hx_lo, hx_hi, C.byref(params),
+                              ctx.handle if ctx is not None else None, _addr(stream)))
+
+
+def lpi_map_host(fields, ne3d, params, te=1000.0, band=(0.20, 0.25), cone_bins=8, hx_lo=0, hx_hi=None, out=None, summary=None):
+    """cbet_lpi_map_host, the host twin: (stack [LPI_NQ, nx + 2, ny + 2, nz + 2], summary dict) of normalised HOST fields
+    [4, nbeams, nx + 2, ny + 2, nz + 2] over the planes [hx_lo, hx_hi).  ne3d (nx, ny, nz); te: a float (eV, uniform) or an
+    (nx, ny, nz) array; out: a stack to write the planes of (default: a zeroed new one); summary: an LpiSummary to merge
+    into (default: a new one)."""
+    host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
+    fields, ne3d = host(fields), host(ne3d)
+    te3d, te_ev = (None, float(te)) if np.isscalar(te) else (host(te), 0.0)
+    grid = (params.nx + 2, params.ny + 2, params.nz + 2)
+    out = np.zeros((LPI_NQ,) + grid) if out is None else out
+    summary = lpi_summary_new() if summary is None else summary
+    _check(lib().cbet_lpi_map_host(_addr(fields), _addr(ne3d), _addr(te3d), te_ev, float(band[0]), float(band[1]), int(cone_bins),
+                                   _addr(out), C.byref(summary), hx_lo, grid[0] if hx_hi is None else hx_hi, C.byref(params)))
+    return out, summary.as_dict()
 
 
 POL_ALIGNED, POL_SMOOTHED = 0, 1                # CBET_POL_* of the header

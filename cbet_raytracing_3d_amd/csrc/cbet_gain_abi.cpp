@@ -1,9 +1,10 @@
 // cbet_gain_abi.cpp -- the CBET stage of the C ABI (include/cbet_mi355x.h; SURVEY 8(f) f1, parity unpinned -- see the
 // header): the gain update, the trace with the CBET hooks, the sparse exchange's pack / unpack and the native one-device
-// fixed-point loop, the amplitude map of the saturation clamp, the pairwise exchange matrix.
+// fixed-point loop, the amplitude map of the saturation clamp, the pairwise exchange matrix, the quarter-critical LPI maps.
 #include <cmath>
 
 #include "cbet_host_internal.h"
+#include "cbet_lpi_model.h"
 
 using namespace cbet;
 
@@ -121,6 +122,23 @@ int cbet_exchange_matrix(const double *fields, const double *ne3d, double *out, 
     const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, block_shift(ctx), ctx->pol, ctx->band, ctx->nband, hx_lo, hx_hi, false);
     CBET_ENTER_DEVICE(ctx);
     CBET_HIP(launch_exchange_matrix(a, (double *)work, out, gross, (hipStream_t)stream));
+    return CBET_OK;
+}
+
+// ---- quarter-critical LPI maps (cbet_lpi.hip k_lpi_map, k_lpi_reduce) ------------------------------
+int cbet_lpi_map(const double *fields, const double *ne3d, const double *te3d, double te_ev, double frac_lo, double frac_hi,
+                 int cone_bins, double *lpi, cbet_lpi_summary *summary, void *work, int hx_lo, int hx_hi, const cbet_params *p,
+                 cbet_context *ctx, void *stream)
+{
+    // the arguments first, the context last, as cbet_pair_amplitude; the checks are the host twin's (cbet_lpi_host.cpp)
+    cbet_derived d;
+    if (int rc = lpi_check("cbet_lpi_map", fields, te3d, te_ev, frac_lo, frac_hi, cone_bins, lpi, hx_lo, hx_hi, p, &d)) return rc;
+    if (summary && !work) return fail(CBET_EINVAL, "cbet_lpi_map: work is NULL but summary is not (cbet_lpi_work_bytes)");
+    if (int rc = entry_checks(ctx, p)) return rc;
+    if (hx_hi == hx_lo) return CBET_OK;
+    const LpiArgs a = lpi_args(p, ctx->d, fields, ne3d ? ne3d : ctx->ne3d, te3d, te_ev, frac_lo, frac_hi, cone_bins, lpi, hx_lo, hx_hi);
+    CBET_ENTER_DEVICE(ctx);
+    CBET_HIP(launch_lpi_map(a, summary, (cbet_lpi_summary *)work, lpi_groups(p, hx_lo, hx_hi), (hipStream_t)stream));
     return CBET_OK;
 }
 

@@ -173,6 +173,18 @@ int band_check(const char *who, const double *line_domega, const double *line_we
 int band_table(const double *line_domega, const double *line_weight, int nlines, double *table, double *norm);
 // The slab [hx_lo, hx_hi) lies in the haloed grid; who: the entry point's name and ": " in front of the message, or "".
 int slab_check(const char *who, int hx_lo, int hx_hi, const cbet_params *p);
+// k_lpi_map's and its host twin's (cbet_lpi_host.cpp, no HIP call).  lpi_check: the refusals both
+// entries share, `who` in front, and the derived constants into *d; lpi_args: the block (ne3d: the table in use).
+struct LpiArgs;
+int lpi_check(const char *who, const double *fields, const double *te3d, double te_ev, double frac_lo, double frac_hi,
+              int cone_bins, const double *lpi, int hx_lo, int hx_hi, const cbet_params *p, cbet_derived *d);
+LpiArgs lpi_args(const cbet_params *p, const cbet_derived &d, const double *fields, const double *ne3d, const double *te3d,
+                 double te_ev, double frac_lo, double frac_hi, int cone_bins, double *lpi, int hx_lo, int hx_hi);
+// the grid of k_lpi_map for a slab: four bricks per workgroup up to CBET_LPI_MAX_GROUPS, from the slab alone
+long lpi_groups(const cbet_params *p, int hx_lo, int hx_hi);
+// k_lpi_map over the block's planes with `groups` workgroups; summary != NULL: the workgroups' partial summaries into
+// work[groups], then k_lpi_reduce merges them into *summary in workgroup order (cbet_lpi.hip)
+hipError_t launch_lpi_map(const LpiArgs &a, cbet_lpi_summary *summary, cbet_lpi_summary *work, long groups, hipStream_t stream);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
 // The context's own table of `components` doubles per node in *slot, allocated on the first call (not capturable).

@@ -74,6 +74,9 @@ class RayTracer:
         self._state_gp = None           # the gain parameters a "mesh" state takes ti_ev, z_ion and mi_over_me from
         self.saturation = 0.0           # set_saturation(): the limit of the ion-acoustic amplitude, 0.0 = none
         self._exchange_work = None      # exchange_matrix(): the per-workgroup partial tables, allocated by the first call
+        self._lpi_work = None           # lpi_map(): the per-workgroup partial summaries, allocated by the first call
+        self._tables_filled = False     # tabulate() or the pipeline's preparation has filled this context's node tables
+        self._table_addrs = None        # table_te(): the context's (ne3d, kappa3d) addresses, asked for once
         self.grid_shape = (self.params.nx + 2, self.params.ny + 2, self.params.nz + 2)
 
     # ---- the one spelling of what every launch repeats -------------------------------------------------------------
@@ -104,6 +107,8 @@ class RayTracer:
             api.prepare_step_records(ctx, params, None, None, *self._grad_consts(), self._stream())
         else:
             api.prepare_plasma(ctx, params, self.d_te, self.d_r, self.d_ne, *self._grad_consts(), self._stream())
+        if ctx is self.ctx:
+            self._tables_filled = True
         self._tabulate_flow(ctx, params)
         self._tabulate_state(ctx, params)
         ctx.set_saturation(self.saturation)         # a context prepared for this tracer carries its limit, as it carries its tables
@@ -401,6 +406,88 @@ class RayTracer:
                             self.params, gain_params, self.ctx, self._stream())
         return out if gross is None else (out, gross)
 
+    # ---- quarter-critical LPI maps (include/cbet_mi355x.h cbet_lpi_map) -----------------------
+    def table_te(self):
+        """The electron temperature (eV) at the nodes, [nx, ny, nz] on this device, recovered from the context's own node
+        tables by inverting the absorption coefficient's formula (csrc/cbet_node_model.h kappa()):
+            Te = (5.2e-4 * 1e6 * ne^2 * e^2 / me * dt / (ncrit * kappa))^(2/3)
+        whatever the tables were filled from (profiles, a target, a plasma mesh); 0 where ne or kappa is 0.  Needs
+        tabulate() first.  A set-up step: it waits for torch's current stream and copies the two tables."""
+        if not self._tables_filled:
+            raise ValueError("table_te: the context's node tables are not filled: tabulate() first")
+        if self._table_addrs is None:        # once: asking for the (writable) pointers makes the next launch rebuild its records
+            self._table_addrs = self.ctx.tables()
+        shape = (self.params.nx, self.params.ny, self.params.nz)
+        torch.cuda.current_stream(self.device).synchronize()
+        ne, kap = (torch.empty(shape, dtype=torch.float64, device=self.device) for _ in range(2))
+        for t, addr in zip((ne, kap), self._table_addrs):
+            api.moveToAndFromGPU(t, addr, 8 * t.numel(), self.gpu)
+        d = self.derived
+        live = (ne > 0) & (kap > 0)
+        x = (5.2e-4 * 1e6) * ne * ne * (api.EC * api.EC / api.ME) * d.dt / (d.ncrit * torch.where(live, kap, torch.ones_like(kap)))
+        return torch.where(live, x ** (2.0 / 3.0), torch.zeros_like(x))
+
+    def new_lpi_summary(self):
+        """A device cbet_lpi_summary as cbet_lpi_summary_init leaves it (a uint8 tensor of api.LPI_SUMMARY_BYTES bytes), for
+        lpi_map(summary=...) calls that merge into one; api.lpi_summary_from() reads it."""
+        return torch.frombuffer(bytearray(bytes(api.lpi_summary_new())), dtype=torch.uint8).to(self.device)
+
+    def lpi_map(self, fields, te="tables", band=(0.20, 0.25), cone_bins=8, x_lo=0, x_hi=None, ne3d=None, out=None,
+                summary=None):
+        """The laser-plasma-instability maps of the cells whose ne / ncrit lies in `band` (both ends included), over the
+        planes [x_lo, x_hi): (stack, summary).  stack [api.LPI_NQ, *grid_shape] (`out`, or a zeroed new one; cells of other
+        planes are left as they are): api.LPI_BAND 1 in band / 0 out of it, LPI_I_SUM the overlapped intensity of the
+        beams present (W/cm^2), LPI_I_CW the largest sum over beams on one of `cone_bins` cones about the density
+        gradient (the beams that can share an electron-plasma wave), LPI_I_MAX the strongest beam, LPI_LN the density
+        scale length (cm), LPI_ETA_SUM and LPI_ETA_CW the two-plasmon-decay threshold parameter I_14 L_um lambda_um /
+        (81.86 T_keV) of the two intensities; every quantity is 0 out of band.  Unpinned: no reference counterpart.
+        `fields` are normalised fields [4, nbeams, ...] as gain_field leaves them (the ones handed to
+        cbet_solve(fields=...), for example); they are not changed.
+        te: a float (eV, uniform), a device tensor [nx, ny, nz] in eV, or "tables" (the default): table_te(), which needs
+        tabulate() first and is a set-up step (a float or a tensor keeps the call free of synchronisation).
+        summary: None -- the counts, maxima and sums over the band cells come back as a dict (read from the device: the
+        call then waits for the stream); a tensor of new_lpi_summary() -- the call MERGES into it (slab calls and ranks
+        compose) and returns it, without waiting; False -- no summary, None comes back.
+        Runs on torch's current stream; ne3d: a caller's node table instead of the context's."""
+        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+        nodes = (self.params.nx, self.params.ny, self.params.nz)
+        if ne3d is not None:
+            _require(ne3d, nodes, "ne3d")
+        te3d, te_ev = None, 0.0
+        if isinstance(te, str):
+            if te != "tables":
+                raise ValueError('lpi_map: te is a float (eV), a [nx, ny, nz] tensor or "tables", got %r' % (te,))
+            if not self._tables_filled:
+                raise ValueError('lpi_map: te="tables" needs tabulate() first')
+            te3d = self.table_te()
+        elif torch.is_tensor(te):
+            _require(te, nodes, "te")
+            if te.device != self.device:
+                raise ValueError("te must be on %s" % self.device)
+            te3d = te
+        else:
+            te_ev = float(te)
+        if out is None:
+            out = torch.zeros((api.LPI_NQ,) + self.grid_shape, dtype=torch.float64, device=self.device)
+        else:
+            _require(out, (api.LPI_NQ,) + self.grid_shape, "out")
+        read_back = summary is None
+        if summary is False:
+            summary = None
+        elif summary is None:
+            summary = self.new_lpi_summary()
+        elif summary.dtype != torch.uint8 or summary.numel() != api.LPI_SUMMARY_BYTES or not summary.is_contiguous() \
+                or summary.device != self.device:
+            raise ValueError("summary must be a tensor of new_lpi_summary()")
+        if summary is not None and self._lpi_work is None:
+            self._lpi_work = torch.empty(max(api.lpi_work_bytes(self.params), 8), dtype=torch.uint8, device=self.device)
+        api.lpi_map(fields, ne3d, te3d, te_ev, float(band[0]), float(band[1]), int(cone_bins), out, summary,
+                    self._lpi_work if summary is not None else None, x_lo, self.grid_shape[0] if x_hi is None else x_hi,
+                    self.params, self.ctx, self._stream())
+        if read_back:
+            return out, api.lpi_summary_from(summary)
+        return out, summary
+
     def _no_target(self, what):
         if self.flow is not None:
             return
@@ -443,6 +530,7 @@ class RayTracer:
             p.force_wide_index = force_wide_index
         if stats is not None:
             p.window_stats = 1 if stats else 0
+        self._tables_filled = True              # either half below fills the context's node tables first
         if self._tabulate_other(self.ctx, p):   # the halves of the launch: the target's or the mesh's tables, then a trace of them
             api.trace_nodes(0, self.derived.nindices, None, None, edep, *self._tail(use_host_trig), p, self.ctx, self._stream())
             return edep
@@ -459,6 +547,7 @@ class RayTracer:
         mesh, if one is set."""
         if not self._tabulate_other(self.ctx, self.params):
             api.tabulate_plasma(self.ctx, self.params, self.d_te, self.d_r, self.d_ne, self._stream())
+        self._tables_filled = True
         self._tabulate_flow()
         self._tabulate_state()
 

@@ -919,6 +919,78 @@ int cbet_exchange_matrix_host_banded(const double *fields, const double *ne3d, d
                                      double dn_max, const double *shift, int pol, const double *line_domega,
                                      const double *line_weight, int nlines);
 
+/* ---- quarter-critical LPI maps ------------------------------------------------------------- */
+/*
+ * What the light that CBET redistributes does at quarter-critical density: per cell of the haloed deposit grid inside a band
+ * of ne / ncrit, the overlapped intensity, the density scale length and the two-plasmon-decay threshold parameter.  No
+ * reference counterpart: parity UNPINNED, like the whole CBET stage.  The statements are csrc/cbet_lpi_model.h's, one IEEE
+ * fp64 operation per written operator, for the kernel and the host twin alike, so the two agree bit for bit.
+ *
+ * A cell takes its plasma from its clamped node (i, j, k), as the gain kernels' cells do.  frac = ne3d[node] / ncrit; the cell
+ * is IN BAND iff frac_lo <= frac <= frac_hi.  A cell out of band holds 0.0 in every quantity and adds nothing to the summary.
+ *     gradient   per axis (ne[c + p] - ne[c + m]) / (2.0 d), (m, p) = -+1 inside, (0, 2) and (n-3, n-1) on the faces (the
+ *                tracer's own face rule); 0 along an axis of fewer than 3 nodes
+ *     gn         sqrt(gx gx + gy gy + gz gz);   L_n = ne / gn in cm, 0 where gn == 0
+ *     beam b     PRESENT iff I_b > 0 and kn_b = sqrt(kx kx + ky ky + kz kz) > 0; beams in increasing order, sums in that order
+ *     I_sum, I_max, n_present     the sum, the maximum and the number of the present beams' intensities (W/cm^2)
+ *     mu_b       ((kx gx + ky gy) + kz gz) / (kn_b gn), clamped to [-1, 1]; 1 for every beam where gn == 0
+ *     bin_b      min(NB - 1, (int)((1.0 - mu_b) * (0.5 * NB))), NB = cone_bins
+ *     I_cw       max over the bins of the sum of I_b in the bin (beam order): the largest overlapped intensity of beams on
+ *                one cone about the density gradient, which can share a common electron-plasma wave.  NB = 1: I_cw == I_sum
+ *     te         te3d[node] in eV, or te_ev where te3d is NULL
+ *     T          ((L_n * 1e4) * lambda_um) / (81.86 * (te * 1e-3)), 0 where te <= 0 or L_n == 0: Simon et al., Phys. Fluids 26,
+ *                3107 (1983), eta = I_14 L_um lambda_um / (81.86 T_keV) (I_14 L_um / (233 T_keV) at 351 nm); lambda_um is the
+ *                vacuum wavelength 2 pi c / omega of cbet_derive in micrometres
+ *     eta_x      (I_x * 1e-14) * T for x in {sum, cw, max}
+ * The absolute-SRS threshold at n_c / 4 needs a 4/3 power and is not evaluated here (cbet_raytracing_3d_amd/lpi.py).
+ *
+ * `lpi` is [CBET_LPI_NQ][hsize] doubles, whole-grid storage per quantity (CBET_LPI_BAND ... CBET_LPI_ETA_CW).  Every cell of
+ * the planes [hx_lo, hx_hi) is written in all seven quantities, so the caller need not clear; other planes are not touched.
+ * `fields` are NORMALISED whole-grid fields [4][nbeams][hsize] (I, kx, ky, kz) under cbet_pair_amplitude's contract, never
+ * written; fields and lpi need only a double's alignment.
+ *
+ * cbet_lpi_summary is MERGED INTO: counts and sums add, maxima take the maximum, argmax_cw (a haloed cell index) follows
+ * max_eta_cw, the lowest index among ties -- slab calls and ranks compose.  cbet_lpi_summary_init zeroes one and sets
+ * argmax_cw = -1 (host memory; a device summary is initialised by copying one).  lit_cells counts band cells with
+ * n_present >= 1; above_x those with eta_x >= 1; sum_I_sum / band_cells is the band mean of I_sum.
+ *
+ * cbet_lpi_map: device pointers; ne3d NULL = the context's table, te3d NULL = te_ev everywhere.  summary may be NULL (no
+ * reduction runs and `work` is not read); otherwise `work` holds cbet_lpi_work_bytes(p) bytes (enough for any slab; 0 for bad
+ * parameters).  Bricks whose cells are all out of band are written as zeros without reading `fields`.  The reduction uses
+ * no atomics: per-workgroup partial summaries go to `work` and a second kernel merges them in workgroup order, and the
+ * number of workgroups follows from the slab alone, so two calls give the same bits on any device.  Stream-ordered, no
+ * synchronisation, no allocation: capturable.  CBET_EINVAL naming the offence: NULL fields or lpi, a band that is not
+ * 0 <= frac_lo <= frac_hi < 1, cone_bins outside 1 .. CBET_LPI_MAX_BINS, nbeams > CBET_MAX_CBET_BEAMS, te3d NULL with
+ * te_ev <= 0, a summary without work, a slab outside [0, nx + 2] or reversed.
+ * cbet_lpi_map_host: the host twin on HOST pointers (ne3d required), cells in index order, no HIP call.
+ */
+#define CBET_LPI_NQ 7
+#define CBET_LPI_BAND 0
+#define CBET_LPI_I_SUM 1
+#define CBET_LPI_I_CW 2
+#define CBET_LPI_I_MAX 3
+#define CBET_LPI_LN 4
+#define CBET_LPI_ETA_SUM 5
+#define CBET_LPI_ETA_CW 6
+#define CBET_LPI_MAX_BINS 16
+#define CBET_LPI_MAX_GROUPS 8192
+typedef struct cbet_lpi_summary {
+    long long band_cells, lit_cells;
+    long long above_max, above_cw, above_sum;
+    long long argmax_cw;
+    double max_eta_max, max_eta_cw, max_eta_sum;
+    double sum_I_sum, sum_I_cw;
+    int max_present, reserved;
+} cbet_lpi_summary;
+size_t cbet_lpi_work_bytes(const cbet_params *p);
+int cbet_lpi_summary_init(cbet_lpi_summary *s);
+int cbet_lpi_map(const double *fields, const double *ne3d, const double *te3d, double te_ev, double frac_lo, double frac_hi,
+                 int cone_bins, double *lpi, cbet_lpi_summary *summary, void *work, int hx_lo, int hx_hi, const cbet_params *p,
+                 cbet_context *ctx, void *stream);
+int cbet_lpi_map_host(const double *fields, const double *ne3d, const double *te3d, double te_ev, double frac_lo,
+                      double frac_hi, int cone_bins, double *lpi, cbet_lpi_summary *summary, int hx_lo, int hx_hi,
+                      const cbet_params *p);
+
 /* ---- exit pass --------------------------------------------------------------- */
 /*
  * Where the light that is not absorbed goes.  A trajectory-only pass traces the rays of a deposit pass, deposits
