@@ -543,14 +543,14 @@ def lib(tolerate=()):
                                C.POINTER(Params), vp, vp]
     L.cbet_lpi_map_host.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, C.POINTER(LpiSummary), C.c_int,
                                     C.c_int, C.POINTER(Params)]
-    detuning = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
+    optional = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
                 "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp],
                 "cbet_context_set_polarization": [vp, C.c_int], "cbet_context_polarization": [vp, ip],
                 "cbet_exchange_matrix_host_polarized": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int],
                 "cbet_context_set_bandwidth": [vp, vp, vp, C.c_int, vp], "cbet_context_bandwidth": [vp, dp, dp, ip],
                 "cbet_exchange_matrix_host_banded": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int, vp, vp, C.c_int]}
-    absent = [name for name in detuning if name in tolerate and not hasattr(L, name)]
-    for name, types in detuning.items():
+    absent = [name for name in optional if name in tolerate and not hasattr(L, name)]
+    for name, types in optional.items():
         if name not in absent:
             getattr(L, name).argtypes = types
     for name in EXPORTS:
@@ -691,8 +691,7 @@ class Context:
         self.gpu = gpu
         self._flow_ref = None           # set_flow(): the caller's table, kept alive
         self._state_ref = None          # set_state(): likewise
-        self.detuning_source = None     # set_detuning(): the array last given (its own copy), None for none
-        self.bandwidth_source = None    # set_bandwidth(): the (offsets, weights) last given (its own copies), None for none
+        self._given = (None, None)      # given_beam_options(): what set_detuning() and set_bandwidth() were last given
         _check(lib().cbet_context_create(C.byref(self._h), C.byref(params), gpu))
 
     @property
@@ -769,12 +768,9 @@ class Context:
         call: it synchronises `stream` and copies synchronously.  A NaN or infinite shift or a wrong count raises.
         A RayTracer's own context is where the tracer's shifts live: RayTracer.set_detuning calls this, RayTracer.detuning reads
         the context back, and the contexts the tracer prepares later are given what this context was last given."""
-        if domega is None:
-            _check(lib().cbet_context_set_detuning(self._h, None, 0, _addr(stream)))
-        else:
-            arr = np.array(domega, dtype=np.float64).reshape(-1)
-            _check(lib().cbet_context_set_detuning(self._h, arr.ctypes.data, arr.size, _addr(stream)))
-        self.detuning_source = None if domega is None else arr
+        arr = None if domega is None else np.array(domega, dtype=np.float64).reshape(-1)
+        _check(lib().cbet_context_set_detuning(self._h, _addr(arr), 0 if arr is None else arr.size, _addr(stream)))
+        self._given = (arr, self._given[1])
 
     def detuning(self):
         """The shifts in use (cbet_context_detuning): a numpy array of one double per beam, or None if none."""
@@ -789,13 +785,10 @@ class Context:
         none, the default.  A set-up call: it synchronises `stream` and copies synchronously.  A NaN or infinite offset, a weight
         that is not finite and > 0 or too many lines raise and change nothing.  A RayTracer's own context is where the tracer's
         spectrum lives, as its shifts do (set_detuning)."""
-        if domega is None:
-            _check(lib().cbet_context_set_bandwidth(self._h, None, None, 0, _addr(stream)))
-            self.bandwidth_source = None
-            return
-        off, wts = line_arrays(domega, weights)
-        _check(lib().cbet_context_set_bandwidth(self._h, off.ctypes.data, wts.ctypes.data, off.size, _addr(stream)))
-        self.bandwidth_source = (off, wts)
+        lines = None if domega is None else line_arrays(domega, weights)
+        off, wts = lines or (None, None)
+        _check(lib().cbet_context_set_bandwidth(self._h, _addr(off), _addr(wts), 0 if off is None else off.size, _addr(stream)))
+        self._given = (self._given[0], lines)
 
     def bandwidth(self):
         """The spectrum in use (cbet_context_bandwidth): (offsets in rad/s, normalised weights), two numpy arrays of one double
@@ -815,6 +808,22 @@ class Context:
         mode = C.c_int()
         _check(lib().cbet_context_polarization(self._h, C.byref(mode)))
         return POLARIZATIONS[mode.value]
+
+    def given_beam_options(self):
+        """(shifts, (offsets, weights)): the arrays set_detuning and set_bandwidth were last given (own copies), None for none."""
+        return self._given
+
+    def adopt_beam_options(self, source, stream=None):
+        """Gives this context `source`'s limit and polarization mode (host-only calls, made every time) and the shifts and lines `source`
+        was last given: set-up calls that synchronise `stream`, made only if those arrays are not the very ones this context has recorded."""
+        self.set_saturation(source.saturation())
+        self.set_polarization(source.polarization())
+        shifts, lines = source.given_beam_options()
+        if self._given[0] is not shifts:
+            self.set_detuning(shifts, stream)
+        if self._given[1] is not lines:
+            self.set_bandwidth(*(lines or (None, None)), stream=stream)
+        self._given = (shifts, lines)
 
     def close(self):
         if self._h:

@@ -322,13 +322,7 @@ int cbet_context_set_detuning(cbet_context *ctx, const double *domega, int nbeam
         return CBET_OK;
     }
     CBET_ENTER_DEVICE(ctx);
-    if (!ctx->shift_own) {
-        hipError_t e = hipMalloc((void **)&ctx->shift_own, sizeof ctx->shift_host);
-        if (e != hipSuccess) {
-            ctx->shift_own = nullptr;
-            return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(detuning table): %s", hipGetErrorString(e));
-        }
-    }
+    if (int rc = own_table(&ctx->shift_own, CBET_MAX_CBET_BEAMS, "detuning table")) return rc;
     double fresh[CBET_MAX_CBET_BEAMS] = {};   // an entry per possible beam: zero past nbeams
     for (int b = 0; b < nbeams; ++b) fresh[b] = domega[b];
     CBET_HIP(hipStreamSynchronize((hipStream_t)stream));   // a launch in flight may still read the old values
@@ -379,13 +373,7 @@ int cbet_context_set_bandwidth(cbet_context *ctx, const double *line_domega, con
         return CBET_OK;
     }
     CBET_ENTER_DEVICE(ctx);
-    if (!ctx->band_own) {
-        hipError_t e = hipMalloc((void **)&ctx->band_own, sizeof fresh);
-        if (e != hipSuccess) {
-            ctx->band_own = nullptr;
-            return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(bandwidth table): %s", hipGetErrorString(e));
-        }
-    }
+    if (int rc = own_table(&ctx->band_own, sizeof fresh / sizeof(double), "bandwidth table")) return rc;
     CBET_HIP(hipStreamSynchronize((hipStream_t)stream));   // a launch in flight may still read the old values
     CBET_HIP(hipMemcpy(ctx->band_own, fresh, sizeof fresh, hipMemcpyHostToDevice));
     ctx->band = ctx->band_own;

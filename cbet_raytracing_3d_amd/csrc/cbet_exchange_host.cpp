@@ -5,9 +5,9 @@
 // operator, the library is built with -ffp-contract=off -- with every pair's two sums compensated (Neumaier).
 // No HIP call: it is the reference of the device path at any size.  cbet_exchange_matrix_host_shifted is the twin with per-beam
 // frequency shifts, cbet_exchange_matrix_host_polarized the one with a polarization mode on top (section
-// 20), cbet_exchange_matrix_host_banded the one with a line spectrum on top of that (section 21): the loop itself; the argument
-// builder the kernels and the twin share (gain_args) and the builder of the spectrum's difference table (band_table), which
-// the twin and the context share, live here too.
+// 20), cbet_exchange_matrix_host_banded the one with a line spectrum on top of that (section 21): the loop itself, its options
+// in the kernels' GainOptions record (cbet_host_internal.h).  The argument builder the kernels and the twin share (gain_args) and
+// the builder of the spectrum's difference table (band_table), which the twin and the context share, live here too.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -34,8 +34,7 @@ inline void add_compensated(double &sum, double &comp, double x)
 // The argument block of the gain kernels, of k_pair_amplitude, of k_exchange_matrix and of the twin below (cbet_host_internal.h):
 // here, beside the twin, so that the twin links without the HIP runtime.
 cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
-                               const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                               const double *shift, int pol, const double *band, int nband, int hx_lo, int hx_hi, bool packed)
+                               const double *fields, const double *ne3d, const GainOptions &o, int hx_lo, int hx_hi, bool packed)
 {
     GainArgs a{};
     grid_args(a, p, d);
@@ -43,8 +42,8 @@ cbet::GainArgs cbet::gain_args(const cbet_params *p, const cbet_derived &d, cons
     a.ncrit = d.ncrit; a.k0 = d.omega / kC;
     ramp_args(a, g, cs);
     a.gain_const = gc; a.iaw = g->iaw; a.relax = g->relax;
-    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = flow; a.state = state; a.sat = sat; a.shift = shift; a.pol = pol;
-    a.band = band; a.nband = band ? nband : 0;
+    a.fields = const_cast<double *>(fields); a.ne3d = ne3d; a.flow = o.flow; a.state = o.state; a.sat = o.sat; a.shift = o.shift;
+    a.pol = o.pol; a.band = o.band; a.nband = o.band ? o.nband : 0;
     a.hx_lo = hx_lo; a.hx_hi = hx_hi;
     const long plane = (long)(p->ny + 2) * (p->nz + 2);
     a.store0 = packed ? (long)hx_lo * plane : 0;
@@ -167,10 +166,12 @@ extern "C" int cbet_exchange_matrix_host_banded(const double *fields, const doub
     }
     if (nb < 2 || hx_hi == hx_lo) return CBET_OK;
     double band[1 + 2 * kBandMax];
-    const int nband = (line_domega && line_weight && nlines > 1) ? band_table(line_domega, line_weight, nlines, band, nullptr) : 0;
-    // a block with a spectrum carries shifts, as the kernels' does: zeros where none are given
-    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, flow, state, dn_max, (shift || nband) ? table : nullptr, pol,
-                                 nband ? band : nullptr, nband, hx_lo, hx_hi, false);
+    GainOptions o;
+    o.flow = flow; o.state = state; o.sat = dn_max; o.shift = shift ? table : nullptr; o.pol = pol;
+    o.nband = (line_domega && line_weight && nlines > 1) ? band_table(line_domega, line_weight, nlines, band, nullptr) : 0;
+    o.band = o.nband ? band : nullptr;
+    carry_shifts(o, table);   // as the kernels' block (without shifts the table holds zeros)
+    const GainArgs a = gain_args(p, d, g, cs, gc, fields, ne3d, o, hx_lo, hx_hi, false);
     const int HY = a.ny + 2, HZ = a.nz + 2;
     const long hsize = a.bstride, total = hsize * nb;
     const double iaw2 = a.iaw * a.iaw;

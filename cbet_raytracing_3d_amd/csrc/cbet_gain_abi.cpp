@@ -8,13 +8,6 @@
 
 using namespace cbet;
 
-// The shift table of a context's argument block: its own, or -- a context with a line spectrum and no shifts -- the zeros
-// behind its difference table (the BAND arms of the kernels run the DETUNE statements with dw = 0).
-static const double *block_shift(const cbet_context *ctx)
-{
-    return (ctx->shift || !ctx->band) ? ctx->shift : ctx->band + (1 + 2 * kBandMax);
-}
-
 int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, double *scratch, double *change, int hx_lo,
                           int hx_hi, bool packed, const cbet_params *p, const cbet_gain_params *g, cbet_context *ctx,
                           void *stream, bool consume)
@@ -26,8 +19,7 @@ int cbet::gain_field_impl(double *fields, const double *ne3d, double *gain, doub
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (hx_hi == hx_lo) return CBET_OK;   // an empty slab (more ranks than planes)
-    GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, block_shift(ctx),
-                           ctx->pol, ctx->band, ctx->nband, hx_lo, hx_hi, packed);
+    GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, context_gain_options(ctx), hx_lo, hx_hi, packed);
     a.gain = gain; a.scratch = scratch; a.change = change;
     a.consume = (consume && scratch) ? 1 : 0;
     a.frozen = g->directions_frozen ? 1 : 0;
@@ -88,7 +80,8 @@ int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, i
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (hx_hi == hx_lo) return CBET_OK;
     // sat = 0: the map is the unclamped amplitude (of the detuned gain, if the context has shifts; of the smoothed one, if that is its mode; of the summed one, if it has a line spectrum)
-    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, 0.0, block_shift(ctx), ctx->pol, ctx->band, ctx->nband, hx_lo, hx_hi, false);
+    GainOptions o = context_gain_options(ctx); o.sat = 0.0;
+    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, o, hx_lo, hx_hi, false);
     CBET_ENTER_DEVICE(ctx);
     CBET_HIP(launch_pair_amplitude(a, amp, (hipStream_t)stream));
     return CBET_OK;
@@ -118,8 +111,8 @@ int cbet_exchange_matrix(const double *fields, const double *ne3d, double *out, 
     double cs = 0, gc = 0;
     if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
     if (p->nbeams < 2 || hx_hi == hx_lo) return CBET_OK;   // one beam exchanges with nobody; an empty slab adds nothing
-    // sat, shift, pol and band = the context's: the matrix decomposes the K the solve uses, the limit, the detuning, the polarization mode and the line spectrum are honoured
-    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, ctx->flow, ctx->state, ctx->dn_max, block_shift(ctx), ctx->pol, ctx->band, ctx->nband, hx_lo, hx_hi, false);
+    // the context's options, all of them: the matrix decomposes the K the solve uses, the limit, the detuning, the polarization mode and the line spectrum are honoured
+    const GainArgs a = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, context_gain_options(ctx), hx_lo, hx_hi, false);
     CBET_ENTER_DEVICE(ctx);
     CBET_HIP(launch_exchange_matrix(a, (double *)work, out, gross, (hipStream_t)stream));
     return CBET_OK;

@@ -159,16 +159,34 @@ MeshArgs mesh_state_args(const cbet_params *p, const cbet_derived &d, const cbet
 int mesh_check(const cbet_mesh *mesh, bool whole);
 // The gain kernels', k_pair_amplitude's, k_exchange_matrix's and its host twin's (cbet_exchange_host.cpp).  cs, gc: cbet_gain_constants';
 // packed: the arrays hold the slab's planes only.  gain, scratch, change, consume and frozen stay zero: the gain update sets them.
-// shift: the per-beam frequency shifts, a table of CBET_MAX_CBET_BEAMS doubles (device memory for a kernel, host memory for the
-// twin), or NULL.  pol: the polarization mode, CBET_POL_*.  band, nband: the difference table of the line spectrum (band_table;
-// device or host memory like shift) and its entries M, or NULL: a block with a table carries a shift table too.
+// The options reach the block in ONE record, from a context (context_gain_options) or from the twin's arguments.
+constexpr int kBandMax = CBET_MAX_BAND_LINES * (CBET_MAX_BAND_LINES - 1) / 2;
+// What a gain-stage launch (or the host twin) reads beside fields and ne3d: GainArgs' members of the same names.  shift: a table
+// of CBET_MAX_CBET_BEAMS doubles, band: band_table's of nband entries (device memory for a kernel, the host's for the twin), or NULL.
+struct GainOptions {
+    const double *flow = nullptr, *state = nullptr;
+    double sat = 0.0;
+    const double *shift = nullptr;
+    int pol = CBET_POL_ALIGNED;
+    const double *band = nullptr;
+    int nband = 0;
+};
 GainArgs gain_args(const cbet_params *p, const cbet_derived &d, const cbet_gain_params *g, double cs, double gc,
-                   const double *fields, const double *ne3d, const double *flow, const double *state, double sat,
-                   const double *shift, int pol, const double *band, int nband, int hx_lo, int hx_hi, bool packed);
+                   const double *fields, const double *ne3d, const GainOptions &o, int hx_lo, int hx_hi, bool packed);
+// The ONE rule of the zero shifts, for whoever fills a GainOptions: a block with a spectrum always carries shifts too (the BAND
+// arms of the kernels run the DETUNE statements with dw = 0), the given ones or `zeros`.
+inline void carry_shifts(GainOptions &o, const double *zeros) { if (o.band && !o.shift) o.shift = zeros; }
+// A context's options, as every device entry of the gain stage launches with them (zeros: behind band_own's table).
+inline GainOptions context_gain_options(const cbet_context *ctx)
+{
+    GainOptions o;
+    o.flow = ctx->flow; o.state = ctx->state; o.sat = ctx->dn_max; o.shift = ctx->shift; o.pol = ctx->pol; o.band = ctx->band; o.nband = ctx->nband;
+    carry_shifts(o, ctx->band_own ? ctx->band_own + (1 + 2 * kBandMax) : nullptr);
+    return o;
+}
 // The line spectrum of the gain stage (cbet_exchange_host.cpp, no HIP call).  band_check: the refusals of
 // cbet_context_set_bandwidth and of the banded twin, `who` in front.  band_table: the difference table of nlines valid lines
 // into table[1 + 2 kBandMax] = {c_0, d_0, c_0', ...} and the normalised weights into norm[nlines] (or NULL); returns M.
-constexpr int kBandMax = CBET_MAX_BAND_LINES * (CBET_MAX_BAND_LINES - 1) / 2;
 int band_check(const char *who, const double *line_domega, const double *line_weight, int nlines);
 int band_table(const double *line_domega, const double *line_weight, int nlines, double *table, double *norm);
 // The slab [hx_lo, hx_hi) lies in the haloed grid; who: the entry point's name and ": " in front of the message, or "".
@@ -187,8 +205,9 @@ long lpi_groups(const cbet_params *p, int hx_lo, int hx_hi);
 hipError_t launch_lpi_map(const LpiArgs &a, cbet_lpi_summary *summary, cbet_lpi_summary *work, long groups, hipStream_t stream);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
-// The context's own table of `components` doubles per node in *slot, allocated on the first call (not capturable).
-int own_node_table(double **slot, const cbet_params *p, int components, const char *what);
+// The context's own device table of `doubles` doubles (own_node_table: `components` per node) in *slot, allocated on the first call (not capturable).
+int own_table(double **slot, size_t doubles, const char *what);
+inline int own_node_table(double **slot, const cbet_params *p, int components, const char *what) { return own_table(slot, (size_t)components * p->nx * p->ny * p->nz, what); }
 inline int flow_own_table(cbet_context *ctx, const cbet_params *p) { return own_node_table(&ctx->flow_own, p, 3, "flow table"); }     // cbet_tabulate_flow, cbet_tabulate_mesh_flow
 inline int state_own_table(cbet_context *ctx, const cbet_params *p) { return own_node_table(&ctx->state_own, p, 2, "state table"); }  // cbet_tabulate_mesh_state
 int step_records(cbet_context *ctx, const cbet_params *p, const double *ne3d, const double *kappa3d, double xconst,

@@ -48,13 +48,12 @@ int cbet::step_records(cbet_context *ctx, const cbet_params *p, const double *ne
     return CBET_OK;
 }
 
-// A context's own flow or state table, allocated by the first call on a context (not capturable).  The context's device is
-// current.
-int cbet::own_node_table(double **slot, const cbet_params *p, int components, const char *what)
+// A context's own flow, state, detuning or bandwidth table, allocated by the first call on a context (not capturable).  The
+// context's device is current.
+int cbet::own_table(double **slot, size_t doubles, const char *what)
 {
     if (*slot) return CBET_OK;
-    const size_t nodes = (size_t)p->nx * p->ny * p->nz;
-    hipError_t e = hipMalloc((void **)slot, components * nodes * sizeof(double));
+    hipError_t e = hipMalloc((void **)slot, doubles * sizeof(double));
     if (e != hipSuccess) {
         *slot = nullptr;
         return fail_hip(e == hipErrorOutOfMemory ? CBET_ENOMEM : CBET_EHIP, "hipMalloc(%s): %s", what, hipGetErrorString(e));

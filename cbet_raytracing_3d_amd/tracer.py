@@ -111,19 +111,9 @@ class RayTracer:
             self._tables_filled = True
         self._tabulate_flow(ctx, params)
         self._tabulate_state(ctx, params)
-        ctx.set_saturation(self.saturation)         # a context prepared for this tracer carries its limit, as it carries its tables
-        # ... and the frequency shifts the tracer's own context was last given (set_detuning, or a caller's call on it): a
-        # set-up call, made only when they changed
-        own = self.ctx.detuning_source
-        if ctx is not self.ctx and ctx.detuning_source is not own:
-            ctx.set_detuning(own, self._stream())
-            ctx.detuning_source = own
-        if ctx is not self.ctx:                     # ... and its polarization mode (set_polarization)
-            ctx.set_polarization(self.ctx.polarization())
-        band = self.ctx.bandwidth_source            # ... and its line spectrum (set_bandwidth), as the shifts
-        if ctx is not self.ctx and ctx.bandwidth_source is not band:
-            ctx.set_bandwidth(*((None,) if band is None else band), stream=self._stream())
-            ctx.bandwidth_source = band
+        if ctx is not self.ctx:     # a prepared context carries what the tracer's own was last given, by the tracer or by a caller
+            ctx.adopt_beam_options(self.ctx, self._stream())
+        ctx.set_saturation(self.saturation)         # ... but the TRACER's limit, like the tracer's own
 
     def _tabulate_other(self, ctx, params):
         """The node tables of `ctx` from the mesh or on the target, if one is set, on torch's current stream: True.  False

@@ -16,13 +16,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from cbet_raytracing_3d_amd import build
 from conftest import NCPU, ROOT
 from helpers import bandwidth_cases as BC
 from helpers import detuning_cases as DC
 from helpers import exchange_cases as XC
 from helpers import gain_worlds as W
 from helpers import polarization_cases as PC
+from helpers import twin_driver as TD
 from helpers.gain_reference import Restatement
 from helpers.gain_worlds import TOL
 
@@ -414,122 +414,70 @@ def test_slabs_add_up_on_crowded(api, crowded):
 
 
 # ---- the twin as a stand-alone program under the sanitizers ---------------------------------------------------------------
-DRIVER = r'''
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <initializer_list>
-#include <limits>
-#include "cbet_mi355x.h"
-
-#define REQUIRE(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "FAILED %s: ", #cond); std::fprintf(stderr, __VA_ARGS__); \
-                                               std::fprintf(stderr, "\n"); std::exit(1); } } while (0)
-
-static double *block(size_t n) { double *p = (double *)std::calloc(n ? n : 1, sizeof(double)); REQUIRE(p, "calloc"); return p; }
-static bool same(const double *a, const double *b, size_t n) { return std::memcmp(a, b, n * sizeof(double)) == 0; }
-
-// One grid, nb beams, nl lines: every array a heap block of exactly its size (an index out of range is the sanitizer's to
-// catch).  Every beam has |k| = kmag of its cell, as the normalisation leaves it.
-static void run(int nb, int nl, double *checksum)
-{
-    cbet_params p;
-    REQUIRE(cbet_params_default(&p, 6) == CBET_OK, "%s", cbet_last_error());
-    p.ny = 5; p.nz = 7; p.nbeams = nb;
-    cbet_gain_params g;
-    REQUIRE(cbet_gain_params_default(&g) == CBET_OK, "%s", cbet_last_error());
-    cbet_derived d;
-    REQUIRE(cbet_derive(&p, &d) == CBET_OK, "%s", cbet_last_error());
-    const int hy = p.ny + 2, hz = p.nz + 2;
-    const long nodes = (long)p.nx * p.ny * p.nz, cells = (long)(p.nx + 2) * hy * hz, total = nb * cells;
-    double *ne3d = block(nodes), *flow = block(3 * nodes), *still = block(3 * nodes), *state = block(2 * nodes), *fields = block(4 * total);
-    double *shift = block(nb), *minus = block(nb), *off = block(nl), *wts = block(nl);
-    for (long n = 0; n < nodes; ++n) {
-        ne3d[n] = d.ncrit * (0.05 + 0.9 * (double)((7 * n) % nodes) / nodes);
-        for (int x = 0; x < 3; ++x) flow[n + x * nodes] = 2e7 * std::sin(0.7 * n + x);
-        state[n] = 2e7 + 1e6 * (n % 5); state[n + nodes] = 1e-19 * (1 + n % 3);
-    }
-    ne3d[17] = 2.5 * d.ncrit;                                   // a super-critical node
-    for (int b = 0; b < nb; ++b) { shift[b] = 4.6e12 * (((37 * b) % 60) - 29.5) / 30.0; minus[b] = -shift[b]; }
-    for (int a = 0; a < nl; ++a) { off[a] = 1099511627776.0 * (a - 0.5 * (nl - 1)); wts[a] = 1.0 + (a % 3); }   // a 2^40 grid: differences merge
-    const double k0 = d.omega / 29979245800.0;
-    auto clampi = [](int v, int n) { return v < 1 ? 0 : (v > n ? n - 1 : v - 1); };
-    for (long h = 0; h < cells; ++h) {
-        const int hi = (int)(h / ((long)hy * hz)), hj = (int)((h / hz) % hy), hk = (int)(h % hz);
-        const long node = ((long)clampi(hi, p.nx) * p.ny + clampi(hj, p.ny)) * p.nz + clampi(hk, p.nz);
-        const double eps = 1.0 - ne3d[node] / d.ncrit;
-        const double kmag = eps > 0.0 ? k0 * std::sqrt(eps) : 0.0;
-        for (int b = 0; b < nb; ++b) {
-            const bool absent = (h + 3 * b) % 7 == 0 || !(eps > 0.0);
-            const double t = 0.3 + 0.01 * h + 0.9 * (b % 16), s = 0.2 + 0.05 * b;
-            fields[b * cells + h] = absent ? 0.0 : 1e14 * (1 + (h + b) % 4);
-            fields[total + b * cells + h] = absent ? 0.0 : kmag * std::cos(t) * std::cos(s);
-            fields[2 * total + b * cells + h] = absent ? 0.0 : kmag * std::sin(t) * std::cos(s);
-            fields[3 * total + b * cells + h] = absent ? 0.0 : kmag * std::sin(s);
+DRIVER = TD.PRELUDE + r'''
+// The cases of the banded twin on one world of nb beams, every beam with |k| = kmag of its cell, and nl lines.
+struct Banded : World {
+    explicit Banded(int beams) : World(beams, true) {}
+    void run(int nl, double *checksum)
+    {
+        double *off = block(nl), *wts = block(nl);
+        for (int a = 0; a < nl; ++a) { off[a] = 1099511627776.0 * (a - 0.5 * (nl - 1)); wts[a] = 1.0 + (a % 3); }   // a 2^40 grid: differences merge
+        auto twin = [&](double *t, double *gr, const double *fl, const double *st, double dn, const double *w, int pol, int lines, int lo, int hi) {
+            std::memset(t, 0, m * sizeof(double)); std::memset(gr, 0, m * sizeof(double));
+            REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, t, gr, lo, hi, &p, &g, fl, st, dn, w, pol, off, wts, lines) == CBET_OK, "%s", cbet_last_error());
+        };
+        for (int tables = 0; tables < 2; ++tables)
+            for (double dn : {0.0, 1e-4})
+                for (int shifted = 0; shifted < 2; ++shifted)
+                    for (int pol : {CBET_POL_ALIGNED, CBET_POL_SMOOTHED}) {
+                        const double *fl = tables ? flow : nullptr, *st = tables ? state : nullptr, *w = shifted ? shift : nullptr;
+                        twin(T, G, fl, st, dn, w, pol, 0, 0, hx);             // no lines: the bits of the polarized twin
+                        std::memset(T2, 0, m * sizeof(double)); std::memset(G2, 0, m * sizeof(double));
+                        REQUIRE(cbet_exchange_matrix_host_polarized(fields, ne3d, T2, G2, 0, hx, &p, &g, fl, st, dn, w, pol) == CBET_OK, "%s", cbet_last_error());
+                        REQUIRE(same(T, T2, m) && same(G, G2, m), "no lines is not the polarized twin (tables %d, dn_max %g, shifts %d, pol %d)", tables, dn, shifted, pol);
+                        twin(T2, G2, fl, st, dn, w, pol, nl, 0, hx);
+                        if (nl == 1) REQUIRE(same(T, T2, m) && same(G, G2, m), "one line is not the polarized twin");
+                        for (int i = 0; i < nb; ++i)
+                            for (int j = 0; j < nb; ++j) {
+                                const double a = T2[i * nb + j], b = -T2[j * nb + i];
+                                REQUIRE(same(&a, &b, 1) || (a == 0.0 && b == 0.0), "T[%d][%d] %a, T[%d][%d] %a", i, j, a, j, i, T2[j * nb + i]);
+                                REQUIRE(G2[i * nb + j] >= std::fabs(T2[i * nb + j]), "Gross[%d][%d]", i, j);
+                                *checksum += T2[i * nb + j] + G2[i * nb + j];
+                            }
+                        if (nb >= 2) REQUIRE(T2[1] == 0.0 && G2[1] == 0.0, "parallel beams exchange %a", T2[1]);
+                    }
+        twin(T2, G2, still, nullptr, 0.0, nullptr, CBET_POL_ALIGNED, nl, 0, hx);   // still plasma, no shifts: exact zeros
+        for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == 0.0 && G2[k] == 0.0, "still plasma exchanges %a at entry %zu", T2[k], k);
+        twin(T, G, still, state, 1e-4, shift, CBET_POL_SMOOTHED, nl, 0, hx);       // still plasma: negated shifts negate T
+        twin(T2, G2, still, state, 1e-4, minus, CBET_POL_SMOOTHED, nl, 0, hx);
+        for (size_t k = 0; k < m; ++k) { const double a = -T2[k]; REQUIRE((same(&a, &T[k], 1) || (a == 0.0 && T[k] == 0.0)) && same(&G2[k], &G[k], 1), "negated shifts: entry %zu", k); }
+        twin(T2, G2, nullptr, nullptr, 0.0, shift, CBET_POL_SMOOTHED, nl, 2, 2);   // an empty slab
+        for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == 0.0, "an empty slab wrote entry %zu", k);
+        twin(T, G, flow, state, 1e-4, shift, CBET_POL_SMOOTHED, nl, 0, hx);        // slabs add up
+        std::memset(T2, 0, m * sizeof(double)); std::memset(G2, 0, m * sizeof(double));
+        for (int lo = 0; lo < hx; lo += 3)
+            REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, lo, lo + 3 < hx ? lo + 3 : hx, &p, &g, flow, state, 1e-4, shift,
+                                                     CBET_POL_SMOOTHED, off, wts, nl) == CBET_OK, "%s", cbet_last_error());
+        for (size_t k = 0; k < m; ++k) REQUIRE(std::fabs(T2[k] - T[k]) <= 1e-13 * G[k], "slabs: entry %zu: %a against %a", k, T2[k], T[k]);
+        if (nl >= 2) {                                                              // a NaN offset, a bad weight, too many lines
+            const double keep = off[nl - 1], wkeep = wts[0];
+            off[nl - 1] = std::numeric_limits<double>::quiet_NaN();
+            REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, nullptr, 0, off, wts, nl) == CBET_EINVAL, "a NaN offset passed");
+            REQUIRE(std::strstr(cbet_last_error(), "is NaN"), "%s", cbet_last_error());
+            off[nl - 1] = keep; wts[0] = 0.0;
+            REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, nullptr, 0, off, wts, nl) == CBET_EINVAL, "a zero weight passed");
+            wts[0] = wkeep;
         }
+        REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, nullptr, 0, off, wts, CBET_MAX_BAND_LINES + 1) == CBET_EINVAL, "nine lines passed");
+        std::free(off); std::free(wts);
     }
-    if (nb >= 2)                                                // beams 0 and 1 parallel in every cell: they exchange nothing
-        for (long h = 0; h < cells; ++h)
-            for (int x = 1; x < 4; ++x) fields[x * total + cells + h] = fields[x * total + h];
-    const size_t m = (size_t)nb * nb;
-    double *T = block(m), *G = block(m), *T2 = block(m), *G2 = block(m);
-    auto twin = [&](double *t, double *gr, const double *fl, const double *st, double dn, const double *w, int pol, int lines, int lo, int hi) {
-        std::memset(t, 0, m * sizeof(double)); std::memset(gr, 0, m * sizeof(double));
-        REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, t, gr, lo, hi, &p, &g, fl, st, dn, w, pol, off, wts, lines) == CBET_OK, "%s", cbet_last_error());
-    };
-    const int hx = p.nx + 2;
-    for (int tables = 0; tables < 2; ++tables)
-        for (double dn : {0.0, 1e-4})
-            for (int shifted = 0; shifted < 2; ++shifted)
-                for (int pol : {CBET_POL_ALIGNED, CBET_POL_SMOOTHED}) {
-                    const double *fl = tables ? flow : nullptr, *st = tables ? state : nullptr, *w = shifted ? shift : nullptr;
-                    twin(T, G, fl, st, dn, w, pol, 0, 0, hx);             // no lines: the bits of the polarized twin
-                    std::memset(T2, 0, m * sizeof(double)); std::memset(G2, 0, m * sizeof(double));
-                    REQUIRE(cbet_exchange_matrix_host_polarized(fields, ne3d, T2, G2, 0, hx, &p, &g, fl, st, dn, w, pol) == CBET_OK, "%s", cbet_last_error());
-                    REQUIRE(same(T, T2, m) && same(G, G2, m), "no lines is not the polarized twin (tables %d, dn_max %g, shifts %d, pol %d)", tables, dn, shifted, pol);
-                    twin(T2, G2, fl, st, dn, w, pol, nl, 0, hx);
-                    if (nl == 1) REQUIRE(same(T, T2, m) && same(G, G2, m), "one line is not the polarized twin");
-                    for (int i = 0; i < nb; ++i)
-                        for (int j = 0; j < nb; ++j) {
-                            const double a = T2[i * nb + j], b = -T2[j * nb + i];
-                            REQUIRE(same(&a, &b, 1) || (a == 0.0 && b == 0.0), "T[%d][%d] %a, T[%d][%d] %a", i, j, a, j, i, T2[j * nb + i]);
-                            REQUIRE(G2[i * nb + j] >= std::fabs(T2[i * nb + j]), "Gross[%d][%d]", i, j);
-                            *checksum += T2[i * nb + j] + G2[i * nb + j];
-                        }
-                    if (nb >= 2) REQUIRE(T2[1] == 0.0 && G2[1] == 0.0, "parallel beams exchange %a", T2[1]);
-                }
-    twin(T2, G2, still, nullptr, 0.0, nullptr, CBET_POL_ALIGNED, nl, 0, hx);   // still plasma, no shifts: exact zeros
-    for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == 0.0 && G2[k] == 0.0, "still plasma exchanges %a at entry %zu", T2[k], k);
-    twin(T, G, still, state, 1e-4, shift, CBET_POL_SMOOTHED, nl, 0, hx);       // still plasma: negated shifts negate T
-    twin(T2, G2, still, state, 1e-4, minus, CBET_POL_SMOOTHED, nl, 0, hx);
-    for (size_t k = 0; k < m; ++k) { const double a = -T2[k]; REQUIRE((same(&a, &T[k], 1) || (a == 0.0 && T[k] == 0.0)) && same(&G2[k], &G[k], 1), "negated shifts: entry %zu", k); }
-    twin(T2, G2, nullptr, nullptr, 0.0, shift, CBET_POL_SMOOTHED, nl, 2, 2);   // an empty slab
-    for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == 0.0, "an empty slab wrote entry %zu", k);
-    twin(T, G, flow, state, 1e-4, shift, CBET_POL_SMOOTHED, nl, 0, hx);        // slabs add up
-    std::memset(T2, 0, m * sizeof(double)); std::memset(G2, 0, m * sizeof(double));
-    for (int lo = 0; lo < hx; lo += 3)
-        REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, lo, lo + 3 < hx ? lo + 3 : hx, &p, &g, flow, state, 1e-4, shift,
-                                                 CBET_POL_SMOOTHED, off, wts, nl) == CBET_OK, "%s", cbet_last_error());
-    for (size_t k = 0; k < m; ++k) REQUIRE(std::fabs(T2[k] - T[k]) <= 1e-13 * G[k], "slabs: entry %zu: %a against %a", k, T2[k], T[k]);
-    if (nl >= 2) {                                                              // a NaN offset, a bad weight, too many lines
-        const double keep = off[nl - 1], wkeep = wts[0];
-        off[nl - 1] = std::numeric_limits<double>::quiet_NaN();
-        REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, nullptr, 0, off, wts, nl) == CBET_EINVAL, "a NaN offset passed");
-        REQUIRE(std::strstr(cbet_last_error(), "is NaN"), "%s", cbet_last_error());
-        off[nl - 1] = keep; wts[0] = 0.0;
-        REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, nullptr, 0, off, wts, nl) == CBET_EINVAL, "a zero weight passed");
-        wts[0] = wkeep;
-    }
-    REQUIRE(cbet_exchange_matrix_host_banded(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, nullptr, 0, off, wts, CBET_MAX_BAND_LINES + 1) == CBET_EINVAL, "nine lines passed");
-    std::free(ne3d); std::free(flow); std::free(still); std::free(state); std::free(fields); std::free(shift); std::free(minus);
-    std::free(off); std::free(wts); std::free(T); std::free(G); std::free(T2); std::free(G2);
-}
+};
 
 int main()
 {
     double checksum = 0.0;
     for (int nb : {1, 2, 7, 64})
-        for (int nl : {1, 2, 8}) run(nb, nl, &checksum);
+        for (int nl : {1, 2, 8}) Banded(nb).run(nl, &checksum);
     std::printf("banded twin ok: checksum %.17g\n", checksum);
     return 0;
 }
@@ -541,16 +489,5 @@ def test_banded_twin_is_clean_under_asan_ubsan(tmp_path):
     (cbet_exchange_host.cpp) and the host arithmetic (cbet_params.cpp) compiled with the sanitizers into a program of their
     own, no HIP library on the link line: 1, 2, 7 and 64 beams x 1, 2 and 8 lines, heap blocks of exactly their size, a parallel
     pair, a NaN offset; nothing is loaded into Python."""
-    src = tmp_path / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = str(tmp_path / "driver")
-    hip_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc()))), "include")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-I", hip_include,
-                           "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(src),
-                           os.path.join(CSRC, "cbet_exchange_host.cpp"), os.path.join(CSRC, "cbet_params.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "banded twin ok" in out.stdout and "checksum" in out.stdout
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr
+    out = TD.run_driver(tmp_path, DRIVER)
+    assert "banded twin ok" in out and "checksum" in out

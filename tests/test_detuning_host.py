@@ -14,12 +14,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from cbet_raytracing_3d_amd import build
 from conftest import NCPU, ROOT
 from helpers import detuning_cases as DC
 from helpers import exchange_cases as XC
 from helpers import gain_worlds as W
 from helpers import saturation_cases as SC
+from helpers import twin_driver as TD
 from helpers.gain_worlds import LAST_BITS         # here of Gross_ij: tests/test_exchange_host.py's bound
 
 NAMES = ("cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted")
@@ -253,97 +253,55 @@ def test_slabs_of_the_shifted_twin_add_up(api, crowded):
 
 
 # ---- the twin as a stand-alone program under the sanitizers ---------------------------------------------------------------
-DRIVER = r'''
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <initializer_list>
-#include "cbet_mi355x.h"
-
-#define REQUIRE(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "FAILED %s: ", #cond); std::fprintf(stderr, __VA_ARGS__); \
-                                               std::fprintf(stderr, "\n"); std::exit(1); } } while (0)
-
-static double *block(size_t n) { double *p = (double *)std::calloc(n, sizeof(double)); REQUIRE(p, "calloc"); return p; }
-static bool same(const double *a, const double *b, size_t n) { return std::memcmp(a, b, n * sizeof(double)) == 0; }
-
-// One grid, nb beams: every array a heap block of exactly its size (an index out of range is the sanitizer's to catch).
-static void run(int nb, double *checksum)
-{
-    cbet_params p;
-    REQUIRE(cbet_params_default(&p, 6) == CBET_OK, "%s", cbet_last_error());
-    p.ny = 5; p.nz = 7; p.nbeams = nb;
-    cbet_gain_params g;
-    REQUIRE(cbet_gain_params_default(&g) == CBET_OK, "%s", cbet_last_error());
-    cbet_derived d;
-    REQUIRE(cbet_derive(&p, &d) == CBET_OK, "%s", cbet_last_error());
-    const long nodes = (long)p.nx * p.ny * p.nz, cells = (long)(p.nx + 2) * (p.ny + 2) * (p.nz + 2), total = nb * cells;
-    double *ne3d = block(nodes), *still = block(3 * nodes), *flow = block(3 * nodes), *state = block(2 * nodes), *fields = block(4 * total);
-    double *shift = block(nb), *minus = block(nb), *equal = block(nb);
-    for (long n = 0; n < nodes; ++n) {
-        ne3d[n] = d.ncrit * (0.05 + 0.9 * (double)((7 * n) % nodes) / nodes);
-        for (int x = 0; x < 3; ++x) flow[n + x * nodes] = 2e7 * std::sin(0.7 * n + x);
-        state[n] = 2e7 + 1e6 * (n % 5); state[n + nodes] = 1e-19 * (1 + n % 3);
-    }
-    ne3d[17] = 2.5 * d.ncrit;                                   // a super-critical node
-    for (int b = 0; b < nb; ++b) { shift[b] = 4.6e12 * (((37 * b) % 60) - 29.5) / 30.0; minus[b] = -shift[b]; equal[b] = 3.3e12; }
-    const double k0 = d.omega / 29979245800.0;
-    for (long h = 0; h < cells; ++h)
-        for (int b = 0; b < nb; ++b) {
-            const bool absent = (h + 3 * b) % 7 == 0;
-            const double t = 0.3 + 0.01 * h + 0.9 * (b % 16), s = 0.2 + 0.05 * b;
-            fields[b * cells + h] = absent ? 0.0 : 1e14 * (1 + (h + b) % 4);
-            fields[total + b * cells + h] = absent ? 0.0 : 0.8 * k0 * std::cos(t) * std::cos(s);
-            fields[2 * total + b * cells + h] = absent ? 0.0 : 0.8 * k0 * std::sin(t) * std::cos(s);
-            fields[3 * total + b * cells + h] = absent ? 0.0 : 0.8 * k0 * std::sin(s);
+DRIVER = TD.PRELUDE + r'''
+// The cases of the shifted twin on one world of nb beams (|k| = 0.8 k0 everywhere).
+struct Shifted : World {
+    explicit Shifted(int beams) : World(beams, false) {}
+    void run(double *checksum)
+    {
+        double *equal = block(nb);
+        for (int b = 0; b < nb; ++b) equal[b] = 3.3e12;
+        auto twin = [&](double *t, double *gr, const double *fl, const double *st, double dn, const double *w, int lo, int hi) {
+            std::memset(t, 0, m * sizeof(double)); std::memset(gr, 0, m * sizeof(double));
+            REQUIRE(cbet_exchange_matrix_host_shifted(fields, ne3d, t, gr, lo, hi, &p, &g, fl, st, dn, w) == CBET_OK, "%s", cbet_last_error());
+        };
+        for (int tables = 0; tables < 2; ++tables)
+            for (double dn : {0.0, 1e-4}) {
+                const double *fl = tables ? flow : nullptr, *st = tables ? state : nullptr;
+                twin(T, G, fl, st, dn, shift, 0, hx);
+                for (int i = 0; i < nb; ++i)
+                    for (int j = 0; j < nb; ++j) {
+                        const double a = T[i * nb + j], b = -T[j * nb + i];
+                        REQUIRE(same(&a, &b, 1) || (a == 0.0 && b == 0.0), "T[%d][%d] %a, T[%d][%d] %a", i, j, T[i * nb + j], j, i, T[j * nb + i]);
+                        REQUIRE(G[i * nb + j] >= std::fabs(T[i * nb + j]), "Gross[%d][%d]", i, j);
+                        *checksum += T[i * nb + j] + G[i * nb + j];
+                    }
+                if (nb >= 2) REQUIRE(T[1] == 0.0 && G[1] == 0.0, "parallel beams of different colour exchange %a", T[1]);
+                twin(T, G, fl, st, dn, nullptr, 0, hx);             // one colour: NULL and equal shifts give the same bits
+                twin(T2, G2, fl, st, dn, equal, 0, hx);
+                REQUIRE(same(T, T2, m) && same(G, G2, m), "equal shifts change a bit (tables %d, dn_max %g)", tables, dn);
+                std::memset(T2, 0, m * sizeof(double)); std::memset(G2, 0, m * sizeof(double));
+                REQUIRE(cbet_exchange_matrix_host(fields, ne3d, T2, G2, 0, hx, &p, &g, fl, st, dn) == CBET_OK, "%s", cbet_last_error());
+                REQUIRE(same(T, T2, m) && same(G, G2, m), "cbet_exchange_matrix_host is not the shifted twin with NULL");
+            }
+        twin(T, G, still, nullptr, 0.0, shift, 0, hx);              // still plasma: negated shifts negate T
+        twin(T2, G2, still, nullptr, 0.0, minus, 0, hx);
+        for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == -T[k] && G2[k] == G[k], "entry %zu: %a against %a", k, T2[k], T[k]);
+        twin(T2, G2, still, nullptr, 0.0, shift, 2, 2);             // an empty slab
+        for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == 0.0, "an empty slab wrote entry %zu", k);
+        if (nb >= 2) {
+            shift[nb - 1] = NAN;
+            REQUIRE(cbet_exchange_matrix_host_shifted(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, shift) == CBET_EINVAL, "a NaN shift passed");
+            REQUIRE(std::strstr(cbet_last_error(), "shift["), "%s", cbet_last_error());
         }
-    if (nb >= 2)                                                // beams 0 and 1 parallel in every cell: they exchange nothing
-        for (long h = 0; h < cells; ++h)
-            for (int x = 1; x < 4; ++x) fields[x * total + cells + h] = fields[x * total + h];
-    const size_t m = (size_t)nb * nb;
-    double *T = block(m), *G = block(m), *T2 = block(m), *G2 = block(m);
-    auto twin = [&](double *t, double *gr, const double *fl, const double *st, double dn, const double *w, int lo, int hi) {
-        std::memset(t, 0, m * sizeof(double)); std::memset(gr, 0, m * sizeof(double));
-        REQUIRE(cbet_exchange_matrix_host_shifted(fields, ne3d, t, gr, lo, hi, &p, &g, fl, st, dn, w) == CBET_OK, "%s", cbet_last_error());
-    };
-    const int hx = p.nx + 2;
-    for (int tables = 0; tables < 2; ++tables)
-        for (double dn : {0.0, 1e-4}) {
-            const double *fl = tables ? flow : nullptr, *st = tables ? state : nullptr;
-            twin(T, G, fl, st, dn, shift, 0, hx);
-            for (int i = 0; i < nb; ++i)
-                for (int j = 0; j < nb; ++j) {
-                    const double a = T[i * nb + j], b = -T[j * nb + i];
-                    REQUIRE(same(&a, &b, 1) || (a == 0.0 && b == 0.0), "T[%d][%d] %a, T[%d][%d] %a", i, j, T[i * nb + j], j, i, T[j * nb + i]);
-                    REQUIRE(G[i * nb + j] >= std::fabs(T[i * nb + j]), "Gross[%d][%d]", i, j);
-                    *checksum += T[i * nb + j] + G[i * nb + j];
-                }
-            if (nb >= 2) REQUIRE(T[1] == 0.0 && G[1] == 0.0, "parallel beams of different colour exchange %a", T[1]);
-            twin(T, G, fl, st, dn, nullptr, 0, hx);             // one colour: NULL and equal shifts give the same bits
-            twin(T2, G2, fl, st, dn, equal, 0, hx);
-            REQUIRE(same(T, T2, m) && same(G, G2, m), "equal shifts change a bit (tables %d, dn_max %g)", tables, dn);
-            std::memset(T2, 0, m * sizeof(double)); std::memset(G2, 0, m * sizeof(double));
-            REQUIRE(cbet_exchange_matrix_host(fields, ne3d, T2, G2, 0, hx, &p, &g, fl, st, dn) == CBET_OK, "%s", cbet_last_error());
-            REQUIRE(same(T, T2, m) && same(G, G2, m), "cbet_exchange_matrix_host is not the shifted twin with NULL");
-        }
-    twin(T, G, still, nullptr, 0.0, shift, 0, hx);              // still plasma: negated shifts negate T
-    twin(T2, G2, still, nullptr, 0.0, minus, 0, hx);
-    for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == -T[k] && G2[k] == G[k], "entry %zu: %a against %a", k, T2[k], T[k]);
-    twin(T2, G2, still, nullptr, 0.0, shift, 2, 2);             // an empty slab
-    for (size_t k = 0; k < m; ++k) REQUIRE(T2[k] == 0.0, "an empty slab wrote entry %zu", k);
-    if (nb >= 2) {
-        shift[nb - 1] = NAN;
-        REQUIRE(cbet_exchange_matrix_host_shifted(fields, ne3d, T2, G2, 0, hx, &p, &g, nullptr, nullptr, 0.0, shift) == CBET_EINVAL, "a NaN shift passed");
-        REQUIRE(std::strstr(cbet_last_error(), "shift["), "%s", cbet_last_error());
+        std::free(equal);
     }
-    std::free(ne3d); std::free(still); std::free(flow); std::free(state); std::free(fields);
-    std::free(shift); std::free(minus); std::free(equal); std::free(T); std::free(G); std::free(T2); std::free(G2);
-}
+};
 
 int main()
 {
     double checksum = 0.0;
-    for (int nb : {1, 2, 7, 64}) run(nb, &checksum);
+    for (int nb : {1, 2, 7, 64}) Shifted(nb).run(&checksum);
     std::printf("shifted twin ok: checksum %.17g\n", checksum);
     return 0;
 }
@@ -354,16 +312,5 @@ def test_shifted_twin_is_clean_under_asan_ubsan(tmp_path):
     """The twin with the argument builder it shares with the kernels (cbet_exchange_host.cpp) and the host arithmetic
     (cbet_params.cpp) compiled with the sanitizers into a program of their own, no HIP library on the link line; nothing is
     loaded into Python."""
-    src = tmp_path / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = str(tmp_path / "driver")
-    hip_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc()))), "include")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-I", hip_include,
-                           "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(src),
-                           os.path.join(CSRC, "cbet_exchange_host.cpp"), os.path.join(CSRC, "cbet_params.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "shifted twin ok" in out.stdout and "checksum" in out.stdout
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr
+    out = TD.run_driver(tmp_path, DRIVER)
+    assert "shifted twin ok" in out and "checksum" in out

@@ -136,6 +136,42 @@ def test_context_remembers_replaces_and_refuses(api, torch_cuda, worlds):
         _clear(tr)
 
 
+def test_prepared_context_adopts_all_four_beam_options(api, torch_cuda, worlds):
+    """A limit, "smoothed", sixty distinct shifts and a three-line spectrum on one tracer: a context prepared for it reads all
+    four back; prepared again with nothing changed it makes no set-up call (the arrays it has recorded are the very ones the
+    tracer's context recorded); with the shifts and the spectrum cleared it loses both and keeps the limit and the mode."""
+    tr = worlds["crowded"]["tr"]
+    other = api.Context(tr.params, tr.gpu)
+    try:
+        shifts, (off, wts) = DC.shifts(tr.params.nbeams), BC.lines("three")
+        tr.set_saturation(0.0125)
+        tr.set_polarization("smoothed")
+        tr.set_detuning(domega=shifts)
+        tr.set_bandwidth(off, wts)
+        assert other.given_beam_options() == (None, None)
+        tr._prepare_plasma(tr.params, other)
+        for ctx in (tr.ctx, other):
+            assert ctx.saturation() == 0.0125 and ctx.polarization() == "smoothed"
+            assert np.array_equal(ctx.detuning(), shifts)
+            assert np.array_equal(ctx.bandwidth()[0], off) and np.array_equal(ctx.bandwidth()[1], wts / wts.sum())
+        given = other.given_beam_options()
+        assert given[0] is tr.ctx.given_beam_options()[0] and given[1] is tr.ctx.given_beam_options()[1]
+        assert given[0] is not None and given[1] is not None
+        tr._prepare_plasma(tr.params, other)                    # nothing changed: nothing is set up again
+        again = other.given_beam_options()
+        assert again[0] is given[0] and again[1] is given[1]
+        assert again[0] is tr.ctx.given_beam_options()[0] and again[1] is tr.ctx.given_beam_options()[1]
+        assert np.array_equal(other.detuning(), shifts) and np.array_equal(other.bandwidth()[0], off)
+        tr.set_detuning()
+        tr.set_bandwidth()
+        tr._prepare_plasma(tr.params, other)
+        assert other.detuning() is None and other.bandwidth() is None and other.given_beam_options() == (None, None)
+        assert other.saturation() == 0.0125 and other.polarization() == "smoothed"
+    finally:
+        other.close()
+        _clear(tr)
+
+
 # ---- 1. no spectrum is no spectrum ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("config", [("none", False, "none"), ("tabled", True, "half")], ids=["plain", "everything"])
 @pytest.mark.parametrize("grid", GRIDS)

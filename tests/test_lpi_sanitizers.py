@@ -4,13 +4,7 @@ the fields of its own cell only, finds a cone bin inside [0, NB) for every direc
 and writes its seven quantities inside the stack.  As tests/test_gain_model_sanitizers.py: a stand-alone C++ program walks
 every haloed cell of a 5 x 4 x 3 grid and of a 5 x 2 x 3 one through the header with NB = 1, 8 and 16, every array a heap
 block of exactly its size, under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; nothing is loaded into Python)."""
-import os
-import subprocess
-
-from cbet_raytracing_3d_amd import build
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "cbet_raytracing_3d_amd", "csrc")
+from helpers.twin_driver import run_driver
 
 DRIVER = r'''
 #include <cmath>
@@ -136,15 +130,5 @@ int main()
 
 
 def test_lpi_model_stays_in_bounds_under_asan_ubsan(tmp_path):
-    src = tmp_path / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = str(tmp_path / "driver")
-    hip_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc()))), "include")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-I", hip_include,
-                           "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(src), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "lpi model ok" in out.stdout and "checksum" in out.stdout
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr
+    out = run_driver(tmp_path, DRIVER, sources=())
+    assert "lpi model ok" in out and "checksum" in out

@@ -3,13 +3,7 @@ the indices mesh_locate produces, which lie inside the arrays whatever the coord
 tests/test_mesh_sanitizers.py: a stand-alone C++ program runs mesh_locate and the state statements on meshes whose coordinate
 arrays hold NaN, infinities, descending, constant and random values, te, ti and zbar heap blocks of exactly their size (ti and
 zbar once present, once NULL), under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; nothing is loaded into Python)."""
-import os
-import subprocess
-
-from cbet_raytracing_3d_amd import build
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "cbet_raytracing_3d_amd", "csrc")
+from helpers.twin_driver import run_driver
 
 DRIVER = r'''
 #include <cmath>
@@ -99,13 +93,5 @@ int main()
 
 
 def test_state_model_stays_in_bounds_under_asan_ubsan(tmp_path):
-    src = tmp_path / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = str(tmp_path / "driver")
-    hip_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc()))), "include")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-I", hip_include,
-                           "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(src), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "state model ok" in out.stdout and "ERROR" not in out.stderr and "runtime error" not in out.stderr
+    out = run_driver(tmp_path, DRIVER, sources=())
+    assert "state model ok" in out
