@@ -150,6 +150,57 @@ struct WaveCounters {
     // by the kernel's lambdas, renumbers the shipped kernel's registers although it is empty.
     [[no_unique_address]] WaveDiag dg;
 };
+// ... of the plain trace, whose window misses go out PAIRED (miss_add8): the same counters under a type of their own
+struct PairedMissCounters : WaveCounters {};
+
+// Paired window misses: a miss lane L's eight sums are four (x, y) columns of two z nodes, adjacent doubles that share a
+// 64-B line unless the lower one ends it.  The memory-side atomic unit is priced per 64-B request and two addends to one
+// line merge into one request only when they leave in ONE wave instruction -- so L sends a column's first-visited value
+// itself and its quad neighbour L ^ 1 sends the other one in the same instruction, at the node L names (a cross-lane move
+// within the quad): four or five requests per flush instead of eight.  The neighbour lends its lane slot and nothing else.
+// Two rounds: the even miss lanes through their odd neighbours, then the odd ones through their even neighbours.
+constexpr unsigned long long kEvenLanes = 0x5555555555555555ull;
+__device__ __forceinline__ unsigned long long pair_owners(unsigned long long hbm_m, int round)
+{
+    return hbm_m & (round == 0 ? kEvenLanes : ~kEvenLanes);
+}
+// ... the lanes a round's atomics run on: the owners and the neighbours that carry for them
+__device__ __forceinline__ unsigned long long pair_lanes(unsigned long long owners, int round)
+{
+    return owners | (round == 0 ? owners << 1 : owners >> 1);
+}
+// ... the vector-memory instructions a paired flush issues: four per round that has an owner
+__device__ __forceinline__ int pair_issued(unsigned long long hbm_m)
+{
+    return (pair_owners(hbm_m, 0) != 0ull ? 4 : 0) + (pair_owners(hbm_m, 1) != 0ull ? 4 : 0);
+}
+// An owner's `mine`, a carrier's quad neighbour's `lent`: the move across the pair and the select are ONE v_cndmask_b32 per
+// dword, its first source fetched from lane ^ 1 (DPP quad_perm:[1,0,3,2]).  Both lanes of the pair must be enabled -- a DPP
+// source in a lane that EXEC has switched off fetches nothing -- so these run on every lane, in front of the narrowed atomic.
+// (s_nop 1: two wait states between a vector instruction's result and a DPP read of it, and behind a vector write of vcc:
+// hazards the compiler does not track into inline assembly.)
+#define CBET_PAIR_DPP " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+__device__ __forceinline__ int pair_pick(unsigned long long owners, int mine, int lent)
+{
+    int r;
+    asm volatile("s_nop 1\n\ts_mov_b64 vcc, %1\n\tv_cndmask_b32_dpp %0, %2, %3, vcc" CBET_PAIR_DPP
+                 : "=&v"(r) : "s"(owners), "v"(lent), "v"(mine) : "vcc");
+    return r;
+}
+// ... a column's node offset and value at once, behind one s_nop
+__device__ __forceinline__ void pair_pick(unsigned long long owners, int mine_n, int lent_n, double mine_v, double lent_v, int &n, double &v)
+{
+    int lo, hi;
+    asm volatile("s_nop 1\n\ts_mov_b64 vcc, %3\n\t"
+                 "v_cndmask_b32_dpp %0, %4, %5, vcc" CBET_PAIR_DPP "\n\t"
+                 "v_cndmask_b32_dpp %1, %6, %7, vcc" CBET_PAIR_DPP "\n\t"
+                 "v_cndmask_b32_dpp %2, %8, %9, vcc" CBET_PAIR_DPP
+                 : "=&v"(n), "=&v"(lo), "=&v"(hi)
+                 : "s"(owners), "v"(lent_n), "v"(mine_n), "v"(__double2loint(lent_v)), "v"(__double2loint(mine_v)),
+                   "v"(__double2hiint(lent_v)), "v"(__double2hiint(mine_v))
+                 : "vcc");
+    v = __hiloint2double(hi, lo);
+}
 
 // The deposit grid as the write-back paths see it.  W32: the grid is smaller than 2^32 bytes (checked on the host,
 // launch_trace_window), so a node's byte offset fits the 32-bit offset register of the scalar-base addressing mode -- one
@@ -197,13 +248,16 @@ __device__ __forceinline__ void write_back_far(const TraceArgs &a, double *tile,
 }
 
 // ... of a window miss: the lanes in hbm_m lie outside both boxes and add their eight values straight to HBM (add8: the
-// kernel's hbm_add8 and nothing else that touches memory) -- eight atomics, counted when some lane misses.
-template <class F>
-__device__ __forceinline__ void miss_add8(unsigned long long hbm_m, WaveCounters &wc, F add8)
+// kernel's hbm_add8 and nothing else that touches memory) -- eight atomics, counted when some lane misses.  Paired (the
+// plain trace's counters): add8 runs on every lane and issues four atomics per round that has an owner, which is what is
+// counted -- a round without owners issues nothing and counts nothing.
+template <class WC, class F>
+__device__ __forceinline__ void miss_add8(unsigned long long hbm_m, WC &wc, F add8)
 {
+    constexpr bool PAIRED = std::is_same<WC, PairedMissCounters>::value;
     if (CBET_RARE(hbm_m != 0ull)) {
-        wc.pend += 8;
-        if (CBET_LANES(hbm_m)) add8();
+        wc.pend += PAIRED ? pair_issued(hbm_m) : 8;
+        if (PAIRED || CBET_LANES(hbm_m)) add8();
     }
 }
 
@@ -667,7 +721,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     unsigned cell = launched ? (unsigned)((s.ci * ny + s.cj) * nz + s.ck) : 0u;
     double fcx = (double)s.ci, fcy = (double)s.cj, fcz = (double)s.ck;   // the cell as the reference's (double)thisx
     int tot_steps = 0;              // wave-uniform: ray-steps of this bundle (a lane's count is added when it ends)
-    WaveCounters wc;
+    typename std::conditional<CBET == 0, PairedMissCounters, WaveCounters>::type wc;   // (the plain trace pairs its window misses)
 
     double *const tileA = s_val, *const tileB = s_val + T::N;
     Origin oA{0, 0, 0}, oB{0, 0, 0};
@@ -809,10 +863,36 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         }
     };
     // eight values to the lane's eight nodes X0..Z1 in HBM (a lane outside both boxes)
-    auto hbm_add8 = [&](const double *w) {
+    // The plain trace sends them paired (see pair_owners) and is called on ALL lanes: per round and column the owners take
+    // their first-visited z node and value, their quad neighbours the owner's other z node and value, and one atomic
+    // carries both -- the picks with every lane enabled, EXEC narrowed for the atomic alone.  The carried node is one of the
+    // owner's eight, so it is as valid as the owner's own; the carrier's own sums and nodes are not touched.  17 vector
+    // instructions per round (32-bit offsets): the z node once, then per column the (x, y) offset, the value's two halves and
+    // one add-and-shift.
+    auto hbm_add8 = [&](const double *w, unsigned long long hbm_m) {
         const int nX0 = __mul24(X0, sXh), nX1 = __mul24(X1, sXh), nY0 = __mul24(Y0, sYh), nY1 = __mul24(Y1, sYh);
-        each_corner([&](auto c) { grid_add(a, edep, c.x(nX0, nX1) + c.y(nY0, nY1) + c.z(Z0, Z1), w[c.index]); });
-        wc.n_atomics += 8;
+        if constexpr (CBET == 0) {
+#pragma unroll
+            for (int round = 0; round < 2; ++round) {
+                const unsigned long long owners = pair_owners(hbm_m, round);
+                if (owners == 0ull) continue;   // scalar branch: nothing issued, nothing counted (pair_issued)
+                const unsigned long long lanes = pair_lanes(owners, round);
+                const int z = pair_pick(owners, Z0, Z1);   // (the owner's Z0, or the neighbour's Z1)
+                each_corner([&](auto c) {
+                    if constexpr ((decltype(c)::index & 2) == 0) {   // a column: corner c and its z partner c ^ 2
+                        const int xy = c.x(nX0, nX1) + c.y(nY0, nY1);
+                        int nxy;
+                        double v;
+                        pair_pick(owners, xy, xy, w[c.index], w[c.index ^ 2], nxy, v);
+                        if (CBET_LANES(lanes)) grid_add(a, edep, nxy + z, v);
+                    }
+                });
+            }
+            if (CBET_LANES(hbm_m)) wc.n_atomics += 8;   // lane-atomics, credited to the miss lane
+        } else {
+            each_corner([&](auto c) { grid_add(a, edep, c.x(nX0, nX1) + c.y(nY0, nY1) + c.z(Z0, Z1), w[c.index]); });
+            wc.n_atomics += 8;
+        }
     };
 
     // ---- deposits, the CBET kernels (ACC = false): every step's deposit goes to LDS during the NEXT step, in the shadow of
@@ -839,7 +919,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
         wgt[7] = zy11 * Fx1;
         if (CBET_LANES(lds_m)) lds_add8(wgt);
         miss_add8(hbm_m, wc, [&]() {
-            hbm_add8(wgt);
+            hbm_add8(wgt, hbm_m);
             ++wc.n_miss;
         });
         if (CBET == 4) {
@@ -892,7 +972,7 @@ __global__ void __launch_bounds__(kWave, (CBET == 4) ? 1 : 4) k_trace_window(con
     // the pending sums of the lanes in lds_m go to their LDS box, those of the lanes in hbm_m straight to HBM
     auto flush_sums = [&](unsigned long long lds_m, unsigned long long hbm_m) {
         if (CBET_LANES(lds_m)) lds_add8(S);
-        miss_add8(hbm_m, wc, [&]() { hbm_add8(S); });
+        miss_add8(hbm_m, wc, [&]() { hbm_add8(S, hbm_m); });
     };
 
     // ---- the rest of a step: wait for the record, absorb, add the deposit to the pending sums, end rays -------------
