@@ -173,6 +173,24 @@ assert PATH_DTYPE.itemsize == C.sizeof(PathSample) == 64
 assert TURN_DTYPE.itemsize == C.sizeof(RayTurn) == 64
 
 
+# ---- backscatter SBS gain spectra (cbet_trace_backscatter) ------------------------
+SBS_MAX_SHIFTS = 16                               # CBET_SBS_MAX_SHIFTS
+SBS_TALLY_COLUMNS = ("uray0", "weighted", "max", "n_rays")   # CBET_SBS_TALLY_*
+
+
+class RaySbs(C.Structure):
+    """cbet_ray_sbs: a ray's largest gain exponent, where in the spectrum it is, and how the ray ended (32 bytes)."""
+    _fields_ = [
+        ("gmax", C.c_double), ("uray0", C.c_double), ("uray_end", C.c_double),
+        ("steps", C.c_int), ("imax", C.c_short), ("status", C.c_short),
+    ]
+
+
+# the same record as a numpy structured dtype: view a downloaded [..., 4] float64 array with .view(SBS_DTYPE)
+SBS_DTYPE = np.dtype([(name, {C.c_double: "<f8", C.c_int: "<i4", C.c_short: "<i2"}[ct]) for name, ct in RaySbs._fields_])
+assert SBS_DTYPE.itemsize == C.sizeof(RaySbs) == 32
+
+
 # ---- perturbed targets (cbet_tabulate_target) ----------------------------------------------------
 TARGET_LMAX = 16
 
@@ -418,14 +436,15 @@ EXPORTS = [
     "cbet_context_set_bandwidth", "cbet_context_bandwidth", "cbet_exchange_matrix_host_banded",
     "cbet_trace_paths",
     "cbet_lpi_work_bytes", "cbet_lpi_summary_init", "cbet_lpi_map", "cbet_lpi_map_host",
+    "cbet_trace_backscatter", "cbet_backscatter_work_bytes", "cbet_backscatter_tally", "cbet_backscatter_host",
 ]
 
 _lib = None
 
 
 def lib(tolerate=()):
-    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning, polarization
-    and bandwidth entries that an OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack;
+    """Loads libcbet_mi355x.so; raises (loudly) if it has not been built.  tolerate: names of the detuning, polarization,
+    bandwidth and backscatter entries that an OLDER build of the library (CBET_LIB_PATH, timing experiments against a parent commit) may lack;
     such a build must then not be asked for shifts, for a polarization mode or for a line spectrum."""
     global _lib
     if _lib is not None:
@@ -548,11 +567,20 @@ def lib(tolerate=()):
                 "cbet_context_set_polarization": [vp, C.c_int], "cbet_context_polarization": [vp, ip],
                 "cbet_exchange_matrix_host_polarized": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int],
                 "cbet_context_set_bandwidth": [vp, vp, vp, C.c_int, vp], "cbet_context_bandwidth": [vp, dp, dp, ip],
-                "cbet_exchange_matrix_host_banded": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int, vp, vp, C.c_int]}
+                "cbet_exchange_matrix_host_banded": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int, vp, vp, C.c_int],
+                # the backscatter spectra: an older build is then only asked for the other passes
+                "cbet_trace_backscatter": [vp, vp, vp, vp, vp, C.c_long, vp, dp, C.c_int, vp, vp, vp, vp, vp, vp,
+                                           C.c_double, C.c_double, C.c_double, C.POINTER(Params), C.POINTER(GainParams), vp, vp],
+                "cbet_backscatter_work_bytes": [C.c_long, C.c_int, C.c_int],
+                "cbet_backscatter_tally": [vp, vp, vp, C.c_long, C.c_int, C.c_int, vp, vp, vp],
+                "cbet_backscatter_host": [vp, vp, vp, C.c_long, C.c_int, vp, vp, vp, vp, C.c_int, dp, C.c_int, vp, vp,
+                                          C.POINTER(Params), C.POINTER(GainParams)]}
     absent = [name for name in optional if name in tolerate and not hasattr(L, name)]
     for name, types in optional.items():
         if name not in absent:
             getattr(L, name).argtypes = types
+    if "cbet_backscatter_work_bytes" not in absent:
+        L.cbet_backscatter_work_bytes.restype = C.c_size_t
     for name in EXPORTS:
         if name not in absent:
             getattr(L, name)  # AttributeError here = the library is older than the header
@@ -1227,6 +1255,71 @@ def trace_paths(ne3d, kappa3d, gain, beams, raynums, nitems, stride, capacity, c
         c.ctypes.data_as(C.POINTER(C.c_double)), _addr(samples), _addr(turns), _addr(bbeam_norm), _addr(beam_norm),
         _addr(pow_r), _addr(phase_r), xconst, yconst, zconst, C.byref(params),
         C.byref(gain_params) if gain_params is not None else None, ctx.handle, _addr(stream)))
+
+
+# ---- backscatter SBS gain spectra ---------------------------------------------------------------
+def sbs_shifts(domega):
+    """The scan of cbet_trace_backscatter as a contiguous float64 array: 1 .. SBS_MAX_SHIFTS finite angular-frequency shifts of
+    the scattered light relative to its beam (rad/s, negative = red), or ValueError.  No library call."""
+    s = np.ascontiguousarray(domega, dtype=np.float64).reshape(-1)
+    if not 1 <= s.size <= SBS_MAX_SHIFTS:
+        raise ValueError("a backscatter scan holds 1 .. %d shifts, got %d" % (SBS_MAX_SHIFTS, s.size))
+    if not np.isfinite(s).all():
+        raise ValueError("a backscatter scan's shifts must be finite")
+    return s
+
+
+def trace_backscatter(ne3d, kappa3d, gain, beams, raynums, nitems, fields, shifts, gamma, rays, bbeam_norm, beam_norm, pow_r,
+                      phase_r, xconst, yconst, zconst, params, gain_params, ctx, stream=None):
+    """cbet_trace_backscatter: the rays (beams[k], raynums[k]) (device int32) traced as cbet_trace_paths traces them, the SBS
+    backscatter gain exponent of every shift (host float64 array) into gamma ([nshift][nitems], device) and one cbet_ray_sbs
+    each into rays ([nitems], device); fields: normalised device fields [4][nbeams][grid]."""
+    s = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+    _check(lib().cbet_trace_backscatter(
+        _addr(ne3d), _addr(kappa3d), _addr(gain), _addr(beams), _addr(raynums), nitems, _addr(fields), _dptr(s), int(s.size),
+        _addr(gamma), _addr(rays), _addr(bbeam_norm), _addr(beam_norm), _addr(pow_r), _addr(phase_r), xconst, yconst, zconst,
+        C.byref(params), C.byref(gain_params) if gain_params is not None else None, ctx.handle, _addr(stream)))
+
+
+def backscatter_work_bytes(nitems, nshift, nbeams):
+    """cbet_backscatter_work_bytes: device bytes of the `work` array of backscatter_tally (0 for bad arguments)."""
+    return int(lib().cbet_backscatter_work_bytes(nitems, nshift, nbeams))
+
+
+def backscatter_tally(gamma, rays, beams, nitems, nshift, nbeams, tally, work, stream=None):
+    """cbet_backscatter_tally: per beam and shift {sum uray0, sum uray0 Gamma, max Gamma, rays} over the launched items,
+    MERGED INTO tally (device float64 [nbeams][nshift][4]); deterministic."""
+    _check(lib().cbet_backscatter_tally(_addr(gamma), _addr(rays), _addr(beams), nitems, nshift, nbeams, _addr(tally), _addr(work),
+                                        _addr(stream)))
+
+
+def backscatter_host(samples, turns, beams, fields, ne3d, shifts, params, gain_params, flow=None, state=None,
+                     polarization="aligned"):
+    """cbet_backscatter_host, the host twin: (gamma float64 [nshift, nitems], rays [nitems] of SBS_DTYPE) from STRIDE-1 path
+    records of the items -- samples [capacity, nitems] of PATH_DTYPE (or float64 [capacity, nitems, 8]), turns [nitems] of
+    TURN_DTYPE (or float64 [nitems, 8]), as trace_paths writes them -- their beams, normalised HOST fields
+    [4, nbeams, nx + 2, ny + 2, nz + 2], ne3d (nx, ny, nz), flow (3, nx, ny, nz) or None = the closed-form ramp, state
+    (2, nx, ny, nz) or None = the scalars, and a polarization mode."""
+    host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
+    fields, ne3d, flow, state = host(fields), host(ne3d), host(flow), host(state)
+    samples, turns = np.ascontiguousarray(samples), np.ascontiguousarray(turns)
+    b = np.ascontiguousarray(beams, dtype=np.int32).reshape(-1)
+    nitems = int(b.size)
+    if turns.nbytes != nitems * 64:
+        raise ValueError("turns holds one 64-byte record per item: %d items, %d bytes" % (nitems, turns.nbytes))
+    capacity = samples.nbytes // (64 * nitems) if nitems else 0
+    if samples.nbytes != capacity * nitems * 64:
+        raise ValueError("samples holds capacity x nitems 64-byte records, got %d bytes for %d items" % (samples.nbytes, nitems))
+    s = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+    gamma = np.zeros((s.size, nitems))
+    rays = np.zeros(nitems, dtype=SBS_DTYPE)
+    one = np.zeros(1)                          # (empty arrays have no address to speak of)
+    _check(lib().cbet_backscatter_host(_addr(samples) if samples.size else None, _addr(turns) if nitems else _addr(one),
+                                       _addr(b) if nitems else None, nitems, capacity, _addr(fields), _addr(ne3d), _addr(flow),
+                                       _addr(state), polarization_mode(polarization), _dptr(s), int(s.size),
+                                       _addr(gamma) if gamma.size else _addr(one), _addr(rays) if nitems else _addr(one),
+                                       C.byref(params), C.byref(gain_params) if gain_params is not None else None))
+    return gamma, rays
 
 
 # ---- mode spectra (cbet_sph_modes; DESIGN.md section 11) ------------------------------------------------------------

@@ -153,6 +153,35 @@ struct PathArgs {
     const cbet_ray_turn *audit_turns_lo, *audit_turns_hi;
 };
 
+// What the backscatter kernel (cbet_backscatter.hip) takes BESIDE TraceArgs and a GainArgs (the gain
+// stage's own block, built by gain_args: grid, plasma constants, fields, ne3d, flow and state tables, pol), as a third by-value
+// kernel argument: the other two keep their members and their offsets.
+struct SbsArgs {
+    const int *beams, *raynums;             // device, nitems each: the rays to trace, as PathArgs'
+    long nitems;
+    int nbeams, nrays;                      // an item is decoded only when 0 <= beam < nbeams and 0 <= raynum < nrays
+    int nshift;                             // 1 .. CBET_SBS_MAX_SHIFTS
+    double qs;                              // sbs_qs (cbet_sbs_model.h): q = qs * displacement
+    double iaw2;                            // GainArgs.iaw squared, once on the host
+    double shifts[CBET_SBS_MAX_SHIFTS];     // delta_m, rad/s; entries past nshift are 0 and never read
+    double *gamma;                          // [nshift][nitems], shift-major
+    cbet_ray_sbs *rays;                     // [nitems]
+    // bounds-audit builds (-DCBET_DEBUG_BOUNDS) only; unused otherwise: the ranges the two arrays' stores are checked against
+    const double *audit_gamma_lo, *audit_gamma_hi;
+    const cbet_ray_sbs *audit_rays_lo, *audit_rays_hi;
+};
+// k_backscatter_tally + k_backscatter_reduce (cbet_backscatter.hip): chunk c of the list is the items [c * sbs_chunk_items,
+// (c + 1) * sbs_chunk_items); both follow from nitems alone.
+constexpr long kSbsChunkMin = 4096, kSbsMaxChunks = 1024;
+inline long sbs_chunk_items(long nitems)
+{
+    const long per = ((nitems + kSbsMaxChunks - 1) / kSbsMaxChunks + kWave - 1) / kWave * kWave;
+    return per > kSbsChunkMin ? per : kSbsChunkMin;
+}
+inline long sbs_chunks(long nitems) { return nitems > 0 ? (nitems + sbs_chunk_items(nitems) - 1) / sbs_chunk_items(nitems) : 0; }
+hipError_t launch_backscatter_tally(const double *gamma, const cbet_ray_sbs *rays, const int *beams, long nitems, int nshift,
+                                    int nbeams, double *tally, double *work, hipStream_t stream);
+
 hipError_t launch_tabulate(const TabulateArgs &a, hipStream_t stream);
 hipError_t launch_step_table(const StepTableArgs &a, hipStream_t stream);
 hipError_t launch_plasma_records(const PlasmaRecordsArgs &a, hipStream_t stream);
@@ -160,7 +189,9 @@ size_t plasma_records_lds(int nprofile);       // dynamic LDS of that launch, by
 hipError_t audit_violations(unsigned long long *out, bool reset, hipStream_t stream);
 // variant: CBET_KERNEL_GLOBAL_ATOMICS, _LDS_COMBINE (cbet_kernels.hip) or _LDS_WINDOW (cbet_trace_window.hip)
 // (path: the recorder's second block, variant kTracePaths only)
-hipError_t launch_trace(const TraceArgs &a, int variant, bool force_idx64, hipStream_t stream, const PathArgs *path = nullptr);
+// (sbs, sbs_gain: the backscatter kernel's second and third block, variant kTraceBackscatter only)
+hipError_t launch_trace(const TraceArgs &a, int variant, bool force_idx64, hipStream_t stream, const PathArgs *path = nullptr,
+                        const SbsArgs *sbs = nullptr, const GainArgs *sbs_gain = nullptr);
 hipError_t launch_trace_window(const TraceArgs &a, bool force_idx64, hipStream_t stream);
 // Exit pass (cbet_trace_exit.hip): launch_trace with variant kTraceExits runs it -- TraceArgs.edep is then the record array
 // as doubles and grid_stride = kExitDoubles * L -- after the bounds-audit set-up every trace gets.
@@ -171,6 +202,10 @@ hipError_t launch_trace_exit(const TraceArgs &a, bool force_idx64, hipStream_t s
 // per 64 items of q, after the same bounds-audit set-up.
 constexpr int kTracePaths = 101;
 hipError_t launch_trace_path(const TraceArgs &a, const PathArgs &q, bool force_idx64, hipStream_t stream);
+// Backscatter gain spectra (cbet_backscatter.hip): launch_trace with variant kTraceBackscatter and both blocks runs it, one
+// wavefront per 64 items of q, after the same bounds-audit set-up.
+constexpr int kTraceBackscatter = 102;
+hipError_t launch_trace_backscatter(const TraceArgs &a, const GainArgs &g, const SbsArgs &q, bool force_idx64, hipStream_t stream);
 hipError_t launch_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, hipStream_t stream);
 hipError_t launch_farfield(const cbet_ray_exit *exits, long n, int ntheta, int nphi, double *hist, hipStream_t stream);
 hipError_t launch_gain_field(const GainArgs &a, hipStream_t stream);

@@ -203,6 +203,13 @@ long lpi_groups(const cbet_params *p, int hx_lo, int hx_hi);
 // k_lpi_map over the block's planes with `groups` workgroups; summary != NULL: the workgroups' partial summaries into
 // work[groups], then k_lpi_reduce merges them into *summary in workgroup order (cbet_lpi.hip)
 hipError_t launch_lpi_map(const LpiArgs &a, cbet_lpi_summary *summary, cbet_lpi_summary *work, long groups, hipStream_t stream);
+// k_trace_backscatter's third block and its host twin's (cbet_backscatter_host.cpp, no HIP call).
+// sbs_check: the refusals both entries share, `who` in front, each naming the first offence; sbs_args: the block, beside a
+// GainArgs of gain_args (whole grid) whose k0, dt, iaw and nbeams it reads.  The twin passes no raynums (nrays 0).
+int sbs_check(const char *who, long nitems, const int *beams, const double *fields, const double *shifts, int nshift,
+              const double *gamma, const cbet_ray_sbs *rays, const cbet_params *p, const cbet_gain_params *g);
+SbsArgs sbs_args(const GainArgs &g, const int *beams, const int *raynums, long nitems, int nrays, const double *shifts, int nshift,
+                 double *gamma, cbet_ray_sbs *rays);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
 // The context's own device table of `doubles` doubles (own_node_table: `components` per node) in *slot, allocated on the first call (not capturable).
@@ -220,6 +227,8 @@ struct CbetHooks {
     double max_exponent = 0.0;
     bool exits = false;     // the exit pass (cbet_trace_exits): `edep` is the record array, no deposit
     const PathArgs *paths = nullptr;   // the path recorder (cbet_trace_paths): its second block; `edep` is the turn records, no deposit
+    const SbsArgs *sbs = nullptr;      // the backscatter spectra (cbet_trace_backscatter): its third block and, in sbs_gain, its second;
+    const GainArgs *sbs_gain = nullptr;   // `edep` is the ray records, no deposit
 };
 int trace_impl(int b, unsigned nindices, const double *ne3d, const double *kappa3d, double *edep, const double *bbeam_norm,
                const double *beam_norm, const double *pow_r, const double *phase_r, double xconst, double yconst,

@@ -472,7 +472,8 @@ hipError_t audit_violations(unsigned long long *out, bool reset, hipStream_t str
 #endif
 }
 
-hipError_t launch_trace(const TraceArgs &a0, int variant, bool force_idx64, hipStream_t stream, const PathArgs *path)
+hipError_t launch_trace(const TraceArgs &a0, int variant, bool force_idx64, hipStream_t stream, const PathArgs *path,
+                        const SbsArgs *sbs, const GainArgs *sbs_gain)
 {
     TraceArgs a = a0;
 #ifdef CBET_DEBUG_BOUNDS
@@ -490,6 +491,8 @@ hipError_t launch_trace(const TraceArgs &a0, int variant, bool force_idx64, hipS
     if (variant == CBET_KERNEL_LDS_WINDOW) return launch_trace_window(a, force_idx64, stream);
     if (variant == kTraceExits) return launch_trace_exit(a, force_idx64, stream);
     if (variant == kTracePaths) return path ? launch_trace_path(a, *path, force_idx64, stream) : hipErrorInvalidValue;
+    if (variant == kTraceBackscatter)
+        return sbs && sbs_gain ? launch_trace_backscatter(a, *sbs_gain, *sbs, force_idx64, stream) : hipErrorInvalidValue;
     const long waves = a.item_count;
     if (waves <= 0) return hipSuccess;
     const dim3 grid((unsigned)waves);

@@ -1,5 +1,5 @@
 // cbet_trace_abi.cpp -- the trace launch of the C ABI (include/cbet_mi355x.h): trace_impl, which every ray-tracing entry
-// goes through, its wrappers (plain, reference-shaped, exit pass, path recorder) and the small kernels that consume a trace's output.
+// goes through, its wrappers (plain, reference-shaped, exit pass, path recorder, backscatter spectra) and the small kernels that consume a trace's output.
 // Citations are into /root/reference/.
 #include <climits>
 #include <cmath>
@@ -32,7 +32,7 @@ int cbet::trace_impl(int b, unsigned nindices, const double *ne3d, const double 
     if (beam_lo < 0 || beam_hi > p->nbeams || beam_hi < beam_lo)
         return fail(CBET_EINVAL, "beam range [%d,%d) outside [0,%d)", beam_lo, beam_hi, p->nbeams);
     // (the recorder's rays are its caller's list, not the context's)
-    if (beam_hi == beam_lo || (ctx->nlive == 0 && !hooks.paths)) return CBET_OK;
+    if (beam_hi == beam_lo || (ctx->nlive == 0 && !hooks.paths && !hooks.sbs)) return CBET_OK;
 
     int variant = p->kernel_variant;
     if (variant == CBET_KERNEL_DEFAULT) variant = CBET_KERNEL_LDS_WINDOW;
@@ -98,8 +98,8 @@ int cbet::trace_impl(int b, unsigned nindices, const double *ne3d, const double 
         if (int rc = step_records(ctx, p, ne3d, kappa3d, xconst, yconst, zconst, stream, false)) return rc;
         a.steprec = ctx->steprec;
     }
-    CBET_HIP(launch_trace(a, hooks.paths ? kTracePaths : hooks.exits ? kTraceExits : variant, p->force_wide_index != 0,
-                          (hipStream_t)stream, hooks.paths));
+    CBET_HIP(launch_trace(a, hooks.sbs ? kTraceBackscatter : hooks.paths ? kTracePaths : hooks.exits ? kTraceExits : variant,
+                          p->force_wide_index != 0, (hipStream_t)stream, hooks.paths, hooks.sbs, hooks.sbs_gain));
     return CBET_OK;
 }
 
@@ -223,6 +223,54 @@ int cbet_trace_paths(const double *ne3d, const double *kappa3d, const double *ga
     h.gain = gain; h.max_exponent = g ? g->max_exponent : 0.0; h.paths = &path;
     return trace_impl(0, (unsigned)ctx->d.nindices, ne3d, kappa3d, reinterpret_cast<double *>(turns), bbeam_norm, beam_norm,
                       pow_r, phase_r, xconst, yconst, zconst, &q, ctx, stream, h);
+}
+
+// ---- backscatter SBS gain spectra ------------------------------------------------
+int cbet_trace_backscatter(const double *ne3d, const double *kappa3d, const double *gain, const int *beams, const int *raynums,
+                           long nitems, const double *fields, const double *shifts, int nshift, double *gamma,
+                           cbet_ray_sbs *rays, const double *bbeam_norm, const double *beam_norm, const double *pow_r,
+                           const double *phase_r, double xconst, double yconst, double zconst, const cbet_params *p,
+                           const cbet_gain_params *g, cbet_context *ctx, void *stream)
+{
+    // the argument checks: before the context and before any HIP call; the twin's own (cbet_backscatter_host.cpp)
+    if (int rc = sbs_check("cbet_trace_backscatter", nitems, beams, fields, shifts, nshift, gamma, rays, p, g)) return rc;
+    if (nitems > 0 && !raynums) return fail(CBET_EINVAL, "cbet_trace_backscatter: NULL raynums with nitems = %ld", nitems);
+    if (int rc = no_deposit_checks("cbet_trace_backscatter: ", "backscatter pass", gain, p, g)) return rc;
+    if (int rc = entry_checks(ctx, p)) return rc;
+    if (nitems == 0) return CBET_OK;
+    double cs = 0, gc = 0;
+    if (int rc = cbet_gain_constants(p, g, nullptr, &cs, &gc)) return rc;
+    // as cbet_trace_paths: the beam range, the shard split and the beam-resolved arrays' range do not apply
+    cbet_params q = no_deposit_params(p);
+    q.beam_lo = 0; q.beam_hi = q.nbeams;
+    q.shard_index = 0; q.shard_count = 1;
+    q.grid_beam0 = 0; q.grid_beams = 0;
+    // the context's flow table, state table and polarization mode; its limit, shifts and spectrum are not applied (linear gain,
+    // the seed's shift is the scan variable)
+    GainOptions o;
+    o.flow = ctx->flow; o.state = ctx->state; o.pol = ctx->pol;
+    const GainArgs ga = gain_args(p, ctx->d, g, cs, gc, fields, ne3d ? ne3d : ctx->ne3d, o, 0, p->nx + 2, false);
+    const SbsArgs sbs = sbs_args(ga, beams, raynums, nitems, ctx->d.nrays, shifts, nshift, gamma, rays);
+    CbetHooks h;
+    h.gain = gain; h.max_exponent = g->max_exponent; h.sbs = &sbs; h.sbs_gain = &ga;
+    return trace_impl(0, (unsigned)ctx->d.nindices, ne3d, kappa3d, reinterpret_cast<double *>(rays), bbeam_norm, beam_norm,
+                      pow_r, phase_r, xconst, yconst, zconst, &q, ctx, stream, h);
+}
+
+int cbet_backscatter_tally(const double *gamma, const cbet_ray_sbs *rays, const int *beams, long nitems, int nshift, int nbeams,
+                           double *tally, void *work, void *stream)
+{
+    if (nshift < 1 || nshift > CBET_SBS_MAX_SHIFTS)
+        return fail(CBET_EINVAL, "cbet_backscatter_tally: nshift = %d outside 1 .. %d", nshift, CBET_SBS_MAX_SHIFTS);
+    if (nbeams < 1 || nbeams > CBET_MAX_CBET_BEAMS)
+        return fail(CBET_EINVAL, "cbet_backscatter_tally: nbeams = %d outside 1 .. %d", nbeams, CBET_MAX_CBET_BEAMS);
+    if (nitems < 0) return fail(CBET_EINVAL, "cbet_backscatter_tally: nitems = %ld, must be >= 0", nitems);
+    if (!tally) return fail(CBET_EINVAL, "cbet_backscatter_tally: NULL tally");
+    if (nitems == 0) return CBET_OK;
+    if (!gamma || !rays || !beams) return fail(CBET_EINVAL, "cbet_backscatter_tally: NULL gamma / rays / beams with nitems = %ld", nitems);
+    if (!work) return fail(CBET_EINVAL, "cbet_backscatter_tally: work is NULL (cbet_backscatter_work_bytes)");
+    CBET_HIP(launch_backscatter_tally(gamma, rays, beams, nitems, nshift, nbeams, tally, (double *)work, (hipStream_t)stream));
+    return CBET_OK;
 }
 
 int cbet_exit_tally(const cbet_ray_exit *exits, long L, int nbeams, double *tally, void *stream)

@@ -5,6 +5,8 @@ the two-plasmon-decay threshold parameter (RayTracer.lpi_map, api.lpi_map_host) 
 quantities derived from those: the absolute-SRS threshold, which needs a 4/3 power the kernel does not evaluate, the band
 means over the angular bins of the quarter-critical surface, and fractions and means from the summary's counts and sums.
 Unpinned, like the map: the reference has no such diagnostics.  Works on numpy arrays and torch tensors alike.
+Behind them, what is derived from the backscatter SBS gain spectra of section 24: per-beam spectra and a linear-gain proxy of
+the reflectivity.
 """
 import numpy as np
 
@@ -55,3 +57,44 @@ def summarize(summary):
         out["max_eta_%s" % x] = summary["max_eta_%s" % x]
     out["argmax_cw"], out["max_present"] = summary["argmax_cw"], summary["max_present"]
     return out
+
+
+# ---- backscatter SBS gain spectra (include/cbet_mi355x.h cbet_trace_backscatter) ----------------
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def backscatter_spectrum(tally):
+    """Per-beam spectra from RayTracer.backscatter_tally's table [nbeams, nshift, 4] (columns api.SBS_TALLY_COLUMNS): a dict of
+    numpy arrays -- "mean" [nbeams, nshift], the launch-energy-weighted mean of the gain exponent, sum uray0 Gamma / sum uray0;
+    "max" [nbeams, nshift], the largest exponent of any of the beam's rays; "rays" [nbeams], the rays counted; "peak"
+    [nbeams], the shift index of the largest mean.  A beam without rays has zeros (no 0 / 0).  Against the scan's shifts
+    (the result's "shifts") the rows are the beams' backscatter gain spectra."""
+    t = _host(tally).astype(np.float64)
+    if t.ndim != 3 or t.shape[2] != len(api.SBS_TALLY_COLUMNS):
+        raise ValueError("tally must be [nbeams, nshift, %d], got shape %s" % (len(api.SBS_TALLY_COLUMNS), t.shape))
+    has = t[:, :, 3] > 0
+    mean = np.where(has, t[:, :, 1] / np.where(has, t[:, :, 0], 1.0), 0.0)
+    return {"mean": mean, "max": np.where(has, t[:, :, 2], 0.0), "rays": t[:, 0, 3].astype(np.int64), "peak": np.argmax(mean, axis=1)}
+
+
+def linear_reflectivity(gamma, rays, seed):
+    """A LINEAR-GAIN PROXY of the backscattered fraction: sum uray0 min(1, seed exp(max_m Gamma)) / sum uray0 over the launched
+    rays of a RayTracer.backscatter_gain result (gamma [nshift, nitems]; rays [nitems, 4] float64 or [nitems] of
+    api.SBS_DTYPE), for a seed level `seed` (the noise source relative to the pump, e.g. 1e-9).  Every ray amplifies the seed
+    by its own largest exponent of the scan, capped at the pump's launch energy; no pump depletion, no absorption of the
+    scattered light, no competition between rays or shifts -- a ranking of designs, not a prediction.  0.0 without rays."""
+    g = _host(gamma).astype(np.float64)
+    r = np.ascontiguousarray(_host(rays))
+    if r.dtype != api.SBS_DTYPE:
+        r = r.astype(np.float64, copy=False).reshape(-1, 4).view(api.SBS_DTYPE)[:, 0]
+    r = r.reshape(-1)
+    if g.ndim != 2 or g.shape[1] != r.size:
+        raise ValueError("gamma must be [nshift, %d], got shape %s" % (r.size, g.shape))
+    live = (r["status"] & api.RAY_LAUNCHED) != 0
+    total = float(r["uray0"][live].sum())
+    if not live.any() or total == 0.0:
+        return 0.0
+    with np.errstate(over="ignore"):
+        amp = np.minimum(1.0, seed * np.exp(g[:, live].max(axis=0)))
+    return float((r["uray0"][live] * amp).sum() / total)

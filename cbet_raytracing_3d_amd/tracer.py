@@ -750,6 +750,98 @@ class RayTracer:
                         self._stream())
         return samples, turns
 
+    # ---- backscatter SBS gain spectra (include/cbet_mi355x.h cbet_trace_backscatter) ----------
+    def backscatter_gain(self, fields, gain_params, dlambda_angstrom=None, domega=None, beams=None, raynums=None, gain=None,
+                         ne3d=None, out=None):
+        """Stimulated Brillouin BACKSCATTER as a linear gain post-processor, on torch's current stream: for every ray of the
+        list and every frequency shift of the scattered light the convective gain exponent Gamma = sum over the ray's steps
+        of g(shift; ne, cs, u, k) I ds, with g the gain stage's own detuned pair gain for the pair (backscattered seed, the
+        ray's light), q = 2 k_ray.  Unpinned: no reference counterpart.
+        fields: normalised fields [4, nbeams, ...] as gain_field leaves them (only the intensities are read; not changed).
+        gain_params: the damping, Mach ramp and plasma state of the gain stage.  The scan is ONE of dlambda_angstrom
+        (wavelength shifts of the scattered light in Angstrom, > 0 = red; set_detuning's conversion) or domega (rad/s,
+        negative = red), 1 .. api.SBS_MAX_SHIFTS values.  beams, raynums: the rays, as trace_paths takes them (default:
+        ray_items(), every live ray of every beam); ids that name no live ray are idle items, all zeros.  gain: a gain grid
+        [nbeams, ...] -- the rays' energies (uray_end) then include CBET, the spectrum does not depend on it.  ne3d: a
+        caller's node table instead of the context's, for the trace and the model.
+        The flow (set_flow), the gain state (set_gain_state) and the polarization mode (set_polarization, "smoothed" halves
+        the gain) are read as gain_field reads them -- a "mesh" or "target" flow or state needs tabulate() first; the limit of
+        set_saturation, the colours of set_detuning and the spectrum of set_bandwidth are NOT applied (a linear gain, the
+        seed's shift is the scan variable).  Not modelled: pump depletion, shared-wave SBS, sidescatter, absorption of the
+        scattered light.  The node tables must be filled (tabulate()).
+        Returns {"gamma": float64 [nshift, nitems] (shift-major), "rays": float64 [nitems, 4] (cbet_ray_sbs: gmax, uray0,
+        uray_end, then steps / imax / status -- .cpu().numpy().view(api.SBS_DTYPE)[..., 0] names them), "shifts": domega as a
+        numpy array, "beams": the items' beams on the device}; out: (gamma, rays) tensors to write into."""
+        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+        if gain_params is None:
+            raise ValueError("backscatter_gain needs gain_params (the model's damping, Mach ramp and plasma state)")
+        if (dlambda_angstrom is None) == (domega is None):
+            raise ValueError("backscatter_gain takes ONE of dlambda_angstrom or domega")
+        if dlambda_angstrom is not None:
+            dl = np.asarray(dlambda_angstrom, dtype=np.float64)
+            if not np.isfinite(dl).all():
+                raise ValueError("backscatter_gain: dlambda_angstrom holds a NaN or infinite value")
+            domega = api.wavelength_shift_to_domega(self.params, dl)
+        shifts = api.sbs_shifts(domega)
+        if not self._tables_filled:
+            raise ValueError("backscatter_gain: the context's node tables are not filled: tabulate() first")
+        if self._state_is_mesh() and self.ctx.state() is None:
+            raise ValueError("backscatter_gain: set_gain_state(\"mesh\") needs tabulate() first")
+        if isinstance(self.flow, str):
+            ramp = lambda g: (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)  # noqa: E731
+            if self._flow_is("target") and ramp(gain_params) != ramp(self._flow_gp):
+                raise ValueError("backscatter_gain: the flow table was tabulated from another Mach ramp or sound speed than "
+                                 "gain_params carries (set_flow(\"target\", gain_params), then tabulate())")
+            if self.ctx.flow() is None:
+                raise ValueError("backscatter_gain: set_flow(\"%s\") needs tabulate() first" % self.flow)
+        if (beams is None) != (raynums is None):
+            raise ValueError("backscatter_gain takes beams and raynums together, or neither (ray_items())")
+        if beams is None:
+            beams, raynums = self.ray_items()
+        beams, raynums = api.path_items(beams, raynums)
+        nitems, nshift = int(beams.size), int(shifts.size)
+        if gain is not None:
+            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
+        if ne3d is not None:
+            _require(ne3d, (self.params.nx, self.params.ny, self.params.nz), "ne3d")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        if out is None:
+            gamma, rays = torch.zeros((nshift, nitems), **f64), torch.zeros((nitems, 4), **f64)
+        else:
+            gamma, rays = out
+            _require(gamma, (nshift, nitems), "gamma")
+            _require(rays, (nitems, 4), "rays")
+        d_beams = torch.from_numpy(beams).to(self.device)
+        result = {"gamma": gamma, "rays": rays, "shifts": shifts, "beams": d_beams}
+        if nitems == 0:                # (empty tensors have no address to hand over)
+            return result
+        d_raynums = torch.from_numpy(raynums).to(self.device)
+        api.trace_backscatter(ne3d, None, gain, d_beams, d_raynums, nitems, fields, shifts, gamma, rays, *self._tail(),
+                              self.params, gain_params, self.ctx, self._stream())
+        return result
+
+    def backscatter_tally(self, result, beams=None, out=None):
+        """Per beam and shift over the launched rays of a backscatter_gain result: float64 [nbeams, nshift, 4], columns
+        api.SBS_TALLY_COLUMNS (sum of uray0, sum of uray0 Gamma, max of Gamma, number of rays).  beams: the items' beams
+        (default: the result's own).  out: a table to MERGE into -- results of parts of a list compose; default a zeroed new
+        one.  Deterministic: fixed-order sums, no atomics.  lpi.backscatter_spectrum turns the table into spectra."""
+        gamma, rays = result["gamma"], result["rays"]
+        nshift, nitems = gamma.shape
+        nb = self.params.nbeams
+        d_beams = result["beams"] if beams is None else torch.from_numpy(api.path_items(beams, beams)[0]).to(self.device)
+        if int(d_beams.numel()) != nitems:
+            raise ValueError("beams holds %d items, the result %d" % (int(d_beams.numel()), nitems))
+        _require(rays, (nitems, 4), "rays")
+        if out is None:
+            out = torch.zeros((nb, nshift, 4), dtype=torch.float64, device=self.device)
+        else:
+            _require(out, (nb, nshift, 4), "out")
+        if nitems == 0:
+            return out
+        work = torch.empty(max(api.backscatter_work_bytes(nitems, nshift, nb) // 8, 1), dtype=torch.float64, device=self.device)
+        api.backscatter_tally(gamma, rays, d_beams, nitems, nshift, nb, out, work, self._stream())
+        return out
+
     # ---- mode spectra (include/cbet_mi355x.h cbet_sph_modes; DESIGN.md section 11) ----------------------------------
     def sph_modes(self, grid, r_edges=None, lmax=16, center=(0.0, 0.0, 0.0), geometry=False):
         """Real spherical-harmonic coefficients of a deposit grid on shells, on torch's current stream.  grid: one grid

@@ -1139,6 +1139,92 @@ int cbet_trace_paths(const double *ne3d, const double *kappa3d, const double *ga
                      const double *phase_r, double xconst, double yconst, double zconst, const cbet_params *p,
                      const cbet_gain_params *g, cbet_context *ctx, void *stream);
 
+/* ---- backscatter SBS gain spectra along rays --------------------------------------------- */
+/*
+ * Stimulated Brillouin backscatter as a ray-based LINEAR gain post-processor: for every ray of a list and every frequency
+ * shift delta_m of the scattered light (rad/s relative to the ray's own beam, negative = red) the convective gain exponent
+ *     Gamma_m = sum over the ray's steps of (g_m * I) * ds
+ * No reference counterpart: parity UNPINNED, like the whole CBET stage.  The statements are csrc/cbet_sbs_model.h's, one IEEE
+ * fp64 operation per written operator, for the kernel and the host twin alike, so the two agree bit for bit.
+ *
+ * A ray is traced exactly as cbet_trace_paths traces it (items, idle items, gain hook, absorbing mode: that contract).  With
+ * p_t the position after step t (p_0 the launch point) and (ci, cj, ck)_t the ray's node after it, step t = 1 .. steps adds
+ *     d       p_t - p_(t-1), per component;   ds = sqrt((d.x d.x + d.y d.y) + d.z d.z);   a step with ds == 0.0 adds nothing
+ *     h       ((ci + 1) (ny + 2) + (cj + 1)) (nz + 2) + (ck + 1): the deposit-grid cell whose plasma is that node's
+ *     c, pref the gain stage's cell state and prefactor of cell h, from the context's flow table / state table if it has them
+ *             (the closed-form Mach ramp and cbet_gain_constants' scalars otherwise); pref = 0 at and above critical density
+ *     q       the ion-acoustic wave of the pair (backscattered seed, the ray's own light): q = 2 k_ray = qs d,
+ *             qs = ((2.0 * k0) / c) / dt computed once on the host;   kiaw = sqrt((q.x q.x + q.y q.y) + q.z q.z)
+ *     g_m     pref P(((0.0 - q . u) + (0.0 - delta_m)) / (kiaw cs + 1e-10)), the gain stage's detuned pair gain;
+ *             times 0.5 under CBET_POL_SMOOTHED (the smoothing factor at cos theta = -1)
+ *     I       fields[0][beam][h], the beam's own normalised intensity in that cell
+ * and Gamma_m starts from +0.0 and takes its terms in step order.  The context's saturation limit, per-beam detuning and
+ * line spectrum are NOT applied: the seed's shift is the scan variable and the gain is linear.  Left out as well: pump
+ * depletion, shared-wave (multi-beam) SBS, sidescatter, absorption of the scattered light, and where along the ray the gain
+ * accrues (re-trace chosen rays with cbet_trace_paths).
+ *
+ * gamma is SHIFT-major: gamma[m * nitems + k] is Gamma_m of item k, nshift * nitems doubles; rays[k] is item k's record.
+ * Every entry of both is written; an idle item gets zeros.
+ */
+#define CBET_SBS_MAX_SHIFTS 16
+typedef struct cbet_ray_sbs {
+    double gmax;          /* the largest Gamma_m of the ray                                                      */
+    double uray0;         /* launch energy                                                                       */
+    double uray_end;      /* energy the ray still carries when it ends                                           */
+    int steps;            /* as cbet_ray_exit.steps                                                              */
+    short imax;           /* the shift index of gmax, 0 .. nshift - 1: the FIRST maximum wins                    */
+    short status;         /* as cbet_ray_exit.status (CBET_RAY_* bits); 0 = idle item                            */
+} cbet_ray_sbs;           /* 32 bytes: a wavefront's 64 records are 2 KB of whole lines; three doubles and four ints
+                             would be 40, so the two small members are 16-bit and there is no padding member */
+#ifdef __cplusplus
+static_assert(sizeof(cbet_ray_sbs) == 32, "cbet_ray_sbs is 32 bytes");
+#else
+_Static_assert(sizeof(cbet_ray_sbs) == 32, "cbet_ray_sbs is 32 bytes");
+#endif
+/* Columns of a cbet_backscatter_tally entry. */
+#define CBET_SBS_TALLY_COLUMNS 4
+#define CBET_SBS_TALLY_URAY0 0        /* sum of uray0 over the beam's launched items                   */
+#define CBET_SBS_TALLY_WEIGHTED 1     /* sum of uray0 * Gamma_m                                        */
+#define CBET_SBS_TALLY_MAX 2          /* max of Gamma_m (0 while the entry counts no ray)              */
+#define CBET_SBS_TALLY_N_RAYS 3       /* launched items                                                */
+/*
+ * cbet_trace_backscatter: cbet_trace_paths' arguments without the recorder's own, plus fields (device, NORMALISED whole-grid
+ * [4][nbeams][(nx+2)(ny+2)(nz+2)] as a gain update leaves them, never written; only the intensities are read), shifts
+ * (nshift HOST doubles, captured at the call), gamma and rays (device).  g is REQUIRED: it carries the ion-acoustic damping,
+ * the Mach ramp and the plasma state of the model (and max_exponent for a gain grid).  ne3d NULL = the context's table, for
+ * the trace and the model alike.  The context's counters are not touched.  nitems == 0 succeeds and launches nothing.
+ * CBET_EINVAL, naming the first offence, judged before the context and before any device call: nshift outside
+ * 1 .. CBET_SBS_MAX_SHIFTS; NULL shifts or a shift that is not finite; NULL fields; NULL gain params; nitems < 0 or more
+ * items than one launch takes or nshift * nitems beyond a 64-bit byte count; NULL rays or gamma; NULL beams / raynums with
+ * nitems > 0; non-absorbing mode; nbeams > CBET_MAX_CBET_BEAMS.  Enqueued on `stream`, no synchronisation.
+ *
+ * cbet_backscatter_tally: per beam and shift, over the LAUNCHED items of that beam, {sum uray0, sum uray0 * Gamma_m,
+ * max Gamma_m, number of rays} MERGED INTO tally (device double [nbeams][nshift][4]: sums and counts add, the maximum is
+ * taken over entries that count a ray), so calls on parts of a list compose; zero it before the first.  beams: the item
+ * list's device array.  No atomics: fixed-order partial entries go to `work` (cbet_backscatter_work_bytes(nitems, nshift,
+ * nbeams) bytes; 0 for bad arguments) and a second kernel merges them in a fixed order that follows from nitems alone, so
+ * two calls give the same bytes.  Items whose beam is outside [0, nbeams) or whose record is not LAUNCHED count nowhere.
+ *
+ * cbet_backscatter_host: the host twin, HOST pointers, no HIP call.  samples ([capacity][nitems], sample-major) and turns
+ * ([nitems]) are STRIDE-1 records of the same items as cbet_trace_paths writes them (or built from the CPU oracle's ray
+ * paths): positions, nodes, uray and nsamples are read, and steps / status are copied into the records.  An item whose turn
+ * record has status 0 is idle.  flow ([3][nodes]) and state ([2][nodes]) are node tables or NULL, pol a CBET_POL_* mode.
+ * CBET_EINVAL beside the refusals above: an item with nsamples > capacity or nsamples < 1, a launched item's beam outside
+ * [0, nbeams) or a sample's node outside the grid.
+ */
+int cbet_trace_backscatter(const double *ne3d, const double *kappa3d, const double *gain, const int *beams, const int *raynums,
+                           long nitems, const double *fields, const double *shifts, int nshift, double *gamma,
+                           cbet_ray_sbs *rays, const double *bbeam_norm, const double *beam_norm, const double *pow_r,
+                           const double *phase_r, double xconst, double yconst, double zconst, const cbet_params *p,
+                           const cbet_gain_params *g, cbet_context *ctx, void *stream);
+size_t cbet_backscatter_work_bytes(long nitems, int nshift, int nbeams);
+int cbet_backscatter_tally(const double *gamma, const cbet_ray_sbs *rays, const int *beams, long nitems, int nshift, int nbeams,
+                           double *tally, void *work, void *stream);
+int cbet_backscatter_host(const cbet_path_sample *samples, const cbet_ray_turn *turns, const int *beams, long nitems,
+                          int capacity, const double *fields, const double *ne3d, const double *flow, const double *state,
+                          int pol, const double *shifts, int nshift, double *gamma, cbet_ray_sbs *rays, const cbet_params *p,
+                          const cbet_gain_params *g);
+
 /* ---- mode spectra of the deposit ---------------------------------------------------------- */
 /*
  * How uniformly the energy is deposited around a centre: the real spherical-harmonic coefficients of each grid on
