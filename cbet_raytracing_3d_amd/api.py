@@ -119,8 +119,14 @@ class RayExit(C.Structure):
     ]
 
 
+def record_dtype(cls):
+    """The numpy structured dtype of a ctypes record of doubles, ints and shorts: the same names in the same order."""
+    kinds = {C.c_double: "<f8", C.c_int: "<i4", C.c_short: "<i2"}
+    return np.dtype([(name, kinds[ct]) for name, ct in cls._fields_])
+
+
 # the same record as a numpy structured dtype: view a downloaded [..., 10] float64 array with .view(EXIT_DTYPE)
-EXIT_DTYPE = np.dtype([(name, "<f8" if ct is C.c_double else "<i4") for name, ct in RayExit._fields_])
+EXIT_DTYPE = record_dtype(RayExit)
 assert EXIT_DTYPE.itemsize == C.sizeof(RayExit) == 80
 
 
@@ -167,8 +173,8 @@ class RayTurn(C.Structure):
 
 
 # the same records as numpy structured dtypes: view a downloaded [..., 8] float64 array with .view(PATH_DTYPE) / .view(TURN_DTYPE)
-PATH_DTYPE = np.dtype([(name, "<f8" if ct is C.c_double else "<i4") for name, ct in PathSample._fields_])
-TURN_DTYPE = np.dtype([(name, "<f8" if ct is C.c_double else "<i4") for name, ct in RayTurn._fields_])
+PATH_DTYPE = record_dtype(PathSample)
+TURN_DTYPE = record_dtype(RayTurn)
 assert PATH_DTYPE.itemsize == C.sizeof(PathSample) == 64
 assert TURN_DTYPE.itemsize == C.sizeof(RayTurn) == 64
 
@@ -187,7 +193,7 @@ class RaySbs(C.Structure):
 
 
 # the same record as a numpy structured dtype: view a downloaded [..., 4] float64 array with .view(SBS_DTYPE)
-SBS_DTYPE = np.dtype([(name, {C.c_double: "<f8", C.c_int: "<i4", C.c_short: "<i2"}[ct]) for name, ct in RaySbs._fields_])
+SBS_DTYPE = record_dtype(RaySbs)
 assert SBS_DTYPE.itemsize == C.sizeof(RaySbs) == 32
 
 
@@ -268,17 +274,14 @@ class Mesh(C.Structure):
     def __init__(self, r, theta, phi, ne, te, velocity=None, center=(0.0, 0.0, 0.0), ti=None, zbar=None):
         super().__init__()
 
-        def host(a):
-            return a.detach().cpu().numpy() if hasattr(a, "detach") else a
-
         def axis(a, alone):
-            return np.ascontiguousarray([alone] if a is None else host(a), dtype=np.float64).reshape(-1).copy()
+            return _host([alone] if a is None else a).reshape(-1).copy()
 
         r, theta, phi = axis(r, 0.0), axis(theta, 0.5 * np.pi), axis(phi, 0.0)
         shape = (r.size, theta.size, phi.size)
 
         def field(a, what):
-            a = np.ascontiguousarray(host(a), dtype=np.float64)
+            a = _host(a)
             if a.ndim < 3 and a.shape == shape[:a.ndim] and a.size == int(np.prod(shape)):
                 a = a.reshape(shape)
             if a.shape != shape:
@@ -342,10 +345,7 @@ class MeshCells:
         self._h = C.c_void_p()
 
         def edges(a):
-            if a is None:
-                return None
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
-            return np.ascontiguousarray(a, dtype=np.float64).reshape(-1).copy()
+            return None if a is None else _host(a).reshape(-1).copy()
 
         self.r_edges, self.theta_edges, self.phi_edges = edges(r_edges), edges(theta_edges), edges(phi_edges)
         self.center = tuple(float(v) for v in center)
@@ -410,34 +410,137 @@ class MeshCells:
             pass
 
 
-# Every symbol include/cbet_mi355x.h declares; tests check the library exports all of them.
-EXPORTS = [
-    "cbet_last_error", "cbet_version", "cbet_params_default", "cbet_derive",
-    "cbet_live_ray_list", "cbet_omega60_beam_norm", "cbet_host_power_table", "cbet_host_beam_trig", "cbet_read_profile",
-    "cbet_safeGPUAlloc", "cbet_moveToAndFromGPU", "cbet_gpuFree",
-    "cbet_context_create", "cbet_context_destroy", "cbet_context_counters", "cbet_context_tables", "cbet_context_set_launch_list",
-    "cbet_launch_ray_XYZ", "cbet_tabulate_plasma", "cbet_trace_nodes", "cbet_prepare_step_records", "cbet_ray_tracing",
-    "cbet_write_text", "cbet_edep_average", "cbet_edep_average_device", "cbet_node_coordinates", "cbet_write_npy",
-    "cbet_debug_bounds_violations",
-    "cbet_gain_params_default", "cbet_gain_constants", "cbet_trace_cbet", "cbet_gain_field",
-    "cbet_cbet_workspace_bytes", "cbet_cbet_solve", "cbet_gain_field_slab", "cbet_gain_field_packed",
-    "cbet_cbet_slab_workspace_bytes", "cbet_cbet_slab_workspace_bytes_parts", "cbet_pack_segments", "cbet_unpack_segments",
-    "cbet_context_list_length", "cbet_cbet_workspace_gain", "cbet_trace_exits", "cbet_exit_tally", "cbet_farfield",
-    "cbet_sph_modes_device", "cbet_sph_modes", "cbet_prepare_plasma", "cbet_context_step_records",
-    "cbet_tabulate_target", "cbet_target_tables",
-    "cbet_tabulate_flow", "cbet_context_set_flow", "cbet_context_flow", "cbet_flow_table",
-    "cbet_tabulate_mesh", "cbet_tabulate_mesh_flow", "cbet_mesh_check", "cbet_mesh_tables", "cbet_mesh_flow_table",
-    "cbet_tabulate_mesh_state", "cbet_context_set_state", "cbet_context_state", "cbet_mesh_state_table",
-    "cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit",
-    "cbet_context_set_saturation", "cbet_context_saturation", "cbet_pair_amplitude",
-    "cbet_exchange_matrix_work_bytes", "cbet_exchange_matrix", "cbet_exchange_matrix_host",
+# ---- the C ABI, stated once ----------------------------------------------------------------------
+# The ctypes mirror of every struct of include/cbet_mi355x.h, by its C name; tests/test_abi_host.py asks gcc for sizeof and
+# every offsetof of each.
+STRUCTS = {
+    "cbet_params": Params, "cbet_derived": Derived, "cbet_counters": Counters, "cbet_gain_params": GainParams,
+    "cbet_cbet_report": CbetReport, "cbet_ray_exit": RayExit, "cbet_path_sample": PathSample, "cbet_ray_turn": RayTurn,
+    "cbet_ray_sbs": RaySbs, "cbet_lpi_summary": LpiSummary, "cbet_target": Target, "cbet_mesh": Mesh,
+    "cbet_mesh_ions": MeshIons, "cbet_mesh_cells": MeshCellsStruct,
+}
+
+
+def _signatures():
+    """name -> (return type, argument types) of every function the header declares, in the header's words: the one place
+    that says how Python calls the library.  lib() binds restype and argtypes from it; tests/test_abi_host.py compares it
+    with the header prototype by prototype.  A pointer the callers hand over as an address (_addr: a tensor's, an array's,
+    an int) is a c_void_p whatever it points to in the header; a struct passed with byref() is a POINTER to its mirror."""
+    i32, u32, i64, i64l, usz, f64, cstr = C.c_int, C.c_uint, C.c_long, C.c_longlong, C.c_size_t, C.c_double, C.c_char_p
+    vp, dp, ip, lp, vpp, ullp = (C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_long),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong))
+    P, G, T, M, MI = (C.POINTER(S) for S in (Params, GainParams, Target, Mesh, MeshIons))
+    consts = [f64, f64, f64]                                        # xconst, yconst, zconst
+    sph = [vp, i32, i64, P, dp, dp, i32, i32, vp, vp, vp, vp]       # cbet_sph_modes and its device flavour
+    deposit = [vp, vp, i32, i64, P, i32, i32, vp, vp, vp, vp]       # cbet_mesh_deposit and its device flavour
+    slab = [vp] * 5 + [i32, i32, P, G, vp, vp]                      # the gain update and the exchange matrix over planes
+    segments = [vp, i64, i32, i32, vp, i64, vp, vp]
+    xhost = [vp] * 4 + [i32, i32, P, G, vp, vp, f64]                # cbet_exchange_matrix_host; its successors append
+    return {
+        "cbet_last_error": (cstr, []),
+        "cbet_version": (cstr, []),
+        "cbet_params_default": (i32, [P, i32]),
+        "cbet_derive": (i32, [P, C.POINTER(Derived)]),
+        "cbet_live_ray_list": (i32, [P, ip, i64, lp]),
+        "cbet_omega60_beam_norm": (dp, []),
+        "cbet_host_power_table": (i32, [dp, dp]),
+        "cbet_host_beam_trig": (i32, [dp, i32, dp]),
+        "cbet_read_profile": (i32, [cstr, i32, dp, dp]),
+        "cbet_safeGPUAlloc": (i32, [vpp, usz, i32]),
+        "cbet_moveToAndFromGPU": (i32, [vp, vp, usz, i32]),
+        "cbet_gpuFree": (i32, [vp, i32]),
+        "cbet_context_create": (i32, [vpp, P, i32]),
+        "cbet_context_destroy": (i32, [vp]),
+        "cbet_context_counters": (i32, [vp, vp, C.POINTER(Counters), i32]),
+        "cbet_context_tables": (i32, [vp, vpp, vpp]),
+        "cbet_context_set_launch_list": (i32, [vp, ip, i64]),
+        "cbet_launch_ray_XYZ": (i32, [i32, u32] + [vp] * 8 + consts + [P, vp, vp]),
+        "cbet_tabulate_plasma": (i32, [vp, P, vp, vp, vp, vp]),
+        "cbet_trace_nodes": (i32, [i32, u32] + [vp] * 7 + consts + [P, vp, vp]),
+        "cbet_prepare_step_records": (i32, [vp, P, vp, vp] + consts + [vp]),
+        "cbet_ray_tracing": (i32, [dp, dp, dp, dp, P, dp, ip, i32, dp, C.POINTER(Counters)]),
+        "cbet_write_text": (i64l, [dp, i32, i32, i32, cstr]),
+        "cbet_edep_average": (i32, [dp, dp, i32, i32, i32]),
+        "cbet_edep_average_device": (i32, [vp, vp, i32, i32, i32, vp]),
+        "cbet_node_coordinates": (i32, [P, dp, dp, dp]),
+        "cbet_write_npy": (i64l, [dp, i32, lp, cstr]),
+        "cbet_debug_bounds_violations": (i32, [ullp, i32, vp]),
+        "cbet_gain_params_default": (i32, [G]),
+        "cbet_gain_constants": (i32, [P, G, dp, dp, dp]),
+        "cbet_trace_cbet": (i32, [i32, u32, vp, vp, vp, i32] + [vp] * 6 + consts + [P, G, vp, vp]),
+        "cbet_gain_field": (i32, [vp] * 5 + [P, G, vp, vp]),
+        "cbet_cbet_workspace_bytes": (usz, [P]),
+        "cbet_cbet_solve": (i32, [vp] * 8 + [P, G, vp, vp, vp, C.POINTER(CbetReport)]),
+        "cbet_gain_field_slab": (i32, slab),
+        "cbet_gain_field_packed": (i32, slab),
+        "cbet_cbet_slab_workspace_bytes": (usz, [P, i32, i32]),
+        "cbet_cbet_slab_workspace_bytes_parts": (usz, [P, i32, i32, usz]),
+        "cbet_pack_segments": (i32, segments),
+        "cbet_unpack_segments": (i32, segments),
+        "cbet_context_list_length": (i32, [vp, lp]),
+        "cbet_cbet_workspace_gain": (vp, [P, vp]),
+        "cbet_trace_exits": (i32, [vp] * 8 + consts + [P, G, vp, vp]),
+        "cbet_exit_tally": (i32, [vp, i64, i32, vp, vp]),
+        "cbet_farfield": (i32, [vp, i64, i32, i32, vp, vp]),
+        "cbet_sph_modes_device": (i32, sph),
+        "cbet_sph_modes": (i32, sph),
+        "cbet_prepare_plasma": (i32, [vp, P, vp, vp, vp] + consts + [vp]),
+        "cbet_context_step_records": (i32, [vp, vpp, ullp]),
+        "cbet_tabulate_target": (i32, [vp, P, vp, vp, vp, T, vp]),
+        "cbet_target_tables": (i32, [P, dp, dp, dp, T, dp, dp]),
+        "cbet_tabulate_flow": (i32, [vp, P, G, T, vp]),
+        "cbet_context_set_flow": (i32, [vp, vp]),
+        "cbet_context_flow": (i32, [vp, vpp]),
+        "cbet_flow_table": (i32, [P, G, T, dp]),
+        "cbet_tabulate_mesh": (i32, [vp, P, M, vp]),
+        "cbet_tabulate_mesh_flow": (i32, [vp, P, M, vp]),
+        "cbet_mesh_check": (i32, [M]),
+        "cbet_mesh_tables": (i32, [P, M, dp, dp]),
+        "cbet_mesh_flow_table": (i32, [P, M, dp]),
+        "cbet_tabulate_mesh_state": (i32, [vp, P, G, M, MI, vp]),
+        "cbet_context_set_state": (i32, [vp, vp]),
+        "cbet_context_state": (i32, [vp, vpp]),
+        "cbet_mesh_state_table": (i32, [P, G, M, MI, dp]),
+        "cbet_mesh_cells_create": (i32, [vpp, C.POINTER(MeshCellsStruct), i32, i32]),
+        "cbet_mesh_cells_destroy": (None, [vp]),
+        "cbet_mesh_deposit_device": (i32, deposit),
+        "cbet_mesh_deposit": (i32, deposit),
+        "cbet_context_set_saturation": (i32, [vp, f64]),
+        "cbet_context_saturation": (i32, [vp, dp]),
+        "cbet_pair_amplitude": (i32, [vp, vp, vp, i32, i32, P, G, vp, vp]),
+        "cbet_exchange_matrix_work_bytes": (usz, [P]),
+        "cbet_exchange_matrix": (i32, slab),
+        "cbet_exchange_matrix_host": (i32, xhost),
+        "cbet_context_set_detuning": (i32, [vp, vp, i32, vp]),
+        "cbet_context_detuning": (i32, [vp, dp, ip]),
+        "cbet_exchange_matrix_host_shifted": (i32, xhost + [vp]),
+        "cbet_context_set_polarization": (i32, [vp, i32]),
+        "cbet_context_polarization": (i32, [vp, ip]),
+        "cbet_exchange_matrix_host_polarized": (i32, xhost + [vp, i32]),
+        "cbet_context_set_bandwidth": (i32, [vp, vp, vp, i32, vp]),
+        "cbet_context_bandwidth": (i32, [vp, dp, dp, ip]),
+        "cbet_exchange_matrix_host_banded": (i32, xhost + [vp, i32, vp, vp, i32]),
+        "cbet_trace_paths": (i32, [vp] * 5 + [i64, i32, i32, dp] + [vp] * 6 + consts + [P, G, vp, vp]),
+        "cbet_lpi_work_bytes": (usz, [P]),
+        "cbet_lpi_summary_init": (i32, [C.POINTER(LpiSummary)]),
+        "cbet_lpi_map": (i32, [vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, i32, i32, P, vp, vp]),
+        "cbet_lpi_map_host": (i32, [vp, vp, vp, f64, f64, f64, i32, vp, C.POINTER(LpiSummary), i32, i32, P]),
+        "cbet_trace_backscatter": (i32, [vp] * 5 + [i64, vp, dp, i32] + [vp] * 6 + consts + [P, G, vp, vp]),
+        "cbet_backscatter_work_bytes": (usz, [i64, i32, i32]),
+        "cbet_backscatter_tally": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp]),
+        "cbet_backscatter_host": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, dp, i32, vp, vp, P, G]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)      # every symbol include/cbet_mi355x.h declares
+# lib(tolerate=...): the detuning, polarization, bandwidth and backscatter entries, which an older build may lack
+OPTIONAL = frozenset((
     "cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted",
     "cbet_context_set_polarization", "cbet_context_polarization", "cbet_exchange_matrix_host_polarized",
     "cbet_context_set_bandwidth", "cbet_context_bandwidth", "cbet_exchange_matrix_host_banded",
-    "cbet_trace_paths",
-    "cbet_lpi_work_bytes", "cbet_lpi_summary_init", "cbet_lpi_map", "cbet_lpi_map_host",
-    "cbet_trace_backscatter", "cbet_backscatter_work_bytes", "cbet_backscatter_tally", "cbet_backscatter_host",
-]
+    "cbet_trace_backscatter", "cbet_backscatter_work_bytes", "cbet_backscatter_tally", "cbet_backscatter_host"))
+
 
 _lib = None
 
@@ -461,129 +564,11 @@ def lib(tolerate=()):
             "%s is missing: build it with `python -m cbet_raytracing_3d_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
-    L.cbet_last_error.restype = C.c_char_p
-    L.cbet_version.restype = C.c_char_p
-    L.cbet_params_default.argtypes = [C.POINTER(Params), C.c_int]
-    L.cbet_derive.argtypes = [C.POINTER(Params), C.POINTER(Derived)]
-    L.cbet_live_ray_list.argtypes = [C.POINTER(Params), ip, C.c_long, C.POINTER(C.c_long)]
-    L.cbet_omega60_beam_norm.restype = dp
-    L.cbet_host_power_table.argtypes = [dp, dp]
-    L.cbet_host_beam_trig.argtypes = [dp, C.c_int, dp]
-    L.cbet_read_profile.argtypes = [C.c_char_p, C.c_int, dp, dp]
-    L.cbet_safeGPUAlloc.argtypes = [C.POINTER(vp), C.c_size_t, C.c_int]
-    L.cbet_moveToAndFromGPU.argtypes = [vp, vp, C.c_size_t, C.c_int]
-    L.cbet_gpuFree.argtypes = [vp, C.c_int]
-    L.cbet_context_create.argtypes = [C.POINTER(vp), C.POINTER(Params), C.c_int]
-    L.cbet_context_destroy.argtypes = [vp]
-    L.cbet_context_counters.argtypes = [vp, vp, C.POINTER(Counters), C.c_int]
-    L.cbet_context_set_launch_list.argtypes = [vp, ip, C.c_long]
-    L.cbet_context_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.cbet_launch_ray_XYZ.argtypes = [C.c_int, C.c_uint, vp, vp, vp, vp, vp, vp, vp, vp,
-                                      C.c_double, C.c_double, C.c_double, C.POINTER(Params), vp, vp]
-    L.cbet_tabulate_plasma.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp]
-    L.cbet_prepare_step_records.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_double, C.c_double, C.c_double, vp]
-    L.cbet_prepare_plasma.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.c_double, C.c_double, C.c_double, vp]
-    L.cbet_context_step_records.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_ulonglong)]
-    L.cbet_trace_nodes.argtypes = [C.c_int, C.c_uint, vp, vp, vp, vp, vp, vp, vp,
-                                   C.c_double, C.c_double, C.c_double, C.POINTER(Params), vp, vp]
-    L.cbet_ray_tracing.argtypes = [dp, dp, dp, dp, C.POINTER(Params), dp, ip, C.c_int, dp,
-                                   C.POINTER(Counters)]
-    L.cbet_debug_bounds_violations.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, vp]
-    L.cbet_write_text.argtypes = [dp, C.c_int, C.c_int, C.c_int, C.c_char_p]
-    L.cbet_write_text.restype = C.c_longlong
-    L.cbet_edep_average.argtypes = [dp, dp, C.c_int, C.c_int, C.c_int]
-    L.cbet_edep_average_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
-    L.cbet_node_coordinates.argtypes = [C.POINTER(Params), dp, dp, dp]
-    L.cbet_write_npy.argtypes = [dp, C.c_int, C.POINTER(C.c_long), C.c_char_p]
-    L.cbet_write_npy.restype = C.c_longlong
-    L.cbet_gain_params_default.argtypes = [C.POINTER(GainParams)]
-    L.cbet_gain_constants.argtypes = [C.POINTER(Params), C.POINTER(GainParams), dp, dp, dp]
-    L.cbet_trace_cbet.argtypes = [C.c_int, C.c_uint, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp,
-                                  C.c_double, C.c_double, C.c_double, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_gain_field.argtypes = [vp, vp, vp, vp, vp, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_gain_field_slab.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_gain_field_packed.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_pack_segments.argtypes = [vp, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, vp]
-    L.cbet_unpack_segments.argtypes = [vp, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, vp]
-    L.cbet_cbet_slab_workspace_bytes.argtypes = [C.POINTER(Params), C.c_int, C.c_int]
-    L.cbet_cbet_slab_workspace_bytes.restype = C.c_size_t
-    L.cbet_cbet_slab_workspace_bytes_parts.argtypes = [C.POINTER(Params), C.c_int, C.c_int, C.c_size_t]
-    L.cbet_cbet_slab_workspace_bytes_parts.restype = C.c_size_t
-    L.cbet_cbet_workspace_bytes.argtypes = [C.POINTER(Params)]
-    L.cbet_cbet_workspace_bytes.restype = C.c_size_t
-    L.cbet_cbet_solve.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Params), C.POINTER(GainParams), vp, vp, vp,
-                                  C.POINTER(CbetReport)]
-    L.cbet_context_list_length.argtypes = [vp, C.POINTER(C.c_long)]
-    L.cbet_cbet_workspace_gain.argtypes = [C.POINTER(Params), vp]
-    L.cbet_cbet_workspace_gain.restype = vp
-    L.cbet_trace_exits.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
-                                   C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_trace_paths.argtypes = [vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, dp, vp, vp, vp, vp, vp, vp,
-                                   C.c_double, C.c_double, C.c_double, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_exit_tally.argtypes = [vp, C.c_long, C.c_int, vp, vp]
-    L.cbet_farfield.argtypes = [vp, C.c_long, C.c_int, C.c_int, vp, vp]
-    sph = [vp, C.c_int, C.c_long, C.POINTER(Params), dp, dp, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.cbet_sph_modes_device.argtypes = sph
-    L.cbet_sph_modes.argtypes = sph
-    L.cbet_tabulate_target.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.POINTER(Target), vp]
-    L.cbet_target_tables.argtypes = [C.POINTER(Params), dp, dp, dp, C.POINTER(Target), dp, dp]
-    L.cbet_tabulate_flow.argtypes = [vp, C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Target), vp]
-    L.cbet_context_set_flow.argtypes = [vp, vp]
-    L.cbet_context_flow.argtypes = [vp, C.POINTER(vp)]
-    L.cbet_flow_table.argtypes = [C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Target), dp]
-    L.cbet_tabulate_mesh.argtypes = [vp, C.POINTER(Params), C.POINTER(Mesh), vp]
-    L.cbet_tabulate_mesh_flow.argtypes = [vp, C.POINTER(Params), C.POINTER(Mesh), vp]
-    L.cbet_mesh_check.argtypes = [C.POINTER(Mesh)]
-    L.cbet_mesh_tables.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp, dp]
-    L.cbet_mesh_flow_table.argtypes = [C.POINTER(Params), C.POINTER(Mesh), dp]
-    L.cbet_tabulate_mesh_state.argtypes = [vp, C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Mesh), C.POINTER(MeshIons), vp]
-    L.cbet_context_set_state.argtypes = [vp, vp]
-    L.cbet_context_state.argtypes = [vp, C.POINTER(vp)]
-    L.cbet_mesh_state_table.argtypes = [C.POINTER(Params), C.POINTER(GainParams), C.POINTER(Mesh), C.POINTER(MeshIons), dp]
-    L.cbet_mesh_cells_create.argtypes = [C.POINTER(vp), C.POINTER(MeshCellsStruct), C.c_int, C.c_int]
-    L.cbet_mesh_cells_destroy.argtypes = [vp]
-    L.cbet_mesh_cells_destroy.restype = None
-    deposit = [vp, vp, C.c_int, C.c_long, C.POINTER(Params), C.c_int, C.c_int, vp, vp, vp, vp]
-    L.cbet_mesh_deposit_device.argtypes = deposit
-    L.cbet_mesh_deposit.argtypes = deposit
-    L.cbet_context_set_saturation.argtypes = [vp, C.c_double]
-    L.cbet_context_saturation.argtypes = [vp, dp]
-    L.cbet_pair_amplitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_exchange_matrix_work_bytes.argtypes = [C.POINTER(Params)]
-    L.cbet_exchange_matrix_work_bytes.restype = C.c_size_t
-    L.cbet_exchange_matrix.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp]
-    L.cbet_exchange_matrix_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(GainParams), vp, vp,
-                                            C.c_double]
-    L.cbet_lpi_work_bytes.argtypes = [C.POINTER(Params)]
-    L.cbet_lpi_work_bytes.restype = C.c_size_t
-    L.cbet_lpi_summary_init.argtypes = [C.POINTER(LpiSummary)]
-    L.cbet_lpi_map.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.c_int, C.c_int,
-                               C.POINTER(Params), vp, vp]
-    L.cbet_lpi_map_host.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, C.POINTER(LpiSummary), C.c_int,
-                                    C.c_int, C.POINTER(Params)]
-    optional = {"cbet_context_set_detuning": [vp, vp, C.c_int, vp], "cbet_context_detuning": [vp, dp, ip],
-                "cbet_exchange_matrix_host_shifted": L.cbet_exchange_matrix_host.argtypes + [vp],
-                "cbet_context_set_polarization": [vp, C.c_int], "cbet_context_polarization": [vp, ip],
-                "cbet_exchange_matrix_host_polarized": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int],
-                "cbet_context_set_bandwidth": [vp, vp, vp, C.c_int, vp], "cbet_context_bandwidth": [vp, dp, dp, ip],
-                "cbet_exchange_matrix_host_banded": L.cbet_exchange_matrix_host.argtypes + [vp, C.c_int, vp, vp, C.c_int],
-                # the backscatter spectra: an older build is then only asked for the other passes
-                "cbet_trace_backscatter": [vp, vp, vp, vp, vp, C.c_long, vp, dp, C.c_int, vp, vp, vp, vp, vp, vp,
-                                           C.c_double, C.c_double, C.c_double, C.POINTER(Params), C.POINTER(GainParams), vp, vp],
-                "cbet_backscatter_work_bytes": [C.c_long, C.c_int, C.c_int],
-                "cbet_backscatter_tally": [vp, vp, vp, C.c_long, C.c_int, C.c_int, vp, vp, vp],
-                "cbet_backscatter_host": [vp, vp, vp, C.c_long, C.c_int, vp, vp, vp, vp, C.c_int, dp, C.c_int, vp, vp,
-                                          C.POINTER(Params), C.POINTER(GainParams)]}
-    absent = [name for name in optional if name in tolerate and not hasattr(L, name)]
-    for name, types in optional.items():
-        if name not in absent:
-            getattr(L, name).argtypes = types
-    if "cbet_backscatter_work_bytes" not in absent:
-        L.cbet_backscatter_work_bytes.restype = C.c_size_t
-    for name in EXPORTS:
-        if name not in absent:
-            getattr(L, name)  # AttributeError here = the library is older than the header
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if name in OPTIONAL and name in tolerate and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)       # AttributeError here = the library is older than the header
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -595,6 +580,23 @@ def _check(rc):
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _host(x):
+    """`x` -- a numpy array, a sequence or a torch tensor -- as a contiguous float64 numpy array; None stays None."""
+    if x is None:
+        return None
+    return np.ascontiguousarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64)
+
+
+def _handle(ctx):
+    """A Context's handle for an entry whose context is optional (None -> NULL)."""
+    return None if ctx is None else ctx.handle
+
+
+def _byref(struct):
+    """byref() for an entry whose struct is optional (None -> NULL)."""
+    return None if struct is None else C.byref(struct)
 
 
 def _addr(x):
@@ -873,7 +875,7 @@ def launch_ray_XYZ(b, nindices, te_data_g, r_data_g, ne_data_g, edep, bbeam_norm
     _check(lib().cbet_launch_ray_XYZ(
         b, nindices, _addr(te_data_g), _addr(r_data_g), _addr(ne_data_g), _addr(edep),
         _addr(bbeam_norm), _addr(beam_norm), _addr(pow_r), _addr(phase_r), xconst, yconst, zconst,
-        C.byref(params), ctx.handle if ctx is not None else None, _addr(stream)))
+        C.byref(params), _handle(ctx), _addr(stream)))
 
 
 def tabulate_plasma(ctx, params, te_data_g, r_data_g, ne_data_g, stream=None):
@@ -914,14 +916,14 @@ def tabulate_flow(ctx, params, gain_params, target=None, stream=None):
     """cbet_tabulate_flow: the gain kernels' flow on `target` (api.Target; None = the sphere about the origin) into the
     context's own flow table, which the context's gain updates then read.  The first call on a context allocates."""
     _check(lib().cbet_tabulate_flow(ctx.handle, C.byref(params), C.byref(gain_params),
-                                    None if target is None else C.byref(target), _addr(stream)))
+                                    _byref(target), _addr(stream)))
     ctx._flow_ref = None
 
 
 def flow_table(params, gain_params, target=None):
     """cbet_flow_table, the host twin: numpy (3, nx, ny, nz) -- ux, uy, uz at the nodes."""
     out = np.empty((3, params.nx, params.ny, params.nz))
-    _check(lib().cbet_flow_table(C.byref(params), C.byref(gain_params), None if target is None else C.byref(target),
+    _check(lib().cbet_flow_table(C.byref(params), C.byref(gain_params), _byref(target),
                                  _dptr(out)))
     return out
 
@@ -1045,7 +1047,7 @@ def pair_amplitude(fields, ne3d, amp, hx_lo, hx_hi, params, gain_params, ctx, st
     """cbet_pair_amplitude: into `amp` (whole-grid [hsize] doubles), for the planes [hx_lo, hx_hi), the largest ion-acoustic
     amplitude any beam pair's unclamped gain corresponds to, from the NORMALISED `fields` a gain update leaves."""
     _check(lib().cbet_pair_amplitude(_addr(fields), _addr(ne3d), _addr(amp), hx_lo, hx_hi, C.byref(params), C.byref(gain_params),
-                                     ctx.handle if ctx is not None else None, _addr(stream)))
+                                     _handle(ctx), _addr(stream)))
 
 
 def exchange_matrix_work_bytes(params):
@@ -1059,7 +1061,7 @@ def exchange_matrix(fields, ne3d, out, gross, work, hx_lo, hx_hi, params, gain_p
     triangle negated, diagonal zero) and of `gross` (the sum of magnitudes, symmetric; may be None).  The context's flow and
     state tables and its saturation limit are honoured."""
     _check(lib().cbet_exchange_matrix(_addr(fields), _addr(ne3d), _addr(out), _addr(gross), _addr(work), hx_lo, hx_hi,
-                                      C.byref(params), C.byref(gain_params), ctx.handle if ctx is not None else None, _addr(stream)))
+                                      C.byref(params), C.byref(gain_params), _handle(ctx), _addr(stream)))
 
 
 def lpi_work_bytes(params):
@@ -1085,7 +1087,7 @@ def lpi_map(fields, ne3d, te3d, te_ev, frac_lo, frac_hi, cone_bins, lpi, summary
     of the NORMALISED device `fields`; summary: a device cbet_lpi_summary to merge into (with `work`), or None."""
     _check(lib().cbet_lpi_map(_addr(fields), _addr(ne3d), _addr(te3d), te_ev, frac_lo, frac_hi, cone_bins, _addr(lpi),
                               _addr(summary), _addr(work), hx_lo, hx_hi, C.byref(params),
-                              ctx.handle if ctx is not None else None, _addr(stream)))
+                              _handle(ctx), _addr(stream)))
 
 
 def lpi_map_host(fields, ne3d, params, te=1000.0, band=(0.20, 0.25), cone_bins=8, hx_lo=0, hx_hi=None, out=None, summary=None):
@@ -1093,9 +1095,8 @@ def lpi_map_host(fields, ne3d, params, te=1000.0, band=(0.20, 0.25), cone_bins=8
     [4, nbeams, nx + 2, ny + 2, nz + 2] over the planes [hx_lo, hx_hi).  ne3d (nx, ny, nz); te: a float (eV, uniform) or an
     (nx, ny, nz) array; out: a stack to write the planes of (default: a zeroed new one); summary: an LpiSummary to merge
     into (default: a new one)."""
-    host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
-    fields, ne3d = host(fields), host(ne3d)
-    te3d, te_ev = (None, float(te)) if np.isscalar(te) else (host(te), 0.0)
+    fields, ne3d = _host(fields), _host(ne3d)
+    te3d, te_ev = (None, float(te)) if np.isscalar(te) else (_host(te), 0.0)
     grid = (params.nx + 2, params.ny + 2, params.nz + 2)
     out = np.zeros((LPI_NQ,) + grid) if out is None else out
     summary = lpi_summary_new() if summary is None else summary
@@ -1167,8 +1168,7 @@ def exchange_matrix_host(fields, ne3d, params, gain_params, flow=None, state=Non
     shifts in rad/s or None; polarization "aligned" or "smoothed"; lines (offsets in rad/s, weights) of the spectrum every beam
     carries, or None (cbet_exchange_matrix_host_banded).  out / gross: arrays to ADD into (default: new zeroed ones)."""
     nb = params.nbeams
-    host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
-    fields, ne3d, flow, state, shift = host(fields), host(ne3d), host(flow), host(state), host(shift)
+    fields, ne3d, flow, state, shift = (_host(a) for a in (fields, ne3d, flow, state, shift))
     if shift is not None and shift.shape != (nb,):
         raise ValueError("shift holds one value per beam: shape (%d,), got %r" % (nb, shift.shape))
     out = np.zeros((nb, nb)) if out is None else out
@@ -1192,7 +1192,7 @@ def cbet_solve(te_data_g, r_data_g, ne_data_g, edep, bbeam_norm, beam_norm, pow_
     _check(lib().cbet_cbet_solve(_addr(te_data_g), _addr(r_data_g), _addr(ne_data_g), _addr(edep),
                                  _addr(bbeam_norm), _addr(beam_norm), _addr(pow_r), _addr(phase_r),
                                  C.byref(params), C.byref(gain_params), _addr(workspace),
-                                 ctx.handle if ctx is not None else None, _addr(stream), C.byref(rep)))
+                                 _handle(ctx), _addr(stream), C.byref(rep)))
     return rep
 
 
@@ -1210,7 +1210,7 @@ def trace_exits(ne3d, kappa3d, gain, exits, bbeam_norm, beam_norm, pow_r, phase_
     """cbet_trace_exits: one cbet_ray_exit record per ray into `exits` ([grid beams][L] records, device)."""
     _check(lib().cbet_trace_exits(
         _addr(ne3d), _addr(kappa3d), _addr(gain), _addr(exits), _addr(bbeam_norm), _addr(beam_norm), _addr(pow_r),
-        _addr(phase_r), xconst, yconst, zconst, C.byref(params), C.byref(gain_params) if gain_params is not None else None,
+        _addr(phase_r), xconst, yconst, zconst, C.byref(params), _byref(gain_params),
         ctx.handle, _addr(stream)))
 
 
@@ -1254,7 +1254,7 @@ def trace_paths(ne3d, kappa3d, gain, beams, raynums, nitems, stride, capacity, c
         _addr(ne3d), _addr(kappa3d), _addr(gain), _addr(beams), _addr(raynums), nitems, stride, capacity,
         c.ctypes.data_as(C.POINTER(C.c_double)), _addr(samples), _addr(turns), _addr(bbeam_norm), _addr(beam_norm),
         _addr(pow_r), _addr(phase_r), xconst, yconst, zconst, C.byref(params),
-        C.byref(gain_params) if gain_params is not None else None, ctx.handle, _addr(stream)))
+        _byref(gain_params), ctx.handle, _addr(stream)))
 
 
 # ---- backscatter SBS gain spectra ---------------------------------------------------------------
@@ -1278,7 +1278,7 @@ def trace_backscatter(ne3d, kappa3d, gain, beams, raynums, nitems, fields, shift
     _check(lib().cbet_trace_backscatter(
         _addr(ne3d), _addr(kappa3d), _addr(gain), _addr(beams), _addr(raynums), nitems, _addr(fields), _dptr(s), int(s.size),
         _addr(gamma), _addr(rays), _addr(bbeam_norm), _addr(beam_norm), _addr(pow_r), _addr(phase_r), xconst, yconst, zconst,
-        C.byref(params), C.byref(gain_params) if gain_params is not None else None, ctx.handle, _addr(stream)))
+        C.byref(params), _byref(gain_params), ctx.handle, _addr(stream)))
 
 
 def backscatter_work_bytes(nitems, nshift, nbeams):
@@ -1300,8 +1300,7 @@ def backscatter_host(samples, turns, beams, fields, ne3d, shifts, params, gain_p
     TURN_DTYPE (or float64 [nitems, 8]), as trace_paths writes them -- their beams, normalised HOST fields
     [4, nbeams, nx + 2, ny + 2, nz + 2], ne3d (nx, ny, nz), flow (3, nx, ny, nz) or None = the closed-form ramp, state
     (2, nx, ny, nz) or None = the scalars, and a polarization mode."""
-    host = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
-    fields, ne3d, flow, state = host(fields), host(ne3d), host(flow), host(state)
+    fields, ne3d, flow, state = (_host(a) for a in (fields, ne3d, flow, state))
     samples, turns = np.ascontiguousarray(samples), np.ascontiguousarray(turns)
     b = np.ascontiguousarray(beams, dtype=np.int32).reshape(-1)
     nitems = int(b.size)
@@ -1318,8 +1317,27 @@ def backscatter_host(samples, turns, beams, fields, ne3d, shifts, params, gain_p
                                        _addr(b) if nitems else None, nitems, capacity, _addr(fields), _addr(ne3d), _addr(flow),
                                        _addr(state), polarization_mode(polarization), _dptr(s), int(s.size),
                                        _addr(gamma) if gamma.size else _addr(one), _addr(rays) if nitems else _addr(one),
-                                       C.byref(params), C.byref(gain_params) if gain_params is not None else None))
+                                       C.byref(params), _byref(gain_params)))
     return gamma, rays
+
+
+# ---- deposit grids as cbet_sph_modes and cbet_mesh_deposit take them ------------------------------------------------
+def grid_layout(shape, params):
+    """One grid, a padded grid or a stack: what the shape of a deposit array says, as (ngrids, grid_stride, params with
+    edep_zpitch set, stacked).  shape: (nx+2, ny+2, row) -- one grid -- or (G, nx+2, ny+2, row) -- a stack of G, `stacked`
+    then True -- with row = nz + 2, or longer: padded rows, edep_zpitch = row (0 for dense rows); None: no array (geometry
+    mode, counts alone), one grid.  grid_stride is one grid's doubles, (nx+2)(ny+2) row; the library reads it only with
+    ngrids > 1.  Any other shape is a ValueError."""
+    p = params.copy(edep_zpitch=0)
+    if shape is None:
+        return 1, 0, p, False
+    shape = tuple(int(n) for n in shape)
+    if len(shape) not in (3, 4) or shape[-3:-1] != (p.nx + 2, p.ny + 2) or shape[-1] < p.nz + 2:
+        raise ValueError("a deposit grid is (nx+2, ny+2, >= nz+2) = (%d, %d, >= %d), or a [G, ...] stack of them, got %s"
+                         % (p.nx + 2, p.ny + 2, p.nz + 2, shape))
+    if shape[-1] > p.nz + 2:
+        p.edep_zpitch = shape[-1]
+    return (shape[0] if len(shape) == 4 else 1), shape[-3] * shape[-2] * shape[-1], p, len(shape) == 4
 
 
 # ---- mode spectra (cbet_sph_modes; DESIGN.md section 11) ------------------------------------------------------------
@@ -1343,17 +1361,8 @@ def sph_modes_host(edep, params, center, r_edges, lmax):
     or None (geometry mode); a row longer than nz + 2 is a padded row (cbet_params.edep_zpitch).
     Returns numpy (coeffs [G][nshell][(lmax+1)^2], shell_energy [G][nshell], shell_nodes int64 [nshell])."""
     c, e = _sph_geometry(center, r_edges)
-    p = params.copy(edep_zpitch=0)
-    if edep is None:
-        a, ngrids, stride = None, 1, 0
-    else:
-        a = np.ascontiguousarray(edep, dtype=np.float64)
-        grid = a.shape[-3:]
-        if grid[:2] != (p.nx + 2, p.ny + 2) or grid[2] < p.nz + 2:
-            raise ValueError("edep grids must be (nx+2, ny+2, >= nz+2), got %s" % (grid,))
-        if grid[2] > p.nz + 2:
-            p.edep_zpitch = grid[2]
-        ngrids, stride = (a.shape[0] if a.ndim == 4 else 1), int(np.prod(grid))
+    a = _host(edep)
+    ngrids, stride, p, _ = grid_layout(None if a is None else a.shape, params)
     nshell, ncoef = e.size - 1, (lmax + 1) ** 2
     coeffs = np.zeros((ngrids, max(nshell, 0), ncoef))
     energy = np.zeros((ngrids, max(nshell, 0)))
@@ -1376,17 +1385,8 @@ def mesh_deposit_host(cells, edep, params, subsamples=2):
     """cbet_mesh_deposit, the host twin, on host arrays: edep as sph_modes_host takes it -- a float64 numpy grid
     (nx+2, ny+2, row), a stack (G, nx+2, ny+2, row), or None (counts alone).  Returns numpy (cell_energy [G][nr][ntheta][nphi],
     outside [G], cell_samples int64 [nr][ntheta][nphi])."""
-    p = params.copy(edep_zpitch=0)
-    if edep is None:
-        a, ngrids, stride = None, 1, 0
-    else:
-        a = np.ascontiguousarray(edep, dtype=np.float64)
-        grid = a.shape[-3:]
-        if a.ndim not in (3, 4) or grid[:2] != (p.nx + 2, p.ny + 2) or grid[2] < p.nz + 2:
-            raise ValueError("edep grids must be (nx+2, ny+2, >= nz+2), got %s" % (a.shape,))
-        if grid[2] > p.nz + 2:
-            p.edep_zpitch = grid[2]
-        ngrids, stride = (a.shape[0] if a.ndim == 4 else 1), int(np.prod(grid))
+    a = _host(edep)
+    ngrids, stride, p, _ = grid_layout(None if a is None else a.shape, params)
     energy = np.zeros((ngrids,) + cells.shape)
     outside = np.zeros(ngrids)
     samples = np.zeros(cells.shape, dtype=np.int64)

@@ -30,6 +30,28 @@ def _require(t, shape, what):
         raise ValueError("%s must be a contiguous float64 tensor of shape %s" % (what, tuple(shape)))
 
 
+def shifts_to_domega(params, what, dlambda_angstrom, domega, required):
+    """Wavelength shifts or frequency shifts, as frequency shifts: ONE of dlambda_angstrom (shifts of the nominal wavelength
+    of `params` in Angstrom, > 0 = red; converted by api.wavelength_shift_to_domega) or domega (rad/s, handed back as it is).
+    Both given is a ValueError in the name of `what`, and so is a NaN or infinite wavelength shift; neither given is one if
+    `required`, and None (= off) otherwise.  No device call."""
+    if dlambda_angstrom is not None and domega is not None:
+        raise ValueError("%s takes dlambda_angstrom or domega, not both" % what)
+    if dlambda_angstrom is None:
+        if domega is None and required:
+            raise ValueError("%s takes ONE of dlambda_angstrom or domega" % what)
+        return domega
+    dl = np.asarray(dlambda_angstrom, dtype=np.float64)
+    if not np.isfinite(dl).all():
+        raise ValueError("%s: dlambda_angstrom holds a NaN or infinite value" % what)
+    return api.wavelength_shift_to_domega(params, dl)
+
+
+def _ramp(g):
+    """What a "target" flow table is tabulated from: the Mach ramp and the sound speed's inputs of gain parameters."""
+    return (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)
+
+
 class RayTracer:
     """One device's share of a ray-tracing pass.
 
@@ -92,6 +114,56 @@ class RayTracer:
         """The arguments every trace entry point of the C ABI takes between its output array and its params, in the
         header's order: bbeam_norm, beam_norm, pow_r, phase_r, xconst, yconst, zconst."""
         return (self.d_bbeam_norm if host_trig else None, self.d_beam_norm, self.d_pow_r, self.d_phase_r) + self._grad_consts()
+
+    def _launch_params(self, beam_lo, beam_hi, shard_index, shard_count, **more):
+        """A launch's copy of the parameters: its beams [beam_lo, beam_hi) (beam_hi None = all that follow) and its shard."""
+        return self.params.copy(beam_lo=beam_lo, beam_hi=self.params.nbeams if beam_hi is None else beam_hi,
+                                shard_index=shard_index, shard_count=shard_count, **more)
+
+    def _x_hi(self, x_hi):
+        """The end of a slab of planes [x_lo, x_hi): None = the grid's last plane."""
+        return self.grid_shape[0] if x_hi is None else x_hi
+
+    def _out(self, out, shape, what="out"):
+        """`out` if it is a contiguous float64 tensor of `shape` (ValueError otherwise); None: a zeroed new one."""
+        if out is None:
+            return torch.zeros(shape, dtype=torch.float64, device=self.device)
+        _require(out, shape, what)
+        return out
+
+    def _require_fields(self, fields):
+        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+
+    def _require_gain(self, gain):
+        _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
+
+    def _upload_items(self, *lists):
+        """The int32 item lists of api.path_items on this device."""
+        return [torch.from_numpy(a).to(self.device) for a in lists]
+
+    def _require_tabulated(self, who, gain_params=None):
+        """What the gain model reads is tabulated, or ValueError in the name of `who`: a "mesh" state needs the context's
+        state table and a "target" or "mesh" flow its flow table (tabulate() fills both).  gain_params: the caller's, for
+        the callers that hand them to the model with a "target" flow -- they must carry the ramp the table was tabulated
+        from."""
+        if self._state_is_mesh() and self.ctx.state() is None:
+            raise ValueError('%s: set_gain_state("mesh") needs tabulate() first' % who)
+        if isinstance(self.flow, str):
+            if gain_params is not None and self._flow_is("target") and _ramp(gain_params) != _ramp(self._flow_gp):
+                raise ValueError("%s: the flow table was tabulated from another Mach ramp or sound speed than gain_params "
+                                 "carries (set_flow(\"target\", gain_params), then tabulate())" % who)
+            if self.ctx.flow() is None:
+                raise ValueError('%s: set_flow("%s") needs tabulate() first' % (who, self.flow))
+
+    def _grid_layout(self, grid):
+        """api.grid_layout of a deposit tensor on this device: one grid, a padded one or a [G, ...] stack of dense ones."""
+        _require(grid, grid.shape, "grid")          # (which shapes: api.grid_layout)
+        if grid.device != self.device:
+            raise ValueError("grid must be on %s" % self.device)
+        layout = api.grid_layout(grid.shape, self.params)
+        if layout[3] and layout[2].edep_zpitch:
+            raise ValueError("grid: a stack holds dense grids %s, got %s" % (self.grid_shape, tuple(grid.shape)))
+        return layout
 
     def _trace(self, out, params, ctx=None):
         """cbet_trace_nodes into `out` with `params` on torch's current stream, from the tables of `ctx` (default: this
@@ -293,14 +365,7 @@ class RayTracer:
         api.cbet_solve(ctx=tracer.ctx) honour them from the next launch on, and so does every context prepared for this
         tracer later (the pipeline's).  A set-up call: it waits for torch's current stream.  A NaN or infinite shift or a
         wrong count raises and changes nothing."""
-        if dlambda_angstrom is not None and domega is not None:
-            raise ValueError("set_detuning takes dlambda_angstrom or domega, not both")
-        if dlambda_angstrom is not None:
-            dl = np.asarray(dlambda_angstrom, dtype=np.float64)
-            if not np.isfinite(dl).all():
-                raise ValueError("set_detuning: dlambda_angstrom holds a NaN or infinite value")
-            domega = api.wavelength_shift_to_domega(self.params, dl)
-        self.ctx.set_detuning(domega, self._stream())
+        self.ctx.set_detuning(shifts_to_domega(self.params, "set_detuning", dlambda_angstrom, domega, False), self._stream())
 
     def detuning(self):
         """The frequency shifts in use (rad/s, one per beam; the context's own record), or None if none."""
@@ -318,13 +383,7 @@ class RayTracer:
         exchange_matrix, both loops of cbet_solve and the contexts this tracer prepares later honour it; the tracer keeps no
         copy.  A set-up call: it waits for torch's current stream.  A NaN or infinite offset or a weight that is not finite and
         > 0 raises and changes nothing."""
-        if domega is not None and dlambda_angstrom is not None:
-            raise ValueError("set_bandwidth takes domega or dlambda_angstrom, not both")
-        if dlambda_angstrom is not None:
-            dl = np.asarray(dlambda_angstrom, dtype=np.float64)
-            if not np.isfinite(dl).all():
-                raise ValueError("set_bandwidth: dlambda_angstrom holds a NaN or infinite value")
-            domega = api.wavelength_shift_to_domega(self.params, dl)
+        domega = shifts_to_domega(self.params, "set_bandwidth", dlambda_angstrom, domega, False)
         self.ctx.set_bandwidth(domega, weights, self._stream())
 
     def bandwidth(self):
@@ -353,17 +412,10 @@ class RayTracer:
         [x_lo, x_hi): a grid-shaped tensor (`out`, or a zeroed new one; cells of other planes are left as they are).
         `fields` are normalised fields [4, nbeams, ...] as gain_field leaves them; they are not changed.  The flow and the
         gain state are read as gain_field reads them; the limit of set_saturation is not."""
-        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
-        if self._state_is_mesh() and self.ctx.state() is None:
-            raise ValueError("pair_amplitude: set_gain_state(\"mesh\") needs tabulate() first")
-        if isinstance(self.flow, str) and self.ctx.flow() is None:
-            raise ValueError("pair_amplitude: set_flow(\"%s\") needs tabulate() first" % self.flow)
-        if out is None:
-            out = torch.zeros(self.grid_shape, dtype=torch.float64, device=self.device)
-        else:
-            _require(out, self.grid_shape, "out")
-        api.pair_amplitude(fields, ne3d, out, x_lo, self.grid_shape[0] if x_hi is None else x_hi, self.params, gain_params,
-                           self.ctx, self._stream())
+        self._require_fields(fields)
+        self._require_tabulated("pair_amplitude")
+        out = self._out(out, self.grid_shape)
+        api.pair_amplitude(fields, ne3d, out, x_lo, self._x_hi(x_hi), self.params, gain_params, self.ctx, self._stream())
         return out
 
     def exchange_matrix(self, fields, gain_params, x_lo=0, x_hi=None, ne3d=None, out=None, gross=False):
@@ -374,26 +426,18 @@ class RayTracer:
         `fields` are normalised fields [4, nbeams, ...] as gain_field leaves them; they are not changed.  The flow and the
         gain state are read as gain_field reads them, and the limit of set_saturation is honoured."""
         nb = self.params.nbeams
-        _require(fields, (4, nb) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
-        if self._state_is_mesh() and self.ctx.state() is None:
-            raise ValueError("exchange_matrix: set_gain_state(\"mesh\") needs tabulate() first")
-        if isinstance(self.flow, str) and self.ctx.flow() is None:
-            raise ValueError("exchange_matrix: set_flow(\"%s\") needs tabulate() first" % self.flow)
-        if out is None:
-            out = torch.zeros((nb, nb), dtype=torch.float64, device=self.device)
-        else:
-            _require(out, (nb, nb), "out")
-        if gross is True:
-            gross = torch.zeros((nb, nb), dtype=torch.float64, device=self.device)
-        elif gross is False or gross is None:
+        self._require_fields(fields)
+        self._require_tabulated("exchange_matrix")
+        out = self._out(out, (nb, nb))
+        if gross is False or gross is None:                # True: a zeroed new one; a tensor: that one
             gross = None
         else:
-            _require(gross, (nb, nb), "gross")
+            gross = self._out(None if gross is True else gross, (nb, nb), "gross")
         if self._exchange_work is None:      # one double at the least: a single beam needs none, the entry wants a pointer
             self._exchange_work = torch.empty(max(api.exchange_matrix_work_bytes(self.params) // 8, 1), dtype=torch.float64,
                                               device=self.device)
-        api.exchange_matrix(fields, ne3d, out, gross, self._exchange_work, x_lo, self.grid_shape[0] if x_hi is None else x_hi,
-                            self.params, gain_params, self.ctx, self._stream())
+        api.exchange_matrix(fields, ne3d, out, gross, self._exchange_work, x_lo, self._x_hi(x_hi), self.params, gain_params,
+                            self.ctx, self._stream())
         return out if gross is None else (out, gross)
 
     # ---- quarter-critical LPI maps (include/cbet_mi355x.h cbet_lpi_map; DESIGN.md section 23) -----------------------
@@ -439,7 +483,7 @@ class RayTracer:
         call then waits for the stream); a tensor of new_lpi_summary() -- the call MERGES into it (slab calls and ranks
         compose) and returns it, without waiting; False -- no summary, None comes back.
         Runs on torch's current stream; ne3d: a caller's node table instead of the context's."""
-        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+        self._require_fields(fields)
         nodes = (self.params.nx, self.params.ny, self.params.nz)
         if ne3d is not None:
             _require(ne3d, nodes, "ne3d")
@@ -457,10 +501,7 @@ class RayTracer:
             te3d = te
         else:
             te_ev = float(te)
-        if out is None:
-            out = torch.zeros((api.LPI_NQ,) + self.grid_shape, dtype=torch.float64, device=self.device)
-        else:
-            _require(out, (api.LPI_NQ,) + self.grid_shape, "out")
+        out = self._out(out, (api.LPI_NQ,) + self.grid_shape)
         read_back = summary is None
         if summary is False:
             summary = None
@@ -472,8 +513,8 @@ class RayTracer:
         if summary is not None and self._lpi_work is None:
             self._lpi_work = torch.empty(max(api.lpi_work_bytes(self.params), 8), dtype=torch.uint8, device=self.device)
         api.lpi_map(fields, ne3d, te3d, te_ev, float(band[0]), float(band[1]), int(cone_bins), out, summary,
-                    self._lpi_work if summary is not None else None, x_lo, self.grid_shape[0] if x_hi is None else x_hi,
-                    self.params, self.ctx, self._stream())
+                    self._lpi_work if summary is not None else None, x_lo, self._x_hi(x_hi), self.params, self.ctx,
+                    self._stream())
         if read_back:
             return out, api.lpi_summary_from(summary)
         return out, summary
@@ -511,9 +552,8 @@ class RayTracer:
         # a single grid whose rows are longer than nz + 2 is a padded grid (new_grid(zpitch=...))
         padded = (not per_beam) and edep.dim() == 3 and tuple(edep.shape[:2]) == want[:2] and edep.shape[2] > want[2]
         _require(edep, edep.shape if padded else want, "edep (one grid, one per beam, or one with padded rows)")
-        p = self.params.copy(per_beam_grids=1 if per_beam else 0, beam_lo=beam_lo,
-                             beam_hi=self.params.nbeams if beam_hi is None else beam_hi,
-                             shard_index=shard_index, shard_count=shard_count, edep_zpitch=int(edep.shape[2]) if padded else 0)
+        p = self._launch_params(beam_lo, beam_hi, shard_index, shard_count, per_beam_grids=1 if per_beam else 0,
+                                edep_zpitch=int(edep.shape[2]) if padded else 0)
         if kernel_variant is not None:
             p.kernel_variant = kernel_variant
         if force_wide_index is not None:
@@ -563,10 +603,8 @@ class RayTracer:
         _require(out, want, "out")
         if gain is not None:
             _require(gain, (ngrids,) + self.grid_shape, "gain")
-        p = self.params.copy(per_beam_grids=1 if per_beam else 0, beam_lo=beam_lo,
-                             beam_hi=self.params.nbeams if beam_hi is None else beam_hi,
-                             shard_index=shard_index, shard_count=shard_count,
-                             grid_beam0=grid_beam0, grid_beams=grid_beams)
+        p = self._launch_params(beam_lo, beam_hi, shard_index, shard_count, per_beam_grids=1 if per_beam else 0,
+                                grid_beam0=grid_beam0, grid_beams=grid_beams)
         quantity = api.DEPOSIT_FIELD_ENERGY if fields == "energy" else (api.DEPOSIT_FIELDS if fields else api.DEPOSIT_ENERGY)
         api.trace_cbet(0, self.derived.nindices, ne3d, kappa3d, gain, quantity, out, beam_gain, *self._tail(), p, gain_params,
                        self.ctx, self._stream())
@@ -588,20 +626,12 @@ class RayTracer:
         ramp of set_flow's gain parameters -- `gain_params` must carry the same ramp; a "mesh" flow is the mesh's velocity
         as the last tabulate() wrote it.  With a gain state set (set_gain_state) the update reads the sound speed and the gain
         constant from it; a "mesh" state is the one the last tabulate() wrote."""
-        if self._state_is_mesh() and self.ctx.state() is None:
-            raise ValueError("gain_field: set_gain_state(\"mesh\") needs tabulate() before the first gain update")
-        if isinstance(self.flow, str):
-            ramp = lambda g: (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)  # noqa: E731
-            if self._flow_is("target") and ramp(gain_params) != ramp(self._flow_gp):
-                raise ValueError("gain_field: the flow table was tabulated from another Mach ramp or sound speed than "
-                                 "gain_params carries (set_flow(\"target\", gain_params), then tabulate())")
-            if self.ctx.flow() is None:
-                raise ValueError("gain_field: set_flow(\"%s\") needs tabulate() before the first gain update" % self.flow)
+        self._require_tabulated("gain_field", gain_params)
         if pair_once is None:
             pair_once = scratch is not None
         scratch = gain if pair_once else None
-        api.gain_field_slab(fields, ne3d, gain, scratch, change, x_lo, self.grid_shape[0] if x_hi is None else x_hi,
-                            self.params, _frozen(gain_params, frozen), self.ctx, self._stream())
+        api.gain_field_slab(fields, ne3d, gain, scratch, change, x_lo, self._x_hi(x_hi), self.params,
+                            _frozen(gain_params, frozen), self.ctx, self._stream())
         return gain
 
     def cbet_solve(self, edep, gain_params, rank=0, world_size=1, group=None, fields=None, gain=None, slabs=False,
@@ -654,7 +684,7 @@ class RayTracer:
         """The gain_params a no-deposit pass (trace_exits, trace_paths) hands on: with a gain grid, its shape checked and
         api.default_gain_params() in place of None."""
         if gain is not None:
-            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
+            self._require_gain(gain)
             if gain_params is None:
                 gain_params = api.default_gain_params()
         return gain_params
@@ -669,8 +699,7 @@ class RayTracer:
         gain_params = self._gain_args(gain, gain_params)
         if tabulate:
             self.tabulate()
-        p = self.params.copy(beam_lo=beam_lo, beam_hi=self.params.nbeams if beam_hi is None else beam_hi,
-                             shard_index=shard_index, shard_count=shard_count)
+        p = self._launch_params(beam_lo, beam_hi, shard_index, shard_count)
         api.trace_exits(None, None, gain, exits, *self._tail(), p, gain_params, self.ctx, self._stream())
         return exits
 
@@ -732,19 +761,16 @@ class RayTracer:
             capacity = 1 + -(-self.derived.nt // stride)
         if capacity < 0:
             raise ValueError("capacity must be >= 0")
-        if out is None:
-            samples, turns = self.new_paths(nitems, capacity)
-        else:
-            samples, turns = out
-            _require(turns, (nitems, 8), "turns (new_paths())")
-            if samples is not None or capacity > 0:
-                _require(samples, (capacity, nitems, 8), "samples (new_paths())")
+        samples, turns = self.new_paths(nitems, capacity) if out is None else out
+        _require(turns, (nitems, 8), "turns (new_paths())")
+        if samples is not None or capacity > 0:
+            _require(samples, (capacity, nitems, 8), "samples (new_paths())")
         gain_params = self._gain_args(gain, gain_params)
         if nitems == 0:                # (empty tensors have no address to hand over)
             return samples, turns
         if tabulate:
             self.tabulate()
-        d_beams, d_raynums = torch.from_numpy(beams).to(self.device), torch.from_numpy(raynums).to(self.device)
+        d_beams, d_raynums = self._upload_items(beams, raynums)
         api.trace_paths(None, None, gain, d_beams, d_raynums, nitems, stride, capacity, center,
                         samples if capacity > 0 else None, turns, *self._tail(), self.params, gain_params, self.ctx,
                         self._stream())
@@ -772,28 +798,13 @@ class RayTracer:
         Returns {"gamma": float64 [nshift, nitems] (shift-major), "rays": float64 [nitems, 4] (cbet_ray_sbs: gmax, uray0,
         uray_end, then steps / imax / status -- .cpu().numpy().view(api.SBS_DTYPE)[..., 0] names them), "shifts": domega as a
         numpy array, "beams": the items' beams on the device}; out: (gamma, rays) tensors to write into."""
-        _require(fields, (4, self.params.nbeams) + self.grid_shape, "fields (new_fields(), normalised by gain_field)")
+        self._require_fields(fields)
         if gain_params is None:
             raise ValueError("backscatter_gain needs gain_params (the model's damping, Mach ramp and plasma state)")
-        if (dlambda_angstrom is None) == (domega is None):
-            raise ValueError("backscatter_gain takes ONE of dlambda_angstrom or domega")
-        if dlambda_angstrom is not None:
-            dl = np.asarray(dlambda_angstrom, dtype=np.float64)
-            if not np.isfinite(dl).all():
-                raise ValueError("backscatter_gain: dlambda_angstrom holds a NaN or infinite value")
-            domega = api.wavelength_shift_to_domega(self.params, dl)
-        shifts = api.sbs_shifts(domega)
+        shifts = api.sbs_shifts(shifts_to_domega(self.params, "backscatter_gain", dlambda_angstrom, domega, True))
         if not self._tables_filled:
             raise ValueError("backscatter_gain: the context's node tables are not filled: tabulate() first")
-        if self._state_is_mesh() and self.ctx.state() is None:
-            raise ValueError("backscatter_gain: set_gain_state(\"mesh\") needs tabulate() first")
-        if isinstance(self.flow, str):
-            ramp = lambda g: (g.mach_r0, g.mach_0, g.mach_r1, g.mach_1, g.z_ion, g.te_ev, g.ti_ev, g.mi_over_me)  # noqa: E731
-            if self._flow_is("target") and ramp(gain_params) != ramp(self._flow_gp):
-                raise ValueError("backscatter_gain: the flow table was tabulated from another Mach ramp or sound speed than "
-                                 "gain_params carries (set_flow(\"target\", gain_params), then tabulate())")
-            if self.ctx.flow() is None:
-                raise ValueError("backscatter_gain: set_flow(\"%s\") needs tabulate() first" % self.flow)
+        self._require_tabulated("backscatter_gain", gain_params)
         if (beams is None) != (raynums is None):
             raise ValueError("backscatter_gain takes beams and raynums together, or neither (ray_items())")
         if beams is None:
@@ -801,21 +812,16 @@ class RayTracer:
         beams, raynums = api.path_items(beams, raynums)
         nitems, nshift = int(beams.size), int(shifts.size)
         if gain is not None:
-            _require(gain, (self.params.nbeams,) + self.grid_shape, "gain")
+            self._require_gain(gain)
         if ne3d is not None:
             _require(ne3d, (self.params.nx, self.params.ny, self.params.nz), "ne3d")
-        f64 = dict(dtype=torch.float64, device=self.device)
-        if out is None:
-            gamma, rays = torch.zeros((nshift, nitems), **f64), torch.zeros((nitems, 4), **f64)
-        else:
-            gamma, rays = out
-            _require(gamma, (nshift, nitems), "gamma")
-            _require(rays, (nitems, 4), "rays")
-        d_beams = torch.from_numpy(beams).to(self.device)
+        gamma, rays = (self._out(None, (nshift, nitems)), self._out(None, (nitems, 4))) if out is None else out
+        _require(gamma, (nshift, nitems), "gamma")
+        _require(rays, (nitems, 4), "rays")
+        d_beams, d_raynums = self._upload_items(beams, raynums)
         result = {"gamma": gamma, "rays": rays, "shifts": shifts, "beams": d_beams}
         if nitems == 0:                # (empty tensors have no address to hand over)
             return result
-        d_raynums = torch.from_numpy(raynums).to(self.device)
         api.trace_backscatter(ne3d, None, gain, d_beams, d_raynums, nitems, fields, shifts, gamma, rays, *self._tail(),
                               self.params, gain_params, self.ctx, self._stream())
         return result
@@ -828,14 +834,11 @@ class RayTracer:
         gamma, rays = result["gamma"], result["rays"]
         nshift, nitems = gamma.shape
         nb = self.params.nbeams
-        d_beams = result["beams"] if beams is None else torch.from_numpy(api.path_items(beams, beams)[0]).to(self.device)
+        d_beams = result["beams"] if beams is None else self._upload_items(api.path_items(beams, beams)[0])[0]
         if int(d_beams.numel()) != nitems:
             raise ValueError("beams holds %d items, the result %d" % (int(d_beams.numel()), nitems))
         _require(rays, (nitems, 4), "rays")
-        if out is None:
-            out = torch.zeros((nb, nshift, 4), dtype=torch.float64, device=self.device)
-        else:
-            _require(out, (nb, nshift, 4), "out")
+        out = self._out(out, (nb, nshift, 4))
         if nitems == 0:
             return out
         work = torch.empty(max(api.backscatter_work_bytes(nitems, nshift, nb) // 8, 1), dtype=torch.float64, device=self.device)
@@ -851,24 +854,8 @@ class RayTracer:
         with a leading [G] on the first two for a stack; modes.nonuniformity turns coeffs into sigma_l, sigma_rms."""
         from . import modes
         edges = np.ascontiguousarray(modes.default_shells(self.params, 32) if r_edges is None else r_edges, dtype=np.float64)
-        p = self.params.copy(edep_zpitch=0)
-        stack = False
-        if geometry:
-            edep, ngrids, stride = None, 1, 0
-        else:
-            gs = self.grid_shape
-            _require(grid, grid.shape, "grid")          # (which shapes: below)
-            if grid.device != self.device:
-                raise ValueError("grid must be on %s" % self.device)
-            if grid.dim() == 4 and tuple(grid.shape[1:]) == gs:
-                stack, ngrids, stride = True, grid.shape[0], int(np.prod(gs))
-            elif grid.dim() == 3 and tuple(grid.shape[:2]) == gs[:2] and grid.shape[2] >= gs[2]:
-                ngrids, stride = 1, 0
-                if grid.shape[2] > gs[2]:
-                    p.edep_zpitch = int(grid.shape[2])
-            else:
-                raise ValueError("grid must be %s, a padded grid or a [G, ...] stack of them, got %s" % (gs, tuple(grid.shape)))
-            edep = grid
+        edep = None if geometry else grid
+        ngrids, stride, p, stack = api.grid_layout(None, self.params) if geometry else self._grid_layout(grid)
         nshell, ncoef = edges.size - 1, (lmax + 1) ** 2
         f64 = dict(dtype=torch.float64, device=self.device)
         coeffs = torch.empty((ngrids, max(nshell, 0), ncoef), **f64)
@@ -895,20 +882,7 @@ class RayTracer:
                 r, theta, phi, center = self._mesh_nodes
                 self._mesh_cells = api.MeshCells.from_nodes(r, theta, phi, center, gpu=self.gpu)
             cells = self._mesh_cells
-        gs = self.grid_shape
-        _require(grid, grid.shape, "grid")          # (which shapes: below)
-        if grid.device != self.device:
-            raise ValueError("grid must be on %s" % self.device)
-        p = self.params.copy(edep_zpitch=0)
-        stack = False
-        if grid.dim() == 4 and tuple(grid.shape[1:]) == gs:
-            stack, ngrids, stride = True, grid.shape[0], int(np.prod(gs))
-        elif grid.dim() == 3 and tuple(grid.shape[:2]) == gs[:2] and grid.shape[2] >= gs[2]:
-            ngrids, stride = 1, 0
-            if grid.shape[2] > gs[2]:
-                p.edep_zpitch = int(grid.shape[2])
-        else:
-            raise ValueError("grid must be %s, a padded grid or a [G, ...] stack of them, got %s" % (gs, tuple(grid.shape)))
+        ngrids, stride, p, stack = self._grid_layout(grid)
         energy = torch.empty((ngrids,) + cells.shape, dtype=torch.float64, device=self.device)
         outside = torch.empty(ngrids, dtype=torch.float64, device=self.device)
         samples = torch.empty(cells.shape, dtype=torch.int64, device=self.device)

@@ -30,11 +30,79 @@ def test_library_exports_every_declared_symbol(api):
         assert hasattr(L, name), name
 
 
+_C_KINDS = {"int": "int", "unsigned": "unsigned", "unsigned int": "unsigned", "long": "i64", "long long": "i64",
+            "size_t": "u64", "unsigned long long": "u64", "double": "double", "void": "void", "char": "char"}
+
+
+def _c_kind(ctype):
+    """(kind, pointee) of a C type without its parameter name: anything with * or [ is a pointer, whose pointee is the type
+    with one * or [n] taken off; kind None = not classified."""
+    t = " ".join(re.sub(r"\bconst\b", " ", ctype).split())
+    if "*" in t or "[" in t:
+        return "ptr", re.sub(r"\s*(\*|\[\d*\])$", "", t, count=1).strip()
+    return _C_KINDS.get(t), None
+
+
+def _ctypes_kind(ct):
+    if ct is None:
+        return "void"
+    if ct in (C.c_void_p, C.c_char_p) or issubclass(ct, C._Pointer):
+        return "ptr"
+    return {C.c_int: "int", C.c_uint: "unsigned", C.c_long: "i64", C.c_longlong: "i64", C.c_size_t: "u64",
+            C.c_ulonglong: "u64", C.c_double: "double"}.get(ct)
+
+
+def _mismatch(api, ctype, ct):
+    """Why the ctypes type `ct` does not describe the C type `ctype`, or None if it does."""
+    kind, pointee = _c_kind(ctype)
+    if kind is None:
+        return "the C type %r is not classified" % ctype
+    if kind != _ctypes_kind(ct):
+        return "%r is %s in the header, %s in the table" % (ctype, kind, _ctypes_kind(ct))
+    if kind == "ptr" and (ct is C.c_char_p or pointee == "char"):
+        return None if (ct is C.c_char_p and pointee == "char") else "%r and c_char_p go together" % ctype
+    if kind == "ptr" and ct is not C.c_void_p:              # POINTER(T): the header's pointee is T
+        target = ct._type_
+        if issubclass(target, C.Structure):
+            names = [name for name, cls in api.STRUCTS.items() if cls is target]
+            return None if names == [pointee] else "%r points to %s in the table" % (ctype, names or target.__name__)
+        if _c_kind(pointee)[0] != _ctypes_kind(target):
+            return "%r points to %s in the table" % (ctype, target.__name__)
+    return None
+
+
+def test_signatures_match_header(api):
+    """api.SIGNATURES vs the prototypes of the C header: the same names, and the return type and every parameter of the same
+    kind -- pointer, int, unsigned, signed or unsigned 64-bit, double, void; a POINTER(T) of the table points to the
+    header's T (a struct by its name in api.STRUCTS), and char * is c_char_p."""
+    hdr = open(os.path.join(ROOT, "include", "cbet_mi355x.h")).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    protos = {m.group(2): (m.group(1), m.group(3))
+              for m in re.finditer(r"^[ \t]*([\w \t\*]+?)\b(cbet_\w+)[ \t]*\(([^()]*)\)\s*;", hdr, flags=re.M)}
+    assert set(protos) == set(api.SIGNATURES), sorted(set(protos) ^ set(api.SIGNATURES))
+    errors = []
+    for name, (ret, params) in protos.items():
+        restype, argtypes = api.SIGNATURES[name]
+        params = [] if params.strip() == "void" else [re.sub(r"\w+\s*(\[\d*\])?\s*$", r"\1", p.strip()) for p in params.split(",")]
+        if len(params) != len(argtypes):
+            errors.append("%s: %d parameters in the header, %d in the table" % (name, len(params), len(argtypes)))
+            continue
+        for where, ctype, ct in [("return", ret, restype)] + [("argument %d" % k, c, t) for k, (c, t) in enumerate(zip(params, argtypes))]:
+            why = _mismatch(api, ctype, ct)
+            if why:
+                errors.append("%s, %s: %s" % (name, where, why))
+    assert not errors, "\n".join(errors)
+    L = api.lib()
+    for name, (restype, argtypes) in api.SIGNATURES.items():      # ... and the table is what the loaded library is called by
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == list(argtypes), name
+
+
 def test_struct_layout_matches_header(api, tmp_path):
-    """ctypes mirrors vs the C header: sizeof and every field offset, asked of gcc."""
+    """ctypes mirrors vs the C header: sizeof and every field offset of every struct of api.STRUCTS, asked of gcc; the numpy
+    dtypes of the four records have the same size and offsets."""
     import subprocess
-    probes = {"cbet_params": api.Params, "cbet_derived": api.Derived, "cbet_counters": api.Counters,
-              "cbet_gain_params": api.GainParams, "cbet_cbet_report": api.CbetReport}
+    probes = api.STRUCTS
+    assert len(probes) == 14
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "cbet_mi355x.h"', 'int main(void){']
     for cname, cls in probes.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -50,6 +118,13 @@ def test_struct_layout_matches_header(api, tmp_path):
         assert int(got[cname]) == C.sizeof(cls), cname
         for fname, _ in cls._fields_:
             assert int(got["%s.%s" % (cname, fname)]) == getattr(cls, fname).offset, (cname, fname)
+    twins = {"cbet_ray_exit": api.EXIT_DTYPE, "cbet_path_sample": api.PATH_DTYPE, "cbet_ray_turn": api.TURN_DTYPE,
+             "cbet_ray_sbs": api.SBS_DTYPE}
+    for cname, dt in twins.items():
+        assert dt.itemsize == int(got[cname]) and dt.names == tuple(f for f, _ in probes[cname]._fields_), cname
+        for fname in dt.names:
+            assert dt.fields[fname][1] == int(got["%s.%s" % (cname, fname)]), (cname, fname)
+            assert dt.fields[fname][0].itemsize == C.sizeof(dict(probes[cname]._fields_)[fname]), (cname, fname)
     p = api.default_params(100)
     assert (p.nx, p.nbeams, p.rays_per_zone, p.nprofile, p.max_threads, p.threads_per_block) == \
         (100, 60, 4, 443, 120000000, 256)

@@ -143,6 +143,18 @@ def test_wavelength_scan_is_the_detuning_conversion(api, ragged):
         ragged.tr.backscatter_gain(ragged.d_fields, gp)
     with pytest.raises(ValueError):
         ragged.tr.backscatter_gain(ragged.d_fields, gp, domega=[0.0] * 17)
+    # out=: tensors of the result's own shapes are written into; any other shape is refused before the launch
+    gamma, rays = a["gamma"].clone().zero_(), a["rays"].clone().zero_()
+    c = ragged.tr.backscatter_gain(ragged.d_fields, gp, domega=domega, beams=ragged.beams[:200], raynums=ragged.raynums[:200],
+                                   out=(gamma, rays))
+    assert c["gamma"] is gamma and c["rays"] is rays and _raw(gamma.cpu().numpy()) == _raw(b["gamma"].cpu().numpy())
+    for bad in ((gamma[:, :199].contiguous(), rays), (gamma, rays[:199]), (gamma.float(), rays)):
+        with pytest.raises(ValueError):
+            ragged.tr.backscatter_gain(ragged.d_fields, gp, domega=domega, beams=ragged.beams[:200], raynums=ragged.raynums[:200],
+                                       out=bad)
+    table = ragged.tr.backscatter_tally(a)
+    with pytest.raises(ValueError):
+        ragged.tr.backscatter_tally(a, out=table[:, :3].contiguous())
 
 
 # ---- 2. the end state is the exit pass's -----------------------------------------------------------------------------------

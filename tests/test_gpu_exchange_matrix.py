@@ -130,6 +130,13 @@ def test_exact_properties_on_the_device(api, torch_cuda, worlds, grid):
     assert bool((G >= T.abs()).all()) and float(G.max()) > 0
     alone = tr.exchange_matrix(f, w["gp"], ne3d=w["dev"]["ne3d"])           # without gross: the tensor alone, the same bits
     assert torch.is_tensor(alone) and torch.equal(alone, T)
+    # out= and gross= as tensors are ADDED into and handed back; any other shape or dtype is refused before the launch
+    mine, mine_g = torch.zeros_like(T), torch.zeros_like(G)
+    got = tr.exchange_matrix(f, w["gp"], ne3d=w["dev"]["ne3d"], out=mine, gross=mine_g)
+    assert got[0] is mine and got[1] is mine_g and torch.equal(mine.triu(), T.triu()) and torch.equal(mine_g.triu(), G.triu())
+    for bad in (dict(out=T[:-1].contiguous()), dict(gross=G[:, :-1].contiguous()), dict(out=T.float()), dict(gross=G.t()[:, :-1])):
+        with pytest.raises(ValueError):
+            tr.exchange_matrix(f, w["gp"], ne3d=w["dev"]["ne3d"], **bad)
     # a view of the fields that starts 1 and 8 doubles off a 128-byte line: the aligned call's bits
     buf = torch.empty(f.numel() + 16, dtype=torch.float64, device="cuda")
     assert buf.data_ptr() % 128 == 0 and f.data_ptr() % 128 == 0

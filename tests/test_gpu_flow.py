@@ -256,6 +256,16 @@ def test_callers_table(api, torch_cuda, world):
     p = tr.params
     host = api.flow_table(p, gp, api.Target(SHIFT))
     try:
+        # a "target" flow is tabulated from one ramp: gain parameters that carry another are refused by the callers that
+        # hand theirs to the model
+        tr.set_flow("target", gp)
+        tr.tabulate()
+        other = type(gp).from_buffer_copy(gp)
+        other.mach_0 = gp.mach_0 + 0.25
+        for reader in (lambda: tr.gain_field(tr.new_fields(), tr.new_grid(per_beam=True), other),
+                       lambda: tr.backscatter_gain(tr.new_fields(), other, domega=[0.0])):
+            with pytest.raises(ValueError, match="Mach ramp"):
+                reader()
         for pair_once in (False, True):
             tr.set_flow("target", gp)
             tr.tabulate()

@@ -178,6 +178,10 @@ def test_te_from_the_tables_and_the_contexts_own_density(api, torch_cuda, cases,
     assert f.cpu().numpy().tobytes() == twin.tobytes() and sf["max_eta_cw"] == ts["max_eta_cw"]
     with pytest.raises(ValueError):
         _device(c, te="profile")
+    with pytest.raises(ValueError):                     # out=: a stack of another shape is refused before the launch
+        _device(c, te=1500.0, out=f[:-1].contiguous())
+    mine = torch.zeros_like(f)
+    assert _device(c, te=1500.0, out=mine)[0] is mine and torch.equal(mine, f)
     with pytest.raises(api.CbetError, match="te_ev"):
         _device(c, te=0.0)
     with pytest.raises(api.CbetError, match="band"):

@@ -295,6 +295,11 @@ def test_stride_and_truncation_long_box(api, inputs, torch_cuda):
     assert none is None
     assert torch.equal(turns0, full_t[:n])
     assert bool((full_t0[n].view(torch.int64) == NAN_PATTERN).all())
+    # out= of other shapes than new_paths(n, capacity) gives is refused before the launch
+    good_s, good_t = tr.new_paths(n, capacity)
+    for bad in ((good_s[:-1], good_t), (good_s, good_t[:-1]), (good_s, good_t.float())):
+        with pytest.raises(ValueError):
+            tr.trace_paths(beams, raynums, stride=stride, capacity=capacity, out=bad)
     tr.close()
 
 

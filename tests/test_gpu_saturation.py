@@ -257,6 +257,9 @@ def test_amplitude_map_matches_the_reference(api, torch_cuda, worlds, grid, tabl
         tr.set_saturation(0.0)
         part = torch.full(tr.grid_shape, -3.0, dtype=torch.float64, device="cuda")
         assert tr.pair_amplitude(f, gp, x_lo=slab[0], x_hi=slab[1], out=part) is part
+        for bad in (part[1:].contiguous(), part.float(), part.transpose(0, 2)):   # another shape, dtype or layout: refused
+            with pytest.raises(ValueError):
+                tr.pair_amplitude(f, gp, out=bad)
         torch.cuda.synchronize()
     finally:
         tr.set_saturation(0.0)

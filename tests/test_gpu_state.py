@@ -356,6 +356,20 @@ def test_cbet_stage_on_the_mesh_state(api, inputs, torch_cuda):
         assert tr.ctx.state() is None
         with pytest.raises(ValueError):
             tr.gain_field(tr.new_fields(), tr.new_grid(per_beam=True), gp)      # no table before tabulate()
+        # every reader of the gain model refuses alike: first the missing state table, then -- the state set aside -- the
+        # missing table of the "mesh" flow
+        blank = tr.new_fields()
+        readers = (lambda: tr.gain_field(blank, tr.new_grid(per_beam=True), gp), lambda: tr.pair_amplitude(blank, gp),
+                   lambda: tr.exchange_matrix(blank, gp), lambda: tr.backscatter_gain(blank, gp, domega=[0.0]))
+        for reader in readers:
+            with pytest.raises(ValueError, match="set_gain_state"):
+                reader()
+        tr.set_gain_state(None)
+        assert tr.ctx.flow() is None
+        for reader in readers:
+            with pytest.raises(ValueError, match="set_flow"):
+                reader()
+        tr.set_gain_state("mesh")
         tr.tabulate()
         assert tr.ctx.state() is not None
         state = _state(api, tr)

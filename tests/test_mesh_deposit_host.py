@@ -229,11 +229,6 @@ def test_from_nodes_edges_are_midpoints(api):
 
 
 def test_exports_and_argtypes(api):
-    L = api.lib()
-    for name in ("cbet_mesh_cells_create", "cbet_mesh_cells_destroy", "cbet_mesh_deposit_device", "cbet_mesh_deposit"):
-        assert name in api.EXPORTS
-        assert getattr(L, name).argtypes is not None
-    assert len(L.cbet_mesh_deposit_device.argtypes) == 11 and L.cbet_mesh_deposit.argtypes == L.cbet_mesh_deposit_device.argtypes
     assert (api.MESH_DEPOSIT_AUTO, api.MESH_DEPOSIT_GLOBAL, api.MESH_DEPOSIT_LDS, api.MESH_MAX_SUBSAMPLES) == (0, 1, 2, 4)
     c = api.MeshCells(D.R_EDGES)
     c.close()

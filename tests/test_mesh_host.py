@@ -218,5 +218,3 @@ def test_python_mesh_helper(api):
         api.Mesh(kw["r"], kw["theta"], kw["phi"], np.ones((3, 3, 5)), np.ones((3, 3, 4)))
     with pytest.raises(ValueError):
         api.Mesh(kw["r"], None, None, np.ones(3), np.ones(3), velocity=[np.ones(3)])
-    for name in ("cbet_tabulate_mesh", "cbet_tabulate_mesh_flow", "cbet_mesh_tables", "cbet_mesh_flow_table"):
-        assert name in api.EXPORTS

@@ -24,13 +24,6 @@ def api():
     return a
 
 
-def test_new_entry_points_exported(api):
-    L = C.CDLL(api.LIB_PATH)
-    for name in ("cbet_sph_modes_device", "cbet_sph_modes"):
-        assert hasattr(L, name), name
-        assert name in api.EXPORTS, name
-
-
 def test_bad_arguments_are_refused(api):
     """Every refusal happens before any HIP call (no device here: the fake pointers are never touched)."""
     L = api.lib()
@@ -270,3 +263,24 @@ def test_listing_no_scratch_at_lmax16_and_no_atomics(listing):
         ops = [l.split()[0] for l in body.splitlines() if l.startswith("\t") and not l.strip().startswith(";")]
         assert ops and not [o for o in ops if "atomic" in o], name
         assert any(o.startswith("global_store") for o in ops), name
+
+
+def test_grid_layout_reads_one_grid_a_padded_grid_or_a_stack(api):
+    """api.grid_layout, the one reading of a deposit array's shape (sph_modes, deposit_on_mesh and their host twins):
+    (ngrids, grid_stride, params with edep_zpitch, stacked)."""
+    p = api.default_params(8)
+    p.edep_zpitch = 24                                      # whatever the caller's params say, the shape decides
+    want = {(10, 10, 10): (1, 1000, 0, False), (10, 10, 16): (1, 1600, 16, False), (3, 10, 10, 10): (3, 1000, 0, True),
+            (1, 10, 10, 10): (1, 1000, 0, True), (2, 10, 10, 16): (2, 1600, 16, True)}
+    for shape, (ngrids, stride, zpitch, stacked) in want.items():
+        got = api.grid_layout(shape, p)
+        assert (got[0], got[1], got[2].edep_zpitch, got[3]) == (ngrids, stride, zpitch, stacked), shape
+        assert got[2] is not p and (got[2].nx, got[2].nbeams) == (p.nx, p.nbeams)
+    got = api.grid_layout(None, p)                          # no array: geometry mode, counts alone
+    assert (got[0], got[1], got[2].edep_zpitch, got[3]) == (1, 0, 0, False)
+    assert p.edep_zpitch == 24                              # the caller's params are not changed
+    for shape in ((10, 10, 9), (10, 9, 10), (9, 10, 10), (10, 10), (2, 3, 10, 10, 10), (3, 10, 10, 9)):
+        with pytest.raises(ValueError):
+            api.grid_layout(shape, p)
+    with pytest.raises(ValueError):                         # ... and through the host twin
+        api.sph_modes_host(np.zeros((10, 9, 10)), api.default_params(8), (0.0, 0.0, 0.0), [0.0, 0.1], 2)

