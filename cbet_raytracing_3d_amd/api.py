@@ -529,13 +529,21 @@ def _signatures():
         "cbet_backscatter_work_bytes": (usz, [i64, i32, i32]),
         "cbet_backscatter_tally": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp]),
         "cbet_backscatter_host": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, dp, i32, vp, vp, P, G]),
+        "cbet_mix_work_bytes": (usz, [i64]),
+        "cbet_mix_residual": (i32, [vp, vp, vp, vp, i32, i64, vp, vp, vp]),
+        "cbet_mix_apply": (i32, [vp, dp, i32, i64, vp, vp, vp]),
+        "cbet_mix_coefficients": (i32, [dp, i32, dp, ip]),
+        "cbet_mix_residual_host": (i32, [vp, vp, vp, vp, i32, i64, dp]),
+        "cbet_mix_apply_host": (i32, [vp, dp, i32, i64, vp, vp]),
     }
 
 
 SIGNATURES = _signatures()
 EXPORTS = list(SIGNATURES)      # every symbol include/cbet_mi355x.h declares
-# lib(tolerate=...): the detuning, polarization, bandwidth and backscatter entries, which an older build may lack
+# lib(tolerate=...): the detuning, polarization, bandwidth, backscatter and mixing entries, which an older build may lack
 OPTIONAL = frozenset((
+    "cbet_mix_work_bytes", "cbet_mix_residual", "cbet_mix_apply", "cbet_mix_coefficients", "cbet_mix_residual_host",
+    "cbet_mix_apply_host",
     "cbet_context_set_detuning", "cbet_context_detuning", "cbet_exchange_matrix_host_shifted",
     "cbet_context_set_polarization", "cbet_context_polarization", "cbet_exchange_matrix_host_polarized",
     "cbet_context_set_bandwidth", "cbet_context_bandwidth", "cbet_exchange_matrix_host_banded",
@@ -1319,6 +1327,71 @@ def backscatter_host(samples, turns, beams, fields, ne3d, shifts, params, gain_p
                                        _addr(gamma) if gamma.size else _addr(one), _addr(rays) if nitems else _addr(one),
                                        C.byref(params), _byref(gain_params)))
     return gamma, rays
+
+
+# ---- Anderson mixing of the gain iterate --------------------------------------------------------
+MIX_MAX_DEPTH, MIX_SPAN, MIX_MAX_GROUPS = 4, 2048, 2048        # CBET_MIX_* of the header
+
+
+def _pointers(arrays):
+    """The addresses of `arrays` as a C array of pointers (None for an empty list); keep it alive across the call."""
+    return (C.c_void_p * len(arrays))(*[_addr(a) for a in arrays]) if len(arrays) else None
+
+
+def _numel(a):
+    return int(a.numel()) if hasattr(a, "numel") else int(a.size)
+
+
+def mix_work_bytes(n):
+    """cbet_mix_work_bytes: device bytes of the `work` array of mix_residual for arrays of n doubles (0 for n < 0)."""
+    return int(lib().cbet_mix_work_bytes(n))
+
+
+def mix_residual(y, x, f, f_held, row, work, n=None, stream=None):
+    """cbet_mix_residual on device arrays of n doubles (default: y's size): f = y - x, and into `row` (device, len(f_held) + 1
+    doubles) the dot products of f with every held residual of the list f_held (oldest first) and with itself."""
+    held = _pointers(f_held)
+    _check(lib().cbet_mix_residual(_addr(y), _addr(x), _addr(f), held, len(f_held), _numel(y) if n is None else n, _addr(row),
+                                   _addr(work), _addr(stream)))
+
+
+def mix_apply(y_held, alpha, x_out, x_keep=None, n=None, stream=None):
+    """cbet_mix_apply on device arrays of n doubles (default: x_out's size): sum_j alpha[j] y_held[j], oldest first, into x_out
+    (which may be one of y_held) and x_keep (or None).  alpha: len(y_held) host floats."""
+    al = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    if al.size != len(y_held):
+        raise ValueError("mix_apply takes one coefficient per held iterate, got %d for %d" % (al.size, len(y_held)))
+    held = _pointers(y_held)
+    _check(lib().cbet_mix_apply(held, _dptr(al) if al.size else None, len(y_held), _numel(x_out) if n is None else n, _addr(x_out),
+                                _addr(x_keep), _addr(stream)))
+
+
+def mix_coefficients(gram):
+    """cbet_mix_coefficients: (alpha float64 [count], dropped) from the count x count Gram matrix of the held residuals, oldest
+    first.  Pure host arithmetic: the same bytes on every rank that passes the same numbers."""
+    g = np.ascontiguousarray(gram, dtype=np.float64)
+    count = g.shape[0] if g.ndim == 2 and g.shape[0] == g.shape[1] else 0
+    alpha, dropped = np.zeros(max(count, 1)), C.c_int(0)
+    _check(lib().cbet_mix_coefficients(_dptr(g) if g.size else None, count, _dptr(alpha), C.byref(dropped)))
+    return alpha, int(dropped.value)
+
+
+def mix_residual_host(y, x, f, f_held, n=None):
+    """cbet_mix_residual_host, the host twin on contiguous float64 numpy arrays: writes f, returns the row [len(f_held) + 1]."""
+    row = np.zeros(len(f_held) + 1)
+    held = _pointers(f_held)
+    _check(lib().cbet_mix_residual_host(_addr(y), _addr(x), _addr(f), held, len(f_held), _numel(y) if n is None else n, _dptr(row)))
+    return row
+
+
+def mix_apply_host(y_held, alpha, x_out, x_keep=None, n=None):
+    """cbet_mix_apply_host, the host twin on contiguous float64 numpy arrays (x_out may be one of y_held)."""
+    al = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    if al.size != len(y_held):
+        raise ValueError("mix_apply_host takes one coefficient per held iterate, got %d for %d" % (al.size, len(y_held)))
+    held = _pointers(y_held)
+    _check(lib().cbet_mix_apply_host(held, _dptr(al) if al.size else None, len(y_held), _numel(x_out) if n is None else n,
+                                     _addr(x_out), _addr(x_keep)))
 
 
 # ---- deposit grids as cbet_sph_modes and cbet_mesh_deposit take them ------------------------------------------------

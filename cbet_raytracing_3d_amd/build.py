@@ -13,11 +13,11 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcbet_mi355x.so")
-SOURCES = ["cbet_kernels.hip", "cbet_trace_window.hip", "cbet_trace_exit.hip", "cbet_trace_path.hip", "cbet_backscatter.hip", "cbet_grid_kernels.hip", "cbet_lpi.hip", "cbet_sph_modes.hip",
+SOURCES = ["cbet_kernels.hip", "cbet_trace_window.hip", "cbet_trace_exit.hip", "cbet_trace_path.hip", "cbet_backscatter.hip", "cbet_grid_kernels.hip", "cbet_lpi.hip", "cbet_mix.hip", "cbet_sph_modes.hip",
            "cbet_target.hip", "cbet_mesh.hip", "cbet_mesh_deposit.hip", "cbet_params.cpp", "cbet_context.cpp", "cbet_tables_abi.cpp", "cbet_trace_abi.cpp", "cbet_gain_abi.cpp",
            "cbet_host.cpp", "cbet_output.cpp", "cbet_sph_host.cpp", "cbet_target_host.cpp", "cbet_mesh_host.cpp", "cbet_mesh_deposit_host.cpp",
-           "cbet_exchange_host.cpp", "cbet_lpi_host.cpp", "cbet_backscatter_host.cpp"]
-HEADERS = [os.path.join(CSRC, "cbet_device.h"), os.path.join(CSRC, "cbet_host_internal.h"), os.path.join(CSRC, "cbet_relocate.h"), os.path.join(CSRC, "cbet_trace_common.h"), os.path.join(CSRC, "cbet_trace_diag.h"), os.path.join(CSRC, "cbet_hd.h"), os.path.join(CSRC, "cbet_node_model.h"), os.path.join(CSRC, "cbet_node_kernel.h"), os.path.join(CSRC, "cbet_target_model.h"), os.path.join(CSRC, "cbet_mesh_model.h"), os.path.join(CSRC, "cbet_state_model.h"), os.path.join(CSRC, "cbet_mesh_deposit_model.h"), os.path.join(CSRC, "cbet_gain_model.h"), os.path.join(CSRC, "cbet_lpi_model.h"), os.path.join(CSRC, "cbet_sbs_model.h"), os.path.join(ROOT, "include", "cbet_mi355x.h"),
+           "cbet_exchange_host.cpp", "cbet_lpi_host.cpp", "cbet_backscatter_host.cpp", "cbet_mix_host.cpp"]
+HEADERS = [os.path.join(CSRC, "cbet_device.h"), os.path.join(CSRC, "cbet_host_internal.h"), os.path.join(CSRC, "cbet_relocate.h"), os.path.join(CSRC, "cbet_trace_common.h"), os.path.join(CSRC, "cbet_trace_diag.h"), os.path.join(CSRC, "cbet_hd.h"), os.path.join(CSRC, "cbet_node_model.h"), os.path.join(CSRC, "cbet_node_kernel.h"), os.path.join(CSRC, "cbet_target_model.h"), os.path.join(CSRC, "cbet_mesh_model.h"), os.path.join(CSRC, "cbet_state_model.h"), os.path.join(CSRC, "cbet_mesh_deposit_model.h"), os.path.join(CSRC, "cbet_gain_model.h"), os.path.join(CSRC, "cbet_lpi_model.h"), os.path.join(CSRC, "cbet_sbs_model.h"), os.path.join(CSRC, "cbet_mix_model.h"), os.path.join(ROOT, "include", "cbet_mi355x.h"),
            os.path.join(ROOT, "include", "cbet_omega_beams.h")]
 
 # -ffp-contract=off: a ray's fp64 arithmetic must be the reference's operation sequence (no fused

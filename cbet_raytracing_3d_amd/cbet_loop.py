@@ -50,6 +50,52 @@ class _DeviceCbetEngine:
                             shard_index=shard_index, shard_count=shard_count)
         return self.beam_gain
 
+    # ---- Anderson mixing of the all-reduce loop's gain (cbet_fixed_point(mixing=depth))
+    def mix_begin(self, depth):
+        """2 depth + 3 gain stacks: depth + 1 slots for the held iterates y (the live `gain` is one of them, rotated by
+        reference: no copy per pass), depth + 1 for the held residuals f, and x_keep, the iterate the update overwrites."""
+        g = self.gain
+        self._mix_depth = depth
+        self._mix_y_free = [torch.empty_like(g) for _ in range(depth)]
+        self._mix_f_free = [torch.empty_like(g) for _ in range(depth + 1)]
+        self._mix_x = g.clone()
+        self._mix_y, self._mix_f = [], []          # held, oldest first
+        self._mix_row = torch.zeros(api.MIX_MAX_DEPTH + 1, dtype=torch.float64, device=g.device)
+        self._mix_work = torch.empty(max(1, api.mix_work_bytes(g.numel()) // 8), dtype=torch.float64, device=g.device)
+        self.mix_bytes = 8 * g.numel() * (2 * depth + 3)
+
+    def mix_residual(self):
+        """`gain` holds y = the update of x_keep: f = y - x_keep into a free slot, and its dot products with the held
+        residuals and itself (device tensor [held + 1])."""
+        self._mix_pending = self._mix_f_free.pop()
+        api.mix_residual(self.gain, self._mix_x, self._mix_pending, self._mix_f, self._mix_row, self._mix_work,
+                         stream=self.tr._stream())
+        return self._mix_row[:len(self._mix_f) + 1]
+
+    def mix_apply(self, alpha):
+        """Push (gain, f), keep the newest len(alpha) entries, and make `gain` (and x_keep) their combination.  With every
+        y slot held the result goes into the oldest, which retires."""
+        self._mix_y.append(self.gain)
+        self._mix_f.append(self._mix_pending)
+        while len(self._mix_y) > len(alpha):
+            self._mix_y_free.append(self._mix_y.pop(0))
+            self._mix_f_free.append(self._mix_f.pop(0))
+        retire = len(self._mix_y) > self._mix_depth
+        out = self._mix_y[0] if retire else self._mix_y_free.pop()
+        api.mix_apply(self._mix_y, alpha, out, self._mix_x, stream=self.tr._stream())
+        if retire:
+            self._mix_y.pop(0)
+            self._mix_f_free.append(self._mix_f.pop(0))
+        self.gain = out
+
+    def mix_end(self):
+        """A caller's gain= tensor holds the result (one copy, unless the live slot is that tensor); the slots are dropped."""
+        if self._gain is not None and self.gain is not self._gain:
+            self._gain.copy_(self.gain)
+            self.gain = self._gain
+        for name in ("_mix_y_free", "_mix_f_free", "_mix_x", "_mix_y", "_mix_f", "_mix_row", "_mix_work", "_mix_pending"):
+            self.__dict__.pop(name, None)
+
     # ---- slab-owned loop: own beams [b0, b1) over the whole grid, all beams over the own planes [x0, x1)
     def begin_beams(self, b0, b1):
         """This rank's beams over the whole grid (their fields are complete here without any reduction) and the two
@@ -200,7 +246,133 @@ def _agree(t, group, world_size):
     return t.detach().cpu()
 
 
-def cbet_fixed_point(engine, gain_params, rank=0, world_size=1, group=None):
+class HostMixing:
+    """mix_begin / mix_residual / mix_apply / mix_end over the host twins (cbet_mix_residual_host, cbet_mix_apply_host), for an
+    engine of cbet_fixed_point whose `gain` lives in host memory: a numpy array (replaced by the new iterate) or a CPU
+    tensor (written in place).  Mix it into the engine's class; the engine's own update may write `gain` in place or
+    replace it -- every held array here is a copy."""
+
+    @staticmethod
+    def _mix_flat(g):
+        a = g if isinstance(g, np.ndarray) else g.detach().numpy()
+        return np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+
+    def mix_begin(self, depth):
+        self._mix_depth = depth
+        self._mix_x = self._mix_flat(self.gain).copy()      # x_keep: the iterate the coming update starts from
+        self._mix_y, self._mix_f = [], []                   # held, oldest first
+        self.mix_bytes = 8 * self._mix_x.size * (2 * depth + 3)
+
+    def mix_residual(self):
+        y = self._mix_flat(self.gain).copy()
+        f = np.empty_like(y)
+        row = api.mix_residual_host(y, self._mix_x, f, self._mix_f)
+        self._mix_pending = (y, f)
+        return torch.from_numpy(row)
+
+    def mix_apply(self, alpha):
+        y, f = self._mix_pending
+        self._mix_y.append(y)
+        self._mix_f.append(f)
+        del self._mix_y[:len(self._mix_y) - len(alpha)], self._mix_f[:len(self._mix_f) - len(alpha)]
+        retire = len(self._mix_y) > self._mix_depth
+        out = self._mix_y[0] if retire else np.empty_like(y)      # (the device engine's slot rule, aliasing included)
+        api.mix_apply_host(self._mix_y, alpha, out, self._mix_x)
+        if retire:
+            del self._mix_y[0], self._mix_f[0]
+        if isinstance(self.gain, np.ndarray):
+            self.gain = self._mix_x.reshape(self.gain.shape).copy()
+        else:
+            self.gain.copy_(torch.from_numpy(self._mix_x).reshape(self.gain.shape))
+
+    def mix_end(self):
+        for name in ("_mix_x", "_mix_y", "_mix_f", "_mix_pending"):
+            self.__dict__.pop(name, None)
+
+
+def _check_mixing(mixing):
+    if isinstance(mixing, bool) or not isinstance(mixing, (int, np.integer)) or not 0 <= mixing <= api.MIX_MAX_DEPTH:
+        raise ValueError("mixing is the Anderson depth, an integer 0 .. %d, got %r" % (api.MIX_MAX_DEPTH, mixing))
+    return int(mixing)
+
+
+class _MixState:
+    """The host side of the Anderson mixing of cbet_fixed_point: the Gram matrix of the held residuals,
+    the restart rule and the report.  Every rank runs it on the same numbers (rank 0's Gram row), so coefficients, drops and
+    restarts are identical everywhere."""
+
+    def __init__(self, depth, engine):
+        self.depth, self.engine = depth, engine
+        self.gram = np.zeros((0, 0))
+        self.mixed = False                 # the step that produced the current iterate combined more than one entry
+        self.rep = {"depth": depth, "held": [], "restarts": 0, "dropped": 0, "residual_l2": [], "alpha": [],
+                    "alpha_history": [], "bytes": int(getattr(engine, "mix_bytes", 0))}
+
+    def note(self, row):
+        """Steps 3-5 of a pass: the agreed Gram row {<f_n, f_j> for the held j, <f_n, f_n>} -> restart or not, push."""
+        row = np.asarray(row, dtype=np.float64).reshape(-1)
+        held, ff = self.gram.shape[0], float(row[-1])
+        assert row.size == held + 1, (row.size, held)
+        if self.mixed and ff > float(self.gram[-1, -1]):       # the residual grew after a mixed step: start over
+            self.gram, held = np.zeros((0, 0)), 0
+            row = row[-1:]
+            self.rep["restarts"] += 1
+        g = np.zeros((held + 1, held + 1))
+        g[:held, :held] = self.gram
+        g[held, :] = row
+        g[:, held] = row
+        self.gram = g
+        self.rep["held"].append(held + 1)
+        self.rep["residual_l2"].append(float(np.sqrt(ff)))
+
+    def step(self):
+        """Steps 6-7: the coefficients of the held entries, the engine's combination, the oldest entry retired when all
+        depth + 1 are held (its slot takes the new iterate)."""
+        alpha, dropped = api.mix_coefficients(self.gram)
+        alpha = alpha[dropped:]
+        self.gram = self.gram[dropped:, dropped:]
+        self.rep["dropped"] += dropped
+        self.engine.mix_apply(alpha)
+        self.mixed = alpha.size > 1
+        if self.gram.shape[0] > self.depth:
+            self.gram = self.gram[1:, 1:]
+        self.rep["alpha"] = [float(a) for a in alpha]
+        self.rep["alpha_history"].append(self.rep["alpha"])
+
+
+def _fixed_point_mixed(engine, gain_params, rank, world_size, group, depth):
+    """cbet_fixed_point with Anderson mixing of depth `depth` >= 1 on the passes with frozen directions: the plain loop's
+    passes, each followed by the residual pass and (unless it converged or was the last) the mixed step."""
+    from .tracer import shard_of_rank
+    si, sc = shard_of_rank(rank, world_size)
+    force = getattr(engine, "force_collectives", False)
+    engine.begin()
+    rep = _new_report()
+    mix = None
+    try:
+        for it in range(gain_params.max_passes):
+            full = it < gain_params.direction_passes
+            fields = engine.field_passes(it > 0, si, sc, full)
+            if world_size > 1 or force:
+                allreduce_grid(fields if full else fields[0], group, force)
+            if not full and mix is None:
+                engine.mix_begin(depth)            # (before the update: it keeps the iterate the update overwrites)
+                mix = _MixState(depth, engine)
+            done = _note_pass(rep, it, _agree(engine.update_gain(fields, not full), group, world_size), gain_params)
+            if mix is not None:
+                mix.note(_agree(engine.mix_residual(), group, world_size).numpy())
+            if done:
+                break
+            if mix is not None and it + 1 < gain_params.max_passes:      # (the last pass leaves y_n, as the plain loop does)
+                mix.step()
+    finally:
+        if mix is not None:
+            engine.mix_end()
+    rep["mixing"] = mix.rep if mix is not None else _MixState(depth, engine).rep
+    return _note_balance(rep, engine.deposit(si, sc), group, world_size, force)
+
+
+def cbet_fixed_point(engine, gain_params, rank=0, world_size=1, group=None, mixing=0):
     """The CBET fixed-point iteration over `world_size` ranks (parity unpinned).
 
     Every pass: each rank deposits the fields of ITS share of the ray bundles (the plain pass's sharding) -- all four
@@ -213,7 +385,21 @@ def cbet_fixed_point(engine, gain_params, rank=0, world_size=1, group=None):
         begin(); field_passes(use_gain, shard_index, shard_count, full) -> fields tensor;
         update_gain(fields, frozen) -> tensor {sum |dK|, sum |K|}; deposit(shard_index, shard_count) -> beam_gain tensor
     (the device engine is RayTracer.cbet_solve's; the CPU tests drive this loop with an oracle engine).
-    Returns {passes, converged, change, beam_gain, imbalance}."""
+    Returns {passes, converged, change, beam_gain, imbalance}.
+
+    mixing = depth 1 .. 4: Anderson mixing of the gain iterate on the passes with frozen directions.
+    The update's own step y = x + relax (K(x) - x) and its convergence test are unchanged; behind them the residual
+    f = y - x is formed, the last depth + 1 pairs (y, f) are held, and the next pass starts from the combination
+    sum alpha_j y_j whose residual combination is smallest (sum alpha_j = 1).  A residual that grows after a mixed step
+    clears the history (a restart: the next step is the plain step, bit for bit); an entry the Gram matrix cannot tell
+    from the newer ones is dropped.  The engine then also supplies mix_begin(depth); mix_residual() -> tensor
+    {<f, f_j> for the held j, <f, f>}; mix_apply(alpha); mix_end() -- the device engine with the kernels of cbet_mix.hip,
+    a host engine by mixing HostMixing in -- and HOLDS 2 depth + 3 gain stacks instead of one: 91 GB at depth 4 for
+    256^3 / 60 beams (8.24 GB each), beside the 41.2 GB workspace.  Rank 0's Gram row is broadcast and every rank solves
+    for the same coefficients.  The report gains "mixing": {depth, held (entries per pass), restarts, dropped,
+    residual_l2 (per frozen pass), alpha (of the last step), alpha_history, bytes}."""
+    if _check_mixing(mixing):
+        return _fixed_point_mixed(engine, gain_params, rank, world_size, group, mixing)
     from .tracer import shard_of_rank        # (tracer.py imports this module)
     si, sc = shard_of_rank(rank, world_size)
     force = getattr(engine, "force_collectives", False)   # one rank, but every collective really runs (RCCL smoke test)

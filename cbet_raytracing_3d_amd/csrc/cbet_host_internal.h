@@ -210,6 +210,11 @@ int sbs_check(const char *who, long nitems, const int *beams, const double *fiel
               const double *gamma, const cbet_ray_sbs *rays, const cbet_params *p, const cbet_gain_params *g);
 SbsArgs sbs_args(const GainArgs &g, const int *beams, const int *raynums, long nitems, int nrays, const double *shifts, int nshift,
                  double *gamma, cbet_ray_sbs *rays);
+// The refusals the Anderson-mixing entries share with their host twins (cbet_mix_host.cpp, no HIP call),
+// `who` in front, each naming the first offence.
+int mix_residual_check(const char *who, const double *y, const double *x, const double *f, const double *const *f_held, int h,
+                       long n, const double *row);
+int mix_apply_check(const char *who, const double *const *y_held, const double *alpha, int count, long n, const double *x_out);
 
 // ---- launches that cross files (cbet_tables_abi.cpp, cbet_trace_abi.cpp, cbet_gain_abi.cpp) ---------------------
 // The context's own device table of `doubles` doubles (own_node_table: `components` per node) in *slot, allocated on the first call (not capturable).

@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import api
-from .cbet_loop import (_DeviceCbetEngine, _agree, _frozen, _parts, balanced_slabs, cbet_fixed_point,  # noqa: F401
-                        cbet_fixed_point_slabs, gain_update_weights, slab_pieces)
+from .cbet_loop import (HostMixing, _check_mixing, _DeviceCbetEngine, _agree, _frozen, _parts, balanced_slabs,  # noqa: F401
+                        cbet_fixed_point, cbet_fixed_point_slabs, gain_update_weights, slab_pieces)
 from .exchange import SegmentPlan, _pack_rows_cpu, _segment_rows, _SlabExchanger  # noqa: F401
 from .pipeline import SweepPipeline, allreduce_grid, reduce_scatter_grid, row_pitch  # noqa: F401
 
@@ -635,11 +635,17 @@ class RayTracer:
         return gain
 
     def cbet_solve(self, edep, gain_params, rank=0, world_size=1, group=None, fields=None, gain=None, slabs=False,
-                   force_collectives=False, sparse=False, **slab_options):
+                   force_collectives=False, sparse=False, mixing=0, **slab_options):
         """The CBET iteration, one rank's share (cbet_fixed_point -- or, with slabs=True, cbet_fixed_point_slabs,
         the exchange sized for xGMI -- with this device as the engine): the deposition pass is ADDED into
         `edep` (not reduced here: use allreduce_grid).  Single-rank callers can use the native loop instead:
-        api.cbet_solve."""
+        api.cbet_solve.
+        mixing = 1 .. 4: Anderson mixing of that depth on the all-reduce loop's gain (cbet_fixed_point; rep["mixing"]).  The
+        device then holds 2 mixing + 3 gain stacks instead of one -- 91 GB at depth 4 for 256^3 / 60 beams, beside the
+        41.2 GB workspace -- and a caller's gain= tensor receives the result with one copy at the end.  Not with slabs=True."""
+        mixing = _check_mixing(mixing)
+        if mixing and slabs:
+            raise ValueError("mixing is the all-reduce loop's: slabs=True with mixing = %d is not supported" % mixing)
         self._no_target("cbet_solve")
         if self._flow_is("target"):
             self._flow_gp = self._copy_gp(gain_params)      # the engine's tabulate() fills the flow table from this ramp
@@ -658,8 +664,8 @@ class RayTracer:
                                "runs_per_exchange": plan.runs_out if plan is not None else None,
                                "dense_fraction": (8.0 * plan.runs_out / max(1, plan.dense_out)) if plan is not None else 1.0}
         else:
-            rep = cbet_fixed_point(engine, gain_params, rank, world_size, group)
-        rep["gain"] = engine.gain      # all beams (all-reduce loop) / this rank's beams (slab loop), whole grid
+            rep = cbet_fixed_point(engine, gain_params, rank, world_size, group, mixing=mixing)
+        rep["gain"] = engine.gain     # all beams (all-reduce loop) / this rank's beams (slab loop), whole grid
         return rep
 
     # ---- exit pass (include/cbet_mi355x.h cbet_trace_exits) -----------------

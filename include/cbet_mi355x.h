@@ -1225,6 +1225,58 @@ int cbet_backscatter_host(const cbet_path_sample *samples, const cbet_ray_turn *
                           int pol, const double *shifts, int nshift, double *gamma, cbet_ray_sbs *rays, const cbet_params *p,
                           const cbet_gain_params *g);
 
+/* ---- Anderson mixing of the gain iterate -------------------------------------------------- */
+/*
+ * The streaming work of Anderson mixing over plain arrays of n doubles (the gain stack of a CBET solve is one such array):
+ * nothing here knows a grid, a beam or a context.  A fixed-point iteration x -> y(x) holds up to CBET_MIX_MAX_DEPTH + 1
+ * entries (y_j, f_j = y_j - x_j), OLDEST FIRST in every list below, and its next iterate is sum_j alpha_j y_j with the alpha
+ * that minimise || sum_j alpha_j f_j ||_2 under sum_j alpha_j = 1.  Every statement is ONE IEEE fp64 operation per written
+ * operator in the written order (csrc/cbet_mix_model.h, no fused multiply-add), for the kernels and the host twins alike.
+ *
+ * cbet_mix_residual: f[e] = y[e] - x[e] for e < n, and the Gram row
+ *     row[j] = sum_e f[e] * f_held[j][e]   (j < h, the h held residuals)        row[h] = sum_e f[e] * f[e]
+ * into row (h + 1 doubles; DEVICE memory for cbet_mix_residual, OVERWRITTEN).  The order of every sum follows from n and
+ * the ELEMENT INDEX alone: element e belongs to span e / CBET_MIX_SPAN, spans go round-robin to
+ * G = min(ceil(n / CBET_MIX_SPAN), CBET_MIX_MAX_GROUPS) workgroups of 256 threads, thread t of a workgroup takes the elements
+ * 2 (256 i + t) and 2 (256 i + t) + 1 of a span (i = 0 .. CBET_MIX_SPAN / 512 - 1) and adds its products in ascending element
+ * order from +0.0; the 64 lanes of a wavefront are summed by six butterfly steps (s = s + s[lane ^ 32], ^ 16, ... ^ 1), the
+ * four wavefronts in order, one partial row per workgroup goes to `work` (cbet_mix_work_bytes(n) bytes of device memory; 0
+ * for n < 0; no atomics), and a second kernel of one workgroup sums the partial rows (thread t rows t, t + 256, ... in
+ * order, then the same butterfly and wavefront order).  Nothing depends on the device or on an address: two calls give the
+ * same bytes, a view that starts anywhere inside an allocation gives the bytes of an aligned copy, and the host twin,
+ * which walks the same order, gives the same bytes as the device.  Arrays need the alignment of a double only (a thread's
+ * pair of elements moves as one 16-byte access at any such address, which changes no sum).  f must not overlap any input.
+ *
+ * cbet_mix_apply: x[e] = alpha[0] * y_held[0][e], then x[e] = x[e] + alpha[j] * y_held[j][e] for j = 1 .. count - 1, stored
+ * to x_out[e] and, when x_keep is not NULL, to x_keep[e].  alpha: count HOST doubles, captured at the call.  count = 1 with
+ * alpha = {1.0} copies y_held[0]'s bytes.  x_out may BE one of the y_held arrays (the slot that retires): every element is
+ * read from all of them before it is written; any other overlap is the caller's error.
+ *
+ * cbet_mix_coefficients: pure host arithmetic, the same bytes wherever it runs.  gram: count x count HOST doubles, row-major,
+ * gram[a * count + b] = <f_a, f_b> (only a <= b is read).  With n = count - 1 the newest entry and d entries dropped, the
+ * differences against the newest, H_ab = G_ab - G_an - G_bn + G_nn and c_a = G_nn - G_an over a, b = n - 1 down to d, are
+ * factored by Cholesky from the newest difference to the oldest, gamma solves H gamma = c, alpha_a = gamma_a and
+ * alpha_n = 1.0 - sum_a gamma_a (summed newest to oldest).  A pivot that is not > 1e-12 * its own diagonal entry H_aa is
+ * lost (the Gram entries are known to that relative bound): the OLDEST held entry is dropped (d = d + 1) and the system is
+ * solved again.  alpha[0 .. d) = 0.0; *dropped = d.  count = 1 gives alpha = {1.0}.
+ *
+ * CBET_EINVAL with cbet_last_error, before any device work: h outside 0 .. CBET_MIX_MAX_DEPTH, count outside
+ * 1 .. CBET_MIX_MAX_DEPTH + 1, n < 0, a NULL array (f_held may be NULL when h == 0; x_keep may be NULL; work may be NULL
+ * when n == 0).  The device entries run on the calling thread's current device, enqueue on `stream` and do not synchronise.
+ */
+#define CBET_MIX_MAX_DEPTH 4
+#define CBET_MIX_SPAN 2048
+#define CBET_MIX_MAX_GROUPS 2048
+size_t cbet_mix_work_bytes(long n);
+int cbet_mix_residual(const double *y, const double *x, double *f, const double *const *f_held, int h, long n, double *row,
+                      void *work, void *stream);
+int cbet_mix_apply(const double *const *y_held, const double *alpha, int count, long n, double *x_out, double *x_keep,
+                   void *stream);
+int cbet_mix_coefficients(const double *gram, int count, double *alpha, int *dropped);
+int cbet_mix_residual_host(const double *y, const double *x, double *f, const double *const *f_held, int h, long n,
+                           double *row);
+int cbet_mix_apply_host(const double *const *y_held, const double *alpha, int count, long n, double *x_out, double *x_keep);
+
 /* ---- mode spectra of the deposit ---------------------------------------------------------- */
 /*
  * How uniformly the energy is deposited around a centre: the real spherical-harmonic coefficients of each grid on
