@@ -288,8 +288,9 @@ __device__ __forceinline__ int run_hk(int run, int c, int sft) { return LC * run
 
 // pref * P(eta_ij) as ONE quotient: with N = -(q . u) and D = |q| cs + 1e-10 (eta = N / D),
 //   P = iaw^2 eta / ((eta^2 - 1)^2 + iaw^2 eta^2) = iaw^2 N D^3 / ((N^2 - D^2)^2 + iaw^2 N^2 D^2),
-// square root and reciprocal by the hardware estimates and Newton steps (a few ulp; the sums of the symmetric kernels are
-// grouped differently from the ordered kernel's anyway).  q = 0 (a beam against itself, or two parallel beams) gives
+// square root and reciprocal by the hardware estimates and Newton steps (measured: K within 5.7 units of 2^-53 S of a 200-bit
+// model where the ordered statements reach 4.7, DESIGN.md section 9, "Per-pair accuracy"; the sums of the symmetric kernels
+// are grouped differently from the ordered kernel's anyway).  q = 0 (a beam against itself, or two parallel beams) gives
 // N = 0 over D^4 = 1e-40: zero, as in the ordered kernel.
 // DETUNE: N = -(q . u) + dw with dw = w_j - w_i, the pair's beat frequency.  Two parallel beams of
 // different colour would give N = dw over D = 1e-10; the ordered kernel does not evaluate them (pair_present), so here dw
@@ -367,8 +368,8 @@ __device__ __forceinline__ double cell_rk(double k0, double rt)
 }
 
 // The clamp of the pair-once kernel on the value pair_gain_fast returned: with w^2 = (gn Ii) (gn Ij)
-// beyond lim^2 the gain is scaled by lim / w = lim rsqrt(w^2) -- the estimate and two Goldschmidt steps, a few ulp like the
-// pair function itself; squares are compared, and gn comes back untouched where the limit is not reached.
+// beyond lim^2 the gain is scaled by lim / w = lim rsqrt(w^2) -- the estimate and two Goldschmidt steps, the clamped K
+// within 4.9 such units like the pair function itself; squares are compared, and gn comes back untouched where the limit is not reached.
 __device__ __forceinline__ double saturate_fast(double gn, double Ii, double Ij, double lim)
 {
     const double w2 = (gn * Ii) * (gn * Ij);

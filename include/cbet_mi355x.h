@@ -728,7 +728,8 @@ const double *cbet_cbet_workspace_gain(const cbet_params *p, const void *workspa
  * A pair that does not reach the limit keeps its bits (the update without a limit adds (pref * P) * Ij).  With a state table
  * pref holds the node's gain_const, as without a limit.  The pair-once kernel applies ONE factor per unordered pair to its
  * pair function's value before both addends, comparing squares and scaling by lim rsqrt(w^2) from the hardware estimate
- * (a few ulp, like its pair function); where the limit is not reached the value is untouched.
+ * (measured: K_i within 4.9 units of 2^-53 S_i of a 200-bit model where the ordered statements reach 4.7 -- S_i the
+ * condition-aware scale of DESIGN.md section 9, "Per-pair accuracy"); where the limit is not reached the value is untouched.
  *
  * cbet_context_set_saturation: dn_max > 0 sets the limit, 0 = none (a new context's default); negative, NaN or infinite:
  * CBET_EINVAL naming the offence.  Host-side state only, like cbet_context_set_state: it applies to launches made after it.
@@ -767,7 +768,8 @@ int cbet_pair_amplitude(const double *fields, const double *ne3d, double *amp, i
  * negated upper one and its diagonal as 0.  `gross` is the same shape (upper triangle added into, lower mirrored, diagonal
  * 0), or NULL.  ne3d NULL = the context's table.  Stream-ordered, no synchronisation, no allocation.
  * Every unordered pair is evaluated once per cell with the pair-once gain kernel's pair function (and its clamp): the
- * arithmetic of the kernel cbet_cbet_solve runs, a few ulp per pair from the ordered statements.  Per-workgroup partial
+ * arithmetic of the kernel cbet_cbet_solve runs, per pair within 5.7 units of 2^-53 S of a 200-bit model where the ordered
+ * statements stay within 4.7 ("Per-pair accuracy").  Per-workgroup partial
  * tables are written to `work` and summed in workgroup order by a second kernel: no floating-point atomics, so two calls on
  * the same inputs give the same bits, on any device -- the number of workgroups is min(rows, CBET_EXCHANGE_MAX_GROUPS) with
  * rows = (hx_hi - hx_lo) (ny + 2), never the device's size.  `work` holds [groups][2][nbeams (nbeams - 1) / 2] doubles;
@@ -798,7 +800,8 @@ int cbet_exchange_matrix_host(const double *fields, const double *ne3d, double *
  * beat frequency, so the resonance of the pair gain G_ij = pref P(eta_ij) becomes
  *     eta_ij = ((0.0 - (qx*ux + qy*uy + qz*uz)) + (w_j - w_i)) / (kiaw*cs + 1e-10)
  * in the ordered kernel -- every written operator ONE IEEE fp64 operation in the written order, no fused multiply-add --
- * and N = -(q . u) + (w_j - w_i) in the pair function of the pair-once kernels (a few ulp from it, as without shifts).
+ * and N = -(q . u) + (w_j - w_i) in the pair function of the pair-once kernels (measured: both within 4.3 units of 2^-53 S of
+ * a 200-bit model, as without shifts: DESIGN.md section 9, "Per-pair accuracy").
  * Identities: beam i gains where its frequency in the plasma frame is the lower one, so in still plasma the red-shifted beam
  * gains; (w_i - w_j) = -(w_j - w_i) exactly, so G_ji = -G_ij stays exact and a cell's exchange sum_i I_i K_i still cancels,
  * with or without a saturation limit; equal shifts add an exact zero and give the bits of no shifts; two exactly parallel
@@ -838,7 +841,8 @@ int cbet_exchange_matrix_host_shifted(const double *fields, const double *ne3d, 
  *     f   = 0.25 * (1.0 + cth*cth)
  *     g   = (pref * P(eta_ij)) * f
  * -- every written operator ONE IEEE fp64 operation in the written order, no fused multiply-add -- while the pair-once
- * kernels form cth = 1 - |k_j - k_i|^2 / (2 kmag^2) from the |q|^2 they hold (a few ulp from it).
+ * kernels form cth = 1 - |k_j - k_i|^2 / (2 kmag^2) from the |q|^2 they hold (measured: within 5.7 units of 2^-53 S of a
+ * 200-bit model, the ordered statements within 3.9: DESIGN.md section 9, "Per-pair accuracy").
  * Identities: 1/4 <= f <= 1/2, exactly 1/4 for beams at right angles and 1/2 for parallel or opposed ones; f is the same bits
  * for (i, j) and (j, i), so G_ji = -G_ij stays exact and a cell's exchange sum_i I_i K_i still cancels, with or without a
  * saturation limit; eta is untouched, so detuning composes unchanged; which pairs are present is unchanged.
@@ -882,7 +886,8 @@ int cbet_exchange_matrix_host_polarized(const double *fields, const double *ne3d
  *     for m = 0 .. M-1:   S = S + c_m * (P((N + d_m) / D) + P((N - d_m) / D))
  *     g = pref * S        then the polarization factor, then the saturation clamp, as without a spectrum
  * -- every written operator ONE IEEE fp64 operation in the written order -- and the pair-once kernels the same sum with their
- * quotient form of P (a few ulp from it).  The table is built deterministically: weights normalised by their sum in line
+ * quotient form of P (measured with shifts, smoothing and a 3-line spectrum: within 4.2 units of 2^-53 S of a 200-bit model,
+ * the ordered statements within 2.5: DESIGN.md section 9, "Per-pair accuracy").  The table is built deterministically: weights normalised by their sum in line
  * order; c_0 summed in line order; the differences |o_b - o_a| in fp64 for a < b in ascending order (a, then b); a zero
  * difference adds 2 p_a p_b to c_0; bitwise-equal differences are merged; the entries are sorted by d.
  * Identities: G_ji = -G_ij bit for bit (N -> -N and (-N + d) = -(N - d) exactly, P is odd, the bracket is one commutative
